@@ -19,6 +19,12 @@ reduce-scatter / all-gather plane (fixed S-step gradient delay; hipGraph replay 
 Timing: W untimed warmup steps (include MIOpen tuning and hipGraph capture), then exactly K timed
 steps bracketed by barrier + device synchronize on both sides; the max over ranks is reported.
 Rank 0 prints one JSON line.
+
+A plain run does only that. ``--full`` adds the measurements beside the headline figure, after
+the timed steps: the async plane's push / pull bandwidth and, at N > 1, the RCCL bus bandwidth per
+collective and bucket size. ``--dump-outputs DIR`` writes the last timed step's loss and the
+resulting PS weights as ``DIR/<name>.npy`` (float32, a fixed seeded sample of a large buffer); the
+model init and the batch are seeded, so the inputs are the same from run to run.
 """
 from __future__ import annotations
 
@@ -114,9 +120,18 @@ def parse():
     ap.add_argument("--ckpt-prefix", default="", help="sharded PS checkpoint path prefix")
     ap.add_argument("--ckpt-every", type=int, default=0, help="checkpoint every N steps (async, off the step)")
     ap.add_argument("--resume", default="", help="load PS shards from this checkpoint prefix before training")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements beside the headline figure: the async "
+                         "plane's push / pull bandwidth (async_plane_bw) and, at N > 1, the RCCL bus bandwidths "
+                         "(--comm-probe). A plain run sets up, warms up, times the steps and reports")
     ap.add_argument("--comm-probe", type=int, default=1,
-                    help="N > 1 with RCCL: after the timed steps, measure all-reduce / reduce-scatter / all-gather "
-                         "bus bandwidth vs bucket size over xGMI and report it (comm_probe in the JSON)")
+                    help="with --full, N > 1 with RCCL: after the timed steps, measure all-reduce / reduce-scatter / "
+                         "all-gather bus bandwidth vs bucket size over xGMI and report it (comm_probe in the JSON); "
+                         "0 also skips the async plane's bandwidth probe")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32): "
+                         "loss and weights (the PS weights after every push of the run is applied; above 4 Mi "
+                         "elements a sample at fixed seeded positions)")
     ap.add_argument("--features", default="",
                     help="kernel-path / engine feature overrides for this run, e.g. 'async_direct_pull=0,convn=1' "
                          "(utils/config.py FEATURES; same syntax as PSD_FEATURES, which it replaces)")
@@ -170,6 +185,35 @@ def comm_probe(dev, world: int, sizes_mb=(1, 4, 16, 64, 256), iters: int = 5) ->
         out[f"{mb}MB"] = res
         del x, part
     return out
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB of float32 (the whole dump stays far below 64 MB)
+
+
+def dump_outputs(path: str, ps, loss) -> dict:
+    """Write what the last timed step handed back -- its loss and the PS weights with every push of
+    the run applied -- as ``path/<name>.npy`` (float32). A buffer above DUMP_MAX_ELEMS is sampled at
+    positions drawn once from a fixed seed (they depend only on the buffer's length), so two builds
+    run with the same arguments write comparable files. (The step's gradient buffer is left out: this
+    early in training two runs of one build differ by tens of percent there, from the kernels the
+    autotuner happened to pick and the order of the asynchronous applies.)"""
+    import numpy as np
+
+    if hasattr(ps, "refresh_weights"):  # async plane: the workers hold the weights of their last pull
+        ps.refresh_weights()
+    arrays = {"loss": loss.detach().reshape(1), "weights": ps.params_flat.detach()}
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(20240607)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.index_select(0, idx.to(t.device))
+        arr = t.float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+        shapes[name] = int(arr.size)
+    return shapes
 
 
 def autotune_summary() -> dict:
@@ -404,14 +448,17 @@ def main():
             break
     while hist and hist[-1] == 0 and len(hist) > 1:
         hist.pop()
+    dumped = None
+    if a.dump_outputs and loss is not None and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, ps, loss)
     probe = None
     async_bw = None
-    if mode == "async" and a.comm_probe:
+    if a.full and mode == "async" and a.comm_probe:
         try:
             async_bw = ps.probe_bandwidth()
         except Exception as e:  # noqa: BLE001
             async_bw = {"error": str(e)[:200]}
-    if world > 1 and a.backend == "nccl" and a.comm_probe:
+    if a.full and world > 1 and a.backend == "nccl" and a.comm_probe:
         try:
             probe = comm_probe(dev, world)
         except Exception as e:  # noqa: BLE001 -- a diagnostic must not cost the measurement
@@ -476,6 +523,7 @@ def main():
             "host_cpu_ms_per_step": round(host_cpu_ms, 2),  # rank 0 launching thread (CPU time, not wall)
             "autotune": autotune_summary(),
             "autotune_source": at_src,
+            "full": bool(a.full), "dumped_outputs": dumped,
         }
         line = json.dumps(rec)
         print(line, flush=True)

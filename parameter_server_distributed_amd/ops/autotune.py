@@ -103,13 +103,16 @@ def _agrees(outs: list, ref: list) -> bool:
             continue
         if o.shape != r.shape:
             return False
-        fin = torch.isfinite(r)
-        if not bool(torch.isfinite(o)[fin].all()):
+        # elementwise passes with the reference's non-finite entries masked to 0 (|.| >= 0, so the
+        # maxima over the finite entries are unchanged): gathering o[fin] / r[fin] out of activations of
+        # 10^8..10^9 elements cost ~45 ms per candidate, most of a first training step's autotuning
+        nonfin = ~torch.isfinite(r)
+        if not bool((torch.isfinite(o) | nonfin).all()):
             return False
-        if not bool(fin.any()):
+        if bool(nonfin.all()):
             continue
-        d = float((o[fin] - r[fin]).abs().max())
-        mx = float(r[fin].abs().max())
+        d = float((o - r).abs_().masked_fill_(nonfin, 0.0).max())
+        mx = float(r.abs().masked_fill_(nonfin, 0.0).max())
         # the floor is one fp32 ulp of the reference's scale: an all-zero reference demands zeros
         if d > AGREE_REL * mx + mx * 2.0 ** -23:
             return False

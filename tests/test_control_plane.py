@@ -75,31 +75,33 @@ def test_emit_proto(tmp_path):
     assert "repeated float data = 3;" in txt
 
 
-REF_PROTO = os.environ.get("PSD_REFERENCE_PROTO_DIR", "/root/reference/proto")
+REF_WIRE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_wire")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PROTO), reason="reference .proto files not present")
 @pytest.mark.parametrize("pkg,fname", [("coordinator", "coordinator.proto"),
                                        ("parameter_server", "parameter_server.proto")])
 def test_schema_is_a_wire_superset_of_the_reference_proto(pkg, fname):
-    """Parse the reference's own .proto (read-only) and require every message, field name, field
-    number, scalar/enum/message type, label (repeated or not), enum value and rpc signature to be
-    identical in our proto/psd_*.proto -- names, numbers *and* types (the old test
-    checked hand-copied numbers only)."""
+    """The reference's wire table, recorded by parsing its own .proto with rpc/protoparse.py
+    (tests/golden/reference_wire/<pkg>.json: protoparse.describe() of the file and its package name):
+    every message, field name, field number, scalar/enum/message type, label (repeated or not), enum
+    value and rpc signature must be identical in our proto/psd_*.proto -- names, numbers *and*
+    types (the old test checked hand-copied numbers only)."""
     from parameter_server_distributed_amd.rpc import protoparse
 
-    ref = protoparse.describe(protoparse.parse_file(os.path.join(REF_PROTO, fname)))
+    with open(os.path.join(REF_WIRE, fname.replace(".proto", ".json"))) as f:
+        rec = json.load(f)
+    ref = {k: tuple(v) if isinstance(v, list) else v for k, v in rec["wire"].items()}
+    assert len(ref) >= 30, len(ref)
     ours = protoparse.describe(schema.FILES[pkg])
     diff = {k: (v, ours.get(k)) for k, v in ref.items() if ours.get(k) != v}
     assert not diff, diff
-    ref_fd = protoparse.parse_file(os.path.join(REF_PROTO, fname))
-    assert ref_fd.package == schema.FILES[pkg].package
+    assert rec["package"] == schema.FILES[pkg].package
     # additions are additive: our extra fields never reuse a number the reference message has
     for m in schema.FILES[pkg].message_type:
-        rm = next((x for x in ref_fd.message_type if x.name == m.name), None)
-        if rm is None:
+        if f"message {m.name}" not in ref:
             continue
-        ref_nums = {f.number: f.name for f in rm.field}
+        ref_nums = {v[0]: k.split(".", 1)[1] for k, v in ref.items()
+                    if isinstance(v, tuple) and len(v) == 4 and k.startswith(m.name + ".")}
         for f in m.field:
             assert ref_nums.get(f.number, f.name) == f.name, (m.name, f.name, f.number)
 
