@@ -36,6 +36,10 @@ def main(argv=None):
     ap.add_argument("--ps-shards", type=int, default=0, help="elastic: PS shards (0: one per rank)")
     ap.add_argument("--staleness", type=int, default=0, help="elastic: staleness bound S")
     ap.add_argument("--optimizer", default="momentum")
+    ap.add_argument("--trust-coef", type=float, default=0.001, help="elastic, lars: trust coefficient eta")
+    ap.add_argument("--exclude-1d", action=argparse.BooleanOptionalAction, default=None,
+                    help="elastic: no weight decay (and no trust ratio) on tensors of ndim <= 1; default: on for "
+                         "lars / lamb (async plane only)")
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--bucket-mb", type=float, default=16.0)
     ap.add_argument("--pull-dtype", default="bf16")
@@ -127,7 +131,7 @@ def elastic_main(a) -> int:
     dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
     spec = build_model(a, dev, dtype)
     batch = spec.make_batch(a.batch, dev, seed=1000 + a.worker_id)
-    optim = OptimConfig(a.optimizer, lr=a.lr, momentum=0.9)
+    optim = OptimConfig(a.optimizer, lr=a.lr, momentum=0.9, trust_coef=a.trust_coef, exclude_1d=a.exclude_1d)
     agent = ElasticAgent(a.coordinator, a.worker_id, heartbeat_s=min(a.heartbeat_s, 1.0))
 
     def make_ps(model, transport):

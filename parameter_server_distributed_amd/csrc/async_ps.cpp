@@ -413,6 +413,17 @@ void AsyncEngine::set_shard_state(int shard, at::Tensor master, c10::optional<at
   st.hyper.eps = (float)eps;
 }
 
+void AsyncEngine::set_shard_layers(int shard, std::vector<at::Tensor> layers, double trust_coef) {
+  TORCH_CHECK(shard >= 0 && shard < (int)owners_.size() && owners_[shard] == rank_, "psd async: shard ", shard,
+              " is not owned by rank ", rank_);
+  ShardState& st = shards_[shard];
+  TORCH_CHECK(st.master.defined(), "psd async: set_shard_state first");
+  TORCH_CHECK(!running_, "psd async: set_shard_layers while the engine runs");
+  TORCH_CHECK(!layers.empty(), "psd async: empty layer table");
+  st.layers = std::move(layers);
+  st.trust_coef = trust_coef;
+}
+
 void AsyncEngine::publish_initial(int shard, int64_t version, std::vector<int64_t> clocks) {
   ShardState& st = shards_[shard];
   TORCH_CHECK(st.master.defined(), "psd async: set_shard_state first");
@@ -645,6 +656,15 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
   }
   optim_advance_(st.dyn, st.hyper.beta1, st.hyper.beta2);
   const bool bf16 = esz_ == 2;
+  if (!st.layers.empty()) {  // norm pass + finalize + apply (or the segmented apply alone), same stream, same cap
+    fused_apply_lw_(st.master, g, st.s1.defined() ? c10::optional<at::Tensor>(st.s1) : c10::nullopt,
+                    st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
+                    bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,
+                    st.hyper.momentum, st.hyper.dampening, st.hyper.nesterov, st.hyper.weight_decay, st.hyper.beta1,
+                    st.hyper.beta2, st.hyper.eps, false, st.trust_coef, st.layers, apply_cap_);
+    if (!bf16) st.publish[buf].copy_(st.master);
+    return;
+  }
   fused_apply_(st.master, g, st.s1.defined() ? c10::optional<at::Tensor>(st.s1) : c10::nullopt,
                st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
                bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,

@@ -66,6 +66,10 @@ class AsyncEngine {
   void set_shard_state(int shard, at::Tensor master, c10::optional<at::Tensor> state1, c10::optional<at::Tensor> state2,
                        at::Tensor dyn, int64_t kind, double momentum, double dampening, bool nesterov,
                        double weight_decay, double beta1, double beta2, double eps);
+  // after set_shard_state: the shard's layer table (ops.h lw_table_build for the shard's range) and
+  // the LARS trust coefficient. With a table every apply of the shard goes through fused_apply_lw_
+  // (lars / lamb, or a flat kind with per-tensor weight decay).
+  void set_shard_layers(int shard, std::vector<at::Tensor> layers, double trust_coef);
   // bf16(master) -> publish buffer 0 as the shard's snapshot `version` (blocking); with `clocks`
   // (one per worker) the SSP clocks are restored too (checkpoint resume)
   void publish_initial(int shard, int64_t version = 0, std::vector<int64_t> clocks = {});
@@ -135,6 +139,8 @@ class AsyncEngine {
   struct ShardState {
     at::Tensor master, s1, s2, dyn;
     OptimHyper hyper{};
+    std::vector<at::Tensor> layers;   // layer table (set_shard_layers); empty: the flat apply
+    double trust_coef = 0.001;
     std::vector<at::Tensor> inbox;    // [workers * (S+1)] bf16 views
     std::vector<at::Tensor> publish;  // [nbuf] bf16 views
     std::vector<bool> busy;           // publish buffer is the target of an enqueued apply

@@ -24,6 +24,19 @@ PYBIND11_MODULE(_C, m) {
         py::arg("nesterov") = false, py::arg("weight_decay") = 0.0, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
         py::arg("eps") = 1e-8, py::arg("maximize") = false,
         py::arg("grid_cap") = 0);
+  m.def("fused_apply_lw_", &fused_apply_lw_, py::arg("master"), py::arg("grads"), py::arg("state1"),
+        py::arg("state2"), py::arg("shadow"), py::arg("dyn"), py::arg("kind"), py::arg("momentum") = 0.0,
+        py::arg("dampening") = 0.0, py::arg("nesterov") = false, py::arg("weight_decay") = 0.0, py::arg("beta1") = 0.9,
+        py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("maximize") = false, py::arg("trust_coef") = 0.001,
+        py::arg("layers") = std::vector<at::Tensor>{}, py::arg("grid_cap") = 0);
+  m.def(
+      "lw_table_build",
+      [](const std::vector<int64_t>& offsets, const std::vector<int64_t>& numels, const std::vector<int64_t>& ndims,
+         int64_t n, bool exclude_1d, int64_t align, const std::string& device) {
+        return lw_table_build(offsets, numels, ndims, n, exclude_1d, align, at::Device(device));
+      },
+      py::arg("offsets"), py::arg("numels"), py::arg("ndims"), py::arg("n"), py::arg("exclude_1d"),
+      py::arg("align") = 64, py::arg("device") = "cpu");
   m.def(
       "async_hyper",
       [](int kind, int workers, double momentum, double beta1, double beta2, double weight_decay) {
@@ -179,6 +192,8 @@ PYBIND11_MODULE(_C, m) {
   m.attr("OPT_MOMENTUM") = (int)OPT_MOMENTUM;
   m.attr("OPT_ADAM") = (int)OPT_ADAM;
   m.attr("OPT_ADAMW") = (int)OPT_ADAMW;
+  m.attr("OPT_LARS") = (int)OPT_LARS;
+  m.attr("OPT_LAMB") = (int)OPT_LAMB;
 
   // ---- checkpoint ----
   m.def("save_reference_ckpt", &save_reference_ckpt, py::call_guard<py::gil_scoped_release>());
@@ -253,6 +268,8 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("beta2", &PSConfig::beta2)
       .def_readwrite("eps", &PSConfig::eps)
       .def_readwrite("nesterov", &PSConfig::nesterov)
+      .def_readwrite("trust_coef", &PSConfig::trust_coef)
+      .def_readwrite("exclude_1d", &PSConfig::exclude_1d)
       .def_readwrite("reference_compat", &PSConfig::reference_compat)
       .def_readwrite("staleness_lr_scaling", &PSConfig::staleness_lr_scaling)
       .def_readwrite("async_grad_scale", &PSConfig::async_grad_scale)
@@ -309,6 +326,7 @@ PYBIND11_MODULE(_C, m) {
       .def("local_desc", [](const AsyncEngine& e) { return py::bytes(e.local_desc()); })
       .def("attach_peer", [](AsyncEngine& e, int r, py::bytes d) { e.attach_peer(r, std::string(d)); })
       .def("set_shard_state", &AsyncEngine::set_shard_state)
+      .def("set_shard_layers", &AsyncEngine::set_shard_layers)
       .def("publish_initial", &AsyncEngine::publish_initial, py::arg("shard"), py::arg("version") = 0,
            py::arg("clocks") = std::vector<int64_t>{})
       .def("set_round", &AsyncEngine::set_round)

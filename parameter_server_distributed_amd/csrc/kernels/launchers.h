@@ -19,6 +19,8 @@ enum OptimKind : int32_t {
   OPT_MOMENTUM = 1,   // torch.optim.SGD(momentum, dampening, nesterov)
   OPT_ADAM = 2,       // torch.optim.Adam (L2 weight decay folded into g)
   OPT_ADAMW = 3,      // torch.optim.AdamW (decoupled weight decay)
+  OPT_LARS = 4,       // momentum on r_t (g + wd p), per-tensor trust ratio r_t (launchers_optim_lw.h)
+  OPT_LAMB = 5,       // Adam direction u + wd p scaled by ||p|| / ||u|| per tensor (launchers_optim_lw.h)
 };
 
 enum DType : int32_t { DT_F32 = 0, DT_BF16 = 1, DT_F8E4M3 = 2 };

@@ -1,0 +1,55 @@
+// Per-element optimizer update and multi-source gradient load shared by the flat apply kernel
+// (optim.hip) and the segmented layer-wise kernels (optim_lw.hip): one definition, so the two
+// produce the same bits for the same inputs.
+#pragma once
+#include "common.h"
+#include "launchers.h"
+
+namespace psd {
+
+template <int KIND>
+__device__ __forceinline__ void opt_update(const OptimHyper& h, float lr, float bc1, float bc2_sqrt,
+                                           bool first, float& p, float g, float& s1, float& s2) {
+  if (h.maximize) g = -g;
+  if (KIND == OPT_SGD) {
+    if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
+    p = fmaf(-lr, g, p);
+  } else if (KIND == OPT_MOMENTUM) {
+    if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
+    float buf = first ? g : fmaf(h.momentum, s1, (1.f - h.dampening) * g);
+    s1 = buf;
+    float d = h.nesterov ? fmaf(h.momentum, buf, g) : buf;
+    p = fmaf(-lr, d, p);
+  } else {  // ADAM / ADAMW
+    if (KIND == OPT_ADAMW) {
+      p = p * (1.f - lr * h.weight_decay);
+    } else if (h.weight_decay != 0.f) {
+      g = fmaf(h.weight_decay, p, g);
+    }
+    float m = fmaf(h.beta1, s1, (1.f - h.beta1) * g);
+    float v = fmaf(h.beta2, s2, (1.f - h.beta2) * g * g);
+    s1 = m;
+    s2 = v;
+    float denom = __fsqrt_rn(v) / bc2_sqrt + h.eps;
+    p = p - (lr / bc1) * (m / denom);
+  }
+}
+
+template <int SRC_DT>
+__device__ __forceinline__ void load_sources8(const SourceList& g, int64_t i, float scale, float out[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = 0.f;
+  for (int k = 0; k < g.count; ++k) {
+    float t[8];
+    if (SRC_DT == DT_BF16)
+      load8_bf16(static_cast<const uint16_t*>(g.ptr[k]) + i, t);
+    else
+      load8_f32(static_cast<const float*>(g.ptr[k]) + i, t);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] += t[e];
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] *= scale;
+}
+
+}  // namespace psd

@@ -14,7 +14,9 @@
 #include <cstring>
 
 #include "kernels/launchers.h"
+#include "kernels/launchers_optim_lw.h"
 #include "kernels/launchers_xfer.h"
+#include "optim_lw.h"
 
 namespace psd {
 
@@ -106,15 +108,25 @@ SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at
   return s;
 }
 
-}  // namespace
-
-void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
-                  c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
-                  double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
-                  double eps, bool maximize, int64_t grid_cap) {
-  TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous(), "psd: master must be contiguous fp32");
-  const int64_t n = master.numel();
+// Validated raw view of one apply call's tensors (shared by the flat and the layer-table entry points).
+struct ApplyArgs {
   OptimHyper h{};
+  int64_t n = 0;
+  float* s1 = nullptr;
+  float* s2 = nullptr;
+  uint16_t* sh = nullptr;
+  SourceList src{};
+};
+
+ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& grads,
+                     const c10::optional<at::Tensor>& state1, const c10::optional<at::Tensor>& state2,
+                     const c10::optional<at::Tensor>& shadow, const at::Tensor& dyn, int64_t kind, double momentum,
+                     double dampening, bool nesterov, double weight_decay, double beta1, double beta2, double eps,
+                     bool maximize) {
+  TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous(), "psd: master must be contiguous fp32");
+  ApplyArgs a;
+  const int64_t n = a.n = master.numel();
+  OptimHyper& h = a.h;
   h.kind = (int32_t)kind;
   h.nesterov = nesterov;
   h.maximize = maximize;
@@ -124,38 +136,70 @@ void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::
   h.beta1 = (float)beta1;
   h.beta2 = (float)beta2;
   h.eps = (float)eps;
-  const bool need1 = kind != OPT_SGD, need2 = kind == OPT_ADAM || kind == OPT_ADAMW;
-  float* s1 = nullptr;
-  float* s2 = nullptr;
+  const bool need1 = kind != OPT_SGD, need2 = kind == OPT_ADAM || kind == OPT_ADAMW || kind == OPT_LAMB;
   if (need1) {
     TORCH_CHECK(state1.has_value() && state1->numel() == n && state1->scalar_type() == at::kFloat &&
                     state1->is_contiguous() && state1->device() == master.device(),
                 "psd: optimizer needs fp32 state1 like master");
-    s1 = state1->data_ptr<float>();
+    a.s1 = state1->data_ptr<float>();
   }
   if (need2) {
     TORCH_CHECK(state2.has_value() && state2->numel() == n && state2->scalar_type() == at::kFloat &&
                     state2->is_contiguous() && state2->device() == master.device(),
                 "psd: optimizer needs fp32 state2 like master");
-    s2 = state2->data_ptr<float>();
+    a.s2 = state2->data_ptr<float>();
   }
-  uint16_t* sh = nullptr;
   if (shadow.has_value() && shadow->defined()) {
     TORCH_CHECK(shadow->scalar_type() == at::kBFloat16 && shadow->numel() == n && shadow->is_contiguous() &&
                     shadow->device() == master.device(),
                 "psd: shadow must be contiguous bf16 like master");
-    sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+    a.sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
   }
-  SourceList src = make_sources(grads, n, master.device());
+  a.src = make_sources(grads, n, master.device());
   TORCH_CHECK(dyn.device() == master.device(), "psd: dyn must live with master");
+  if (master.is_cuda()) {
+    check_aligned(master, "master");
+    if (a.s1) check_aligned(*state1, "state1");
+    if (a.s2) check_aligned(*state2, "state2");
+    if (a.sh) check_aligned(*shadow, "shadow");
+    for (auto& t : grads) check_aligned(t, "grad");
+  }
+  return a;
+}
+
+inline float cpu_source(const SourceList& src, int64_t i, float gs) {
+  float g = 0.f;
+  for (int k = 0; k < src.count; ++k)
+    g += src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
+                              : static_cast<const float*>(src.ptr[k])[i];
+  return g * gs;
+}
+
+// LAMB update direction (kernels/optim_lw.hip lamb_u)
+inline float cpu_lamb_u(float m, float v, float w, float bc1, float bc2s, float eps, float wd) {
+  const float q = (m / bc1) / (std::sqrt(v) / bc2s + eps);
+  return std::fma(wd, w, q);
+}
+
+}  // namespace
+
+void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
+                  c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
+                  double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
+                  double eps, bool maximize, int64_t grid_cap) {
+  TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_ADAMW,
+              "psd: fused_apply_ takes sgd / momentum / adam / adamw; lars and lamb need a layer table "
+              "(fused_apply_lw_)");
+  const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
+                                 weight_decay, beta1, beta2, eps, maximize);
+  const OptimHyper& h = a.h;
+  const int64_t n = a.n;
+  float *s1 = a.s1, *s2 = a.s2;
+  uint16_t* sh = a.sh;
+  const SourceList& src = a.src;
 
   if (master.is_cuda()) {
     const c10::DeviceGuard g(master.device());
-    check_aligned(master, "master");
-    if (s1) check_aligned(*state1, "state1");
-    if (s2) check_aligned(*state2, "state2");
-    if (sh) check_aligned(*shadow, "shadow");
-    for (auto& t : grads) check_aligned(t, "grad");
     hip_check(launch_fused_apply(h, dyn_ptr(dyn), master.data_ptr<float>(), src, s1, s2, sh, n, cur_stream(master),
                                  (int)grid_cap),
               "fused_apply");
@@ -167,16 +211,202 @@ void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::
   float* p = master.data_ptr<float>();
   at::parallel_for(0, n, 1 << 14, [&](int64_t b, int64_t e) {
     for (int64_t i = b; i < e; ++i) {
-      float g = 0.f;
-      for (int k = 0; k < src.count; ++k)
-        g += src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
-                                  : static_cast<const float*>(src.ptr[k])[i];
-      g *= gs;
+      float g = cpu_source(src, i, gs);
       float a = s1 ? s1[i] : 0.f, c = s2 ? s2[i] : 0.f;
       cpu_update(h, lr, bc1, bc2s, first, p[i], g, a, c);
       if (s1) s1[i] = a;
       if (s2) s2[i] = c;
       if (sh) sh[i] = f2bf(p[i]);
+    }
+  });
+}
+
+const LwGpu*& lw_gpu() {
+  static const LwGpu* table = nullptr;
+  return table;
+}
+
+std::vector<at::Tensor> lw_table_build(const std::vector<int64_t>& offsets, const std::vector<int64_t>& numels,
+                                       const std::vector<int64_t>& ndims, int64_t n, bool exclude_1d, int64_t align,
+                                       const at::Device& device) {
+  const size_t T = offsets.size();
+  TORCH_CHECK(T >= 1 && numels.size() == T && ndims.size() == T, "psd: layer table needs one (offset, numel, ndim) per tensor");
+  TORCH_CHECK(align >= 8 && align % 8 == 0, "psd: layer table alignment must be a multiple of 8 elements");
+  TORCH_CHECK(offsets[0] == 0, "psd: the first tensor of a layer table starts its range (offset 0)");
+  TORCH_CHECK(n % 8 == 0, "psd: a layer table's range must be a multiple of 8 elements, got ", n);
+  std::vector<int64_t> seg(T + 1), coff;
+  std::vector<int32_t> segc(T + 1), adapt(T), cseg;
+  std::vector<float> wdm(T);
+  for (size_t t = 0; t < T; ++t) {
+    const int64_t end = t + 1 < T ? offsets[t + 1] : n;
+    TORCH_CHECK(offsets[t] % align == 0, "psd: layer table: tensor ", t, " starts at ", offsets[t],
+                ", not on a ", align, "-element boundary");
+    TORCH_CHECK(numels[t] >= 0 && offsets[t] + std::max<int64_t>(numels[t], 1) <= end, "psd: layer table: tensor ", t,
+                " overlaps the next one or the end of the range");
+    seg[t] = offsets[t];
+    segc[t] = (int32_t)cseg.size();
+    const bool excl = exclude_1d && ndims[t] <= 1;
+    wdm[t] = excl ? 0.f : 1.f;
+    adapt[t] = excl ? 0 : 1;
+    for (int64_t o = offsets[t]; o < end; o += kLwChunk) {
+      TORCH_CHECK(cseg.size() < (size_t)INT32_MAX, "psd: layer table: too many chunks");
+      cseg.push_back((int32_t)t);
+      coff.push_back(o);
+    }
+  }
+  seg[T] = n;
+  segc[T] = (int32_t)cseg.size();
+  const int64_t C = (int64_t)cseg.size();
+  auto dev_of = [&](const void* p, int64_t count, at::ScalarType st) {
+    at::Tensor h = at::empty({count}, at::TensorOptions().dtype(st));
+    std::memcpy(h.data_ptr(), p, (size_t)count * h.element_size());
+    return h.to(device);
+  };
+  at::Tensor meta = at::empty({3}, at::kLong);
+  meta.data_ptr<int64_t>()[0] = n;
+  meta.data_ptr<int64_t>()[1] = (int64_t)T;
+  meta.data_ptr<int64_t>()[2] = C;
+  return {meta,
+          dev_of(seg.data(), (int64_t)T + 1, at::kLong),
+          dev_of(segc.data(), (int64_t)T + 1, at::kInt),
+          dev_of(wdm.data(), (int64_t)T, at::kFloat),
+          dev_of(adapt.data(), (int64_t)T, at::kInt),
+          dev_of(cseg.data(), C, at::kInt),
+          dev_of(coff.data(), C, at::kLong),
+          at::zeros({2 * C}, at::TensorOptions().dtype(at::kFloat).device(device)),
+          at::ones({(int64_t)T}, at::TensorOptions().dtype(at::kFloat).device(device))};
+}
+
+void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
+                     c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
+                     double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
+                     double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
+                     int64_t grid_cap) {
+  TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_LAMB, "psd: unknown optimizer kind ", kind);
+  const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
+                                 weight_decay, beta1, beta2, eps, maximize);
+  // ---- the layer table (lw_table_build): shapes, dtypes, device, and the range it was built for
+  TORCH_CHECK(layers.size() == 9, "psd: layer table must be the 9 tensors of lw_table_build");
+  const at::Tensor& meta = layers[0];
+  TORCH_CHECK(meta.device().is_cpu() && meta.scalar_type() == at::kLong && meta.numel() == 3, "psd: layer table meta");
+  const int64_t T = meta.data_ptr<int64_t>()[1], C = meta.data_ptr<int64_t>()[2];
+  TORCH_CHECK(meta.data_ptr<int64_t>()[0] == a.n, "psd: layer table was built for ", meta.data_ptr<int64_t>()[0],
+              " elements, master has ", a.n);
+  const at::ScalarType want_dt[9] = {at::kLong, at::kLong, at::kInt, at::kFloat, at::kInt,
+                                     at::kInt,  at::kLong, at::kFloat, at::kFloat};
+  const int64_t want_n[9] = {3, T + 1, T + 1, T, T, C, C, 2 * C, T};
+  for (int i = 1; i < 9; ++i)
+    TORCH_CHECK(layers[i].scalar_type() == want_dt[i] && layers[i].numel() == want_n[i] && layers[i].is_contiguous() &&
+                    layers[i].device() == master.device(),
+                "psd: layer table tensor ", i, " has the wrong dtype, size or device");
+  TORCH_CHECK(T >= 1 && C >= 1 && T <= INT32_MAX && C <= INT32_MAX, "psd: empty layer table");
+  LwTable t{};
+  t.seg_start = layers[1].data_ptr<int64_t>();
+  t.seg_chunk = layers[2].data_ptr<int32_t>();
+  t.wd_mult = layers[3].data_ptr<float>();
+  t.adapt = layers[4].data_ptr<int32_t>();
+  t.chunk_seg = layers[5].data_ptr<int32_t>();
+  t.chunk_off = layers[6].data_ptr<int64_t>();
+  t.partials = layers[7].data_ptr<float>();
+  t.ratio = layers[8].data_ptr<float>();
+  t.n_seg = (int32_t)T;
+  t.n_chunks = (int32_t)C;
+  t.trust_coef = (float)trust_coef;
+  const OptimHyper& h = a.h;
+  const bool layerwise = kind == OPT_LARS || kind == OPT_LAMB;
+  float* p = master.data_ptr<float>();
+
+  if (master.is_cuda()) {
+    const LwGpu* gpu = lw_gpu();
+    TORCH_CHECK(gpu != nullptr, "psd: the gfx950 layer-table kernels are not linked into this build; only CPU tensors "
+                                "can take a layer table here");
+    const c10::DeviceGuard g(master.device());
+    hipStream_t st = cur_stream(master);
+    if (layerwise) {
+      hip_check(gpu->norms(h, dyn_ptr(dyn), p, a.src, a.s1, a.s2, t, st, (int)grid_cap), "lw_norms");
+      hip_check(gpu->finalize(h, t, st, (int)grid_cap), "lw_finalize");
+    }
+    hip_check(gpu->apply(h, dyn_ptr(dyn), p, a.src, a.s1, a.s2, a.sh, t, st, (int)grid_cap), "lw_apply");
+    return;
+  }
+
+  // ---- host path: the same three passes. Sums go per chunk, then per segment over the chunks in
+  // order, so the result does not depend on the thread count or on where the buffer was cut.
+  const OptimDyn d = *dyn_ptr(dyn);
+  const float lr = d.lr, gs = d.grad_scale, bc1 = d.bc1, bc2s = std::sqrt(d.bc2);
+  const bool first = d.step <= 1;
+  const SourceList& src = a.src;
+  float *s1 = a.s1, *s2 = a.s2;
+  uint16_t* sh = a.sh;
+  auto chunk_end = [&](int64_t c) {
+    const int64_t left = t.seg_start[t.chunk_seg[c] + 1] - t.chunk_off[c];
+    return t.chunk_off[c] + std::min<int64_t>(left, kLwChunk);
+  };
+  if (layerwise) {
+    at::parallel_for(0, C, 4, [&](int64_t cb, int64_t ce) {
+      for (int64_t c = cb; c < ce; ++c) {
+        const float wd = h.weight_decay * t.wd_mult[t.chunk_seg[c]];
+        double aw = 0.0, ab = 0.0;
+        for (int64_t i = t.chunk_off[c], e = chunk_end(c); i < e; ++i) {
+          float g = cpu_source(src, i, gs);
+          float b = g;
+          if (kind == OPT_LAMB) {
+            if (h.maximize) g = -g;
+            s1[i] = std::fma(h.beta1, s1[i], (1.f - h.beta1) * g);
+            s2[i] = std::fma(h.beta2, s2[i], (1.f - h.beta2) * g * g);
+            b = cpu_lamb_u(s1[i], s2[i], p[i], bc1, bc2s, h.eps, wd);
+          }
+          aw += (double)p[i] * p[i];
+          ab += (double)b * b;
+        }
+        t.partials[2 * c] = (float)aw;
+        t.partials[2 * c + 1] = (float)ab;
+      }
+    });
+    for (int64_t s = 0; s < T; ++s) {
+      double aw = 0.0, ab = 0.0;
+      for (int64_t c = t.seg_chunk[s]; c < t.seg_chunk[s + 1]; ++c) {
+        aw += t.partials[2 * c];
+        ab += t.partials[2 * c + 1];
+      }
+      const float wn = (float)std::sqrt(aw), bn = (float)std::sqrt(ab);
+      float r = 1.f;
+      if (t.adapt[s] && wn > 0.f && bn > 0.f) {
+        if (kind == OPT_LAMB) r = wn / bn;
+        else r = t.trust_coef * wn / (bn + h.weight_decay * t.wd_mult[s] * wn + h.eps);
+      }
+      t.ratio[s] = r;
+    }
+  }
+  at::parallel_for(0, C, 4, [&](int64_t cb, int64_t ce) {
+    for (int64_t c = cb; c < ce; ++c) {
+      const int32_t s = t.chunk_seg[c];
+      const float wd = h.weight_decay * t.wd_mult[s];
+      const float r = layerwise ? t.ratio[s] : 1.f;
+      OptimHyper hs = h;
+      hs.weight_decay = kind == OPT_LARS ? 0.f : wd;
+      if (kind == OPT_LARS) {
+        hs.kind = OPT_MOMENTUM;
+        hs.maximize = 0;
+      }
+      for (int64_t i = t.chunk_off[c], e = chunk_end(c); i < e; ++i) {
+        if (kind == OPT_LAMB) {
+          const float u = cpu_lamb_u(s1[i], s2[i], p[i], bc1, bc2s, h.eps, wd);
+          p[i] = std::fma(-(lr * r), u, p[i]);
+        } else {
+          float g = cpu_source(src, i, gs);
+          if (kind == OPT_LARS) {
+            if (h.maximize) g = -g;
+            if (wd != 0.f) g = std::fma(wd, p[i], g);
+            g *= r;
+          }
+          float m = s1 ? s1[i] : 0.f, v = s2 ? s2[i] : 0.f;
+          cpu_update(hs, lr, bc1, bc2s, first, p[i], g, m, v);
+          if (s1) s1[i] = m;
+          if (s2) s2[i] = v;
+        }
+        if (sh) sh[i] = f2bf(p[i]);
+      }
     }
   });
 }

@@ -9,6 +9,21 @@ void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::
                   c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                   double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
                   double eps, bool maximize, int64_t grid_cap = 0);
+// The layer table of one contiguous flat range of `n` elements (kernels/launchers_optim_lw.h): tensors
+// (offset relative to the range, numel, ndim), every start on an `align`-element boundary. With
+// exclude_1d, tensors of ndim <= 1 get wd_mult 0 and adapt 0. Returns {meta (CPU: n, segments,
+// chunks), seg_start, seg_chunk, wd_mult, adapt, chunk_seg, chunk_off, partials, ratio} on `device`:
+// everything the kernels need, allocated once.
+std::vector<at::Tensor> lw_table_build(const std::vector<int64_t>& offsets, const std::vector<int64_t>& numels,
+                                       const std::vector<int64_t>& ndims, int64_t n, bool exclude_1d, int64_t align,
+                                       const at::Device& device);
+// fused_apply_ with a layer table: LARS / LAMB (norm pass, finalize, apply) or a flat kind with
+// per-tensor weight decay (apply only). `layers`: the tensors of lw_table_build for this range.
+void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
+                     c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
+                     double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
+                     double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
+                     int64_t grid_cap = 0);
 void optim_advance_(at::Tensor dyn, double beta1, double beta2);
 void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale);
 void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts);

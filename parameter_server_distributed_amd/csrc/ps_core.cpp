@@ -26,6 +26,9 @@ int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 PSCore::PSCore(PSConfig cfg, std::string device) : cfg_(std::move(cfg)), dev_(device), hist_(kHistBins, 0) {
   TORCH_CHECK(cfg_.total_workers >= 1, "psd: total_workers must be >= 1");
+  TORCH_CHECK(cfg_.opt_kind >= OPT_SGD && cfg_.opt_kind <= OPT_LAMB, "psd: unknown optimizer kind ", cfg_.opt_kind);
+  TORCH_CHECK(!(cfg_.async_mode && (cfg_.opt_kind == OPT_LARS || cfg_.opt_kind == OPT_LAMB)),
+              "psd: lars / lamb need whole rounds; the async (apply-on-arrival) mode is not supported with them");
   dyn_ = at::zeros({8}, at::TensorOptions().dtype(at::kInt).device(dev_));
 }
 
@@ -54,7 +57,16 @@ void PSCore::alloc_state_locked() {
   auto opt = at::TensorOptions().dtype(at::kFloat).device(dev_);
   master_ = at::zeros({total_}, opt);
   s1_ = (cfg_.opt_kind != OPT_SGD) ? at::zeros({total_}, opt) : at::Tensor();
-  s2_ = (cfg_.opt_kind == OPT_ADAM || cfg_.opt_kind == OPT_ADAMW) ? at::zeros({total_}, opt) : at::Tensor();
+  s2_ = (cfg_.opt_kind == OPT_ADAM || cfg_.opt_kind == OPT_ADAMW || cfg_.opt_kind == OPT_LAMB) ? at::zeros({total_}, opt)
+                                                                                              : at::Tensor();
+  const bool layerwise = cfg_.opt_kind == OPT_LARS || cfg_.opt_kind == OPT_LAMB;
+  const bool excl = cfg_.exclude_1d < 0 ? layerwise : cfg_.exclude_1d != 0;
+  layers_.clear();
+  if ((layerwise || excl) && !offsets_.empty()) {
+    std::vector<int64_t> nd;
+    for (auto& s : shapes_) nd.push_back((int64_t)s.size());
+    layers_ = lw_table_build(offsets_, numels_, nd, total_, excl, kAlign, dev_);
+  }
   dyn_.zero_();
   slots_.clear();
   free_slots_.clear();
@@ -133,6 +145,13 @@ void PSCore::apply_locked(const std::vector<at::Tensor>& sources, double lr, dou
   const double mom = ah ? ah->momentum : cfg_.momentum, wd = ah ? ah->weight_decay : cfg_.weight_decay;
   const double b1 = ah ? ah->beta1 : cfg_.beta1, b2 = ah ? ah->beta2 : cfg_.beta2;
   optim_advance_(dyn_, b1, b2);
+  if (!layers_.empty()) {
+    fused_apply_lw_(master_, srcs, s1_.defined() ? c10::optional<at::Tensor>(s1_) : c10::nullopt,
+                    s2_.defined() ? c10::optional<at::Tensor>(s2_) : c10::nullopt, c10::nullopt, dyn_, cfg_.opt_kind,
+                    mom, cfg_.dampening, cfg_.nesterov, wd, b1, b2, cfg_.eps, false, cfg_.trust_coef, layers_);
+    ctr_["applies"] += 1;
+    return;
+  }
   fused_apply_(master_, srcs, s1_.defined() ? c10::optional<at::Tensor>(s1_) : c10::nullopt,
                s2_.defined() ? c10::optional<at::Tensor>(s2_) : c10::nullopt, c10::nullopt, dyn_, cfg_.opt_kind,
                mom, cfg_.dampening, cfg_.nesterov, wd, b1, b2, cfg_.eps, false);

@@ -38,6 +38,9 @@ struct PSConfig {
   double lr = 1.0;
   double momentum = 0.0, dampening = 0.0, weight_decay = 0.0;
   double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
+  double trust_coef = 0.001;  // LARS eta (OPT_LARS)
+  // -1: by kind (on for lars / lamb), 0 / 1: tensors of ndim <= 1 take no weight decay and no trust ratio
+  int32_t exclude_1d = -1;
   bool nesterov = false;
   bool reference_compat = false;  // first aggregate becomes the params (src/parameter_server.cpp:78-81)
   bool staleness_lr_scaling = false;  // async: lr / (1 + staleness)
@@ -109,6 +112,7 @@ class PSCore {
   int64_t total_ = 0;
   bool init_ = false;
   at::Tensor master_, s1_, s2_, dyn_;
+  std::vector<at::Tensor> layers_;  // layer table of the flat master (lars / lamb / exclude_1d), else empty
   std::vector<at::Tensor> slots_;
   std::vector<int32_t> free_slots_;
 

@@ -8,6 +8,12 @@ Reference parity: ``ParameterServerCore::aggregate_gradients`` applies ``p -= g`
 (src/parameter_server.cpp:77-91, "can add learning rate here" at :87). ``OptimConfig(kind="sgd",
 lr=1.0)`` reproduces it; the other kinds match ``torch.optim.SGD/Adam/AdamW`` (tested against them).
 
+Layer-wise optimizers (gfx950 kernels ``csrc/kernels/optim_lw.hip``): with a ``LayerTable`` -- the
+tensor boundaries of the flat range -- the apply is segmented per tensor. ``lars`` and ``lamb`` scale
+each tensor's update by a trust ratio from whole-tensor norms (norm pass, finalize, apply: three
+launches), and ``exclude_1d`` keeps weight decay (and the trust ratio) off tensors of ndim <= 1
+(BatchNorm / LayerNorm weights, biases) for any kind.
+
 Per-step scalars (lr, grad scale, step count, Adam bias corrections) live in a 32-byte device
 struct (``OptimDyn``) so a captured hipGraph replays with the current values.
 """
@@ -19,7 +25,8 @@ import torch
 
 from .. import native
 
-KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3}
+KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3, "lars": 4, "lamb": 5}
+LAYERWISE = ("lars", "lamb")
 
 
 @dataclass
@@ -34,12 +41,18 @@ class OptimConfig:
     beta2: float = 0.999
     eps: float = 1e-8
     maximize: bool = False
+    trust_coef: float = 0.001  # LARS eta (lamb ignores it)
+    # tensors of ndim <= 1 take no weight decay and no trust ratio; None: True for lars / lamb, else False
+    exclude_1d: bool | None = None
 
     def __post_init__(self):
         if self.kind not in KINDS:
             raise ValueError(f"unknown optimizer kind {self.kind!r}; expected one of {sorted(KINDS)}")
         if self.kind == "momentum" and self.momentum == 0.0:
             self.kind = "sgd"
+        if self.exclude_1d is None:
+            self.exclude_1d = self.kind in LAYERWISE
+        self.exclude_1d = bool(self.exclude_1d)
 
     @property
     def code(self) -> int:
@@ -47,7 +60,12 @@ class OptimConfig:
 
     @property
     def num_states(self) -> int:
-        return {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 2}[self.kind]
+        return {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 2, "lars": 1, "lamb": 2}[self.kind]
+
+    @property
+    def needs_layers(self) -> bool:
+        """The apply needs the tensor boundaries (a ``LayerTable``)."""
+        return self.kind in LAYERWISE or self.exclude_1d
 
     def to_dict(self):
         return asdict(self)
@@ -79,16 +97,77 @@ class OptimDyn:
         return float(self._f[0].item())
 
 
+class LayerTable:
+    """Tensor boundaries of one contiguous flat range, as the segmented kernels read them.
+
+    ``tensors``: ``[(offset, numel, ndim)]`` in buffer order, offsets relative to the range, the first
+    at 0 and every one on an ``align``-element boundary (64: the flat layouts of the data planes).
+    ``n``: the length of the range. A segment runs from one tensor's start to the next tensor's
+    start, so the alignment padding (zero weight, zero gradient) belongs to the tensor in front of
+    it and contributes nothing. With ``exclude_1d`` tensors of ndim <= 1 get ``wd_mult`` 0 and
+    ``adapt`` 0. Segments are cut into chunks of <= 8192 elements numbered from the segment start.
+
+    Owns every device tensor of the table -- segment starts, per-segment ``wd_mult`` / ``adapt``, the
+    chunk table, the per-chunk partials and the per-segment ratio -- allocated once here, so an
+    apply allocates nothing and stays legal under stream capture."""
+
+    def __init__(self, tensors, n: int, exclude_1d: bool, device, align: int = 64):
+        tensors = [(int(o), int(k), int(d)) for (o, k, d) in tensors]
+        if not tensors:
+            raise ValueError("LayerTable needs at least one tensor")
+        self.tensors = tensors
+        self.n = int(n)
+        self.exclude_1d = bool(exclude_1d)
+        self.device = torch.device(device)
+        try:
+            self.t = native().lw_table_build([o for o, _, _ in tensors], [k for _, k, _ in tensors],
+                                             [d for _, _, d in tensors], self.n, self.exclude_1d, int(align),
+                                             str(self.device))
+        except RuntimeError as e:  # a bad layout is the caller's value error
+            raise ValueError(str(e).split("\n")[0]) from None
+        (self.meta, self.seg_start, self.seg_chunk, self.wd_mult, self.adapt, self.chunk_seg, self.chunk_off,
+         self.partials, self.ratio) = self.t
+
+    @classmethod
+    def for_range(cls, layout, lo: int, hi: int, exclude_1d: bool, device, align: int = 64) -> "LayerTable":
+        """The table of ``[lo, hi)`` of a flat buffer from its ``[(offset, numel, ndim)]`` layout
+        (absolute offsets); ``lo`` must be a tensor start."""
+        inside = [(o - lo, k, d) for (o, k, d) in layout if lo <= o < hi]
+        if not inside or inside[0][0] != 0:
+            raise ValueError(f"range [{lo}, {hi}) does not start on a tensor start")
+        return cls(inside, hi - lo, exclude_1d, device, align)
+
+    @property
+    def num_segments(self) -> int:
+        return len(self.tensors)
+
+
 def fused_apply_(cfg: OptimConfig, dyn: OptimDyn, master: torch.Tensor, grads, state1=None, state2=None,
-                 shadow=None, advance: bool = True) -> None:
-    """In-place fused update of ``master`` from the sum of ``grads`` (list or tensor)."""
+                 shadow=None, advance: bool = True, layers: LayerTable | None = None, grid_cap: int = 0) -> None:
+    """In-place fused update of ``master`` from the sum of ``grads`` (list or tensor). ``layers``:
+    the ``LayerTable`` of ``master``'s range -- required for lars / lamb and with ``exclude_1d``,
+    rejected otherwise (a table that changes nothing would only hide a configuration mistake)."""
     C = native()
     if isinstance(grads, torch.Tensor):
         grads = [grads]
+    if cfg.needs_layers and layers is None:
+        raise ValueError(f"optimizer {cfg.kind!r} (exclude_1d={cfg.exclude_1d}) needs the tensor boundaries: pass "
+                         f"layers=LayerTable(...)")
+    if not cfg.needs_layers and layers is not None:
+        raise ValueError(f"optimizer {cfg.kind!r} with exclude_1d=False takes no layer table")
+    if layers is not None and layers.n != master.numel():
+        raise ValueError(f"layer table built for {layers.n} elements, master has {master.numel()}")
+    if layers is not None and layers.exclude_1d != cfg.exclude_1d:
+        raise ValueError(f"layer table built with exclude_1d={layers.exclude_1d}, config has {cfg.exclude_1d}")
     if advance:
         C.optim_advance_(dyn.t, cfg.beta1, cfg.beta2)
-    C.fused_apply_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
-                   cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize)
+    if layers is None:
+        C.fused_apply_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
+                       cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, grid_cap)
+    else:
+        C.fused_apply_lw_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
+                          cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, cfg.trust_coef,
+                          layers.t, grid_cap)
 
 
 def advance_(cfg: OptimConfig, dyn: OptimDyn) -> None:

@@ -36,8 +36,10 @@ Optimizer semantics (``semantics``):
           trajectory in tests/test_async_ps.py.
 
 Layout: the parameters live in one flat working buffer (``.data`` views, reverse registration
-order, 64-element aligned) split into P contiguous shards; gradients alternate between two flat
-buffers so the next step never waits for the previous step's push copies. One node, one process
+order, 64-element aligned) split into P contiguous shards (cut at the nearest tensor starts when the
+optimizer needs tensor boundaries: lars, lamb, ``exclude_1d``; each owner then applies with the
+layer table of its shard, csrc/kernels/optim_lw.hip; round semantics only for lars / lamb);
+gradients alternate between two flat buffers so the next step never waits for the previous step's push copies. One node, one process
 per GPU (the control block is POSIX shared memory); ``device=cpu`` runs the identical protocol on
 host shared memory (CPU CI / gloo plumbing).
 
@@ -57,11 +59,26 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import native
-from ..ops.optim import OptimConfig, OptimDyn
+from ..ops.optim import LAYERWISE, LayerTable, OptimConfig, OptimDyn
 from ..utils.config import fault, feature
 from .collective_ps import ALIGN, _flat_view, _round, install_fp8_weights, zero_grads_, zero_plan
 
 
+
+
+def snap_bounds(total: int, P: int, starts: list[int]) -> list[int]:
+    """Shard boundaries on tensor starts: for each ideal cut ``total * k / P`` the nearest tensor
+    start, strictly increasing (a cut never takes a start an earlier cut took, and leaves one for
+    every later cut). ``starts``: the tensors' offsets in increasing order, the first 0."""
+    if P > len(starts):
+        raise ValueError(f"{P} shards cut on tensor starts need at least {P} tensors, the model has {len(starts)}")
+    bounds, prev = [0], 0
+    for k in range(1, P):
+        ideal = total * k // P
+        cand = range(prev + 1, len(starts) - (P - 1 - k))
+        prev = min(cand, key=lambda i: (abs(starts[i] - ideal), i))
+        bounds.append(starts[prev])
+    return bounds + [total]
 
 
 class _NoTransport:
@@ -119,6 +136,9 @@ class AsyncPS:
         rank together, logged in ``xfer_mode``) if its start-up self-test fails."""
         if xfer not in ("auto", "kernel", "copy"):
             raise ValueError(f"xfer must be auto, kernel or copy, got {xfer!r}")
+        if semantics == "push" and optim.kind in LAYERWISE:
+            raise ValueError(f"optimizer {optim.kind!r} takes whole rounds (the trust ratio is a property of the "
+                             f"round's gradient): semantics='push' is not supported with it, use 'round'")
         self.xfer = xfer
         self.model = model
         self.cfg = optim
@@ -167,7 +187,12 @@ class AsyncPS:
         total = _round(max(off, ALIGN), self.P * ALIGN)
         self.total = total
         # P contiguous shards, 64-element aligned, balanced by size
-        bounds = [_round(total * k // self.P, ALIGN) for k in range(self.P)] + [total]
+        if optim.needs_layers:
+            # per-tensor norms / decay flags: a tensor must not straddle two owners, so the cuts move
+            # to the nearest tensor starts (the apply's result does not depend on where they fall)
+            bounds = snap_bounds(total, self.P, [o for (_n, _p, o, _k) in layout])
+        else:
+            bounds = [_round(total * k // self.P, ALIGN) for k in range(self.P)] + [total]
         self.shard_off = bounds[:-1]
         self.shard_len = [bounds[k + 1] - bounds[k] for k in range(self.P)]
         self._build_buckets(layout, bucket_mb)
@@ -219,6 +244,13 @@ class AsyncPS:
                 self.state2[k] = torch.zeros(self.shard_len[k], **f32)
             self.dyn[k] = OptimDyn(dev, lr=optim.lr * self.hyper["lr_factor"], grad_scale=self.hyper["grad_scale"])
         del init
+        # one layer table per owned shard (tensor boundaries relative to the shard's start)
+        self.layers = {}
+        if optim.needs_layers:
+            flat = [(o, k, p.dim()) for (_n, p, o, k) in layout]
+            for k in self.my_shards:
+                self.layers[k] = LayerTable.for_range(flat, self.shard_off[k], self.shard_off[k] + self.shard_len[k],
+                                                      optim.exclude_1d, dev, ALIGN)
 
         # grad sinks (fused BN / MFMA linear write their parameter gradients straight into the buffer)
         self._direct = set()
@@ -302,6 +334,8 @@ class AsyncPS:
             self.engine.set_shard_state(k, self.master[k], self.state1.get(k), self.state2.get(k), self.dyn[k].t,
                                         optim.code, h["momentum"], optim.dampening, optim.nesterov,
                                         h["weight_decay"], h["beta1"], h["beta2"], optim.eps)
+            if k in self.layers:
+                self.engine.set_shard_layers(k, self.layers[k].t, optim.trust_coef)
             self.engine.publish_initial(k)
         self.engine.set_round(self.round)
         self.engine.set_fixed_schedule(self.schedule == "fixed")

@@ -129,6 +129,12 @@ class CollectivePS:
                  param_dtype: torch.dtype = torch.bfloat16, device: torch.device | None = None,
                  ps_ranks: list[int] | None = None, worker_ranks: list[int] | None = None,
                  pull_dtype: str = "bf16", push_mode: str = "auto"):
+        if optim.needs_layers:
+            # every bucket is cut into P equal slices, so tensors straddle owners and a tensor's norm
+            # would need a cross-rank exchange per step
+            raise ValueError(f"optimizer {optim.kind!r} with exclude_1d={optim.exclude_1d} needs per-tensor shards: "
+                             f"the collective plane cuts buckets into equal slices; use the async plane "
+                             f"(parallel.async_ps.AsyncPS), which puts shard boundaries on tensor starts")
         self.model = model
         self.cfg = optim
         self.t = transport or LocalTransport()

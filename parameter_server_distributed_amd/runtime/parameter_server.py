@@ -46,6 +46,8 @@ def make_config(total_workers: int, optim: OptimConfig, mode: str = "sync", stal
     cfg.lr = optim.lr
     cfg.momentum, cfg.dampening, cfg.nesterov = optim.momentum, optim.dampening, optim.nesterov
     cfg.weight_decay = optim.weight_decay
+    cfg.trust_coef = optim.trust_coef
+    cfg.exclude_1d = int(optim.exclude_1d)
     cfg.beta1, cfg.beta2, cfg.eps = optim.beta1, optim.beta2, optim.eps
     cfg.staleness_lr_scaling = bool(staleness_lr_scaling)
     return cfg
