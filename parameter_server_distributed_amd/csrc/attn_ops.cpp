@@ -19,7 +19,8 @@ void check_attn(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd attn: ", what,
               " must be a contiguous bf16 device tensor");
 }
-AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed, const c10::optional<at::Tensor>& step) {
+AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed, const c10::optional<at::Tensor>& step,
+                   const c10::optional<at::Tensor>& lens, int64_t grid_cap) {
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
   const int64_t dh = qkv.size(2) / (3 * heads);
   TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh), "psd attn: needs head dim 64 and S in {32, 64, 96, 128}");
@@ -34,15 +35,23 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
   a.rescale = (float)(1.0 / (1.0 - p));
   a.seed = (uint32_t)seed;
   a.step = (step.has_value() && step->defined()) ? step->data_ptr<int64_t>() : nullptr;
+  if (lens.has_value() && lens->defined()) {  // per-sequence lengths, clamped and read on the device only
+    TORCH_CHECK(lens->scalar_type() == at::kInt && lens->is_contiguous() && lens->numel() == qkv.size(0) &&
+                    lens->device() == qkv.device(),
+                "psd attn: lens must be a contiguous int32 [B] tensor on qkv's device");
+    a.lens = lens->data_ptr<int32_t>();
+  }
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= INT32_MAX, "psd attn: grid_cap must be >= 0");
+  a.grid_cap = (int32_t)grid_cap;
   return a;
 }
 }  // namespace
 
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
-                                 c10::optional<at::Tensor> step) {
+                                 c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap) {
   check_attn(qkv, "qkv");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap);
   at::Tensor o = at::empty({qkv.size(0), qkv.size(1), qkv.size(2) / 3}, qkv.options());
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
@@ -53,16 +62,18 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
 }
 
 // bias_out (optional, [3*H*Dh] bf16/fp32): also the QKV Linear's bias gradient = the column sums of
-// dqkv, from per-sequence partials the kernel writes + one deterministic column reduce
+// dqkv, from per-sequence partials the kernel writes + one deterministic column reduce (with lens the
+// padded rows of dqkv are written as zeros, so the same sums hold).
+// lens (optional, int32 [B]): valid rows per sequence; grid_cap > 0 bounds the persistent grid (tests).
 at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
-                    c10::optional<at::Tensor> bias_out) {
+                    c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap) {
   at::Tensor dout = dout_in.contiguous();
   check_attn(dout, "dout");
   check_attn(qkv, "qkv");
   check_attn(o, "o");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap);
   TORCH_CHECK(o.sizes() == dout.sizes() && o.size(0) == qkv.size(0) && o.size(1) == qkv.size(1) &&
                   o.size(2) * 3 == qkv.size(2),
               "psd attn bwd: o / dout must be [B, S, H*Dh]");

@@ -13,6 +13,9 @@
 //             wave w owns query block w: dQ = dS K.
 // Dropout keeps (b, h, q, key) from the same counter hash as the fused LayerNorm (seed, device step
 // counter), so the mask is regenerated in backward and a replayed hipGraph draws fresh masks.
+// Padded batches pass per-sequence lengths (AttnArgs::lens): separate VARLEN instantiations skip the
+// 32-row blocks past a length, mask the partial one and never read a padded row; without lengths the
+// launchers pick the VARLEN = false instantiations, which are the full-length kernels unchanged.
 //
 // Replaces what the reference's stub gradient (src/worker.cpp:316-329) stands in for: the model's
 // real forward/backward; the attention is BERT's (BASELINE config 4).
@@ -109,6 +112,15 @@ __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, in
   }
 }
 
+// valid rows of sequence b: S without lengths; else lens[b] clamped to [0, S] here, on the device (the
+// host never reads lens, so a replayed graph sees the current values)
+template <bool VARLEN>
+__device__ __forceinline__ int item_len(const AttnArgs& a, int b, int S) {
+  if constexpr (VARLEN) return min(max(a.lens[b], 0), S);
+  else return S;
+}
+__device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
+
 }  // namespace
 
 static int attn_cus() {
@@ -126,8 +138,19 @@ static int attn_cus() {
 // (batch, head) item's K, V rows and this lane's Q fragments are loaded into registers while the
 // current item is computed. The probabilities never leave registers (P V takes them as its B
 // operand in accumulator-row key order) and O leaves in 8-B pieces.
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
+//
+// VARLEN (a.lens given): sequence b has L = item_len valid rows, nb = ceil(L / 32) blocks. Rows >= L of
+// K, V and Q are never loaded: zeros are staged in their place, so no padded (or stale) row enters a
+// product. A wave whose query block lies past L stores zeros and runs no MFMA; the others walk key
+// blocks j < nb only, with the scores of keys >= L at -inf (probability exactly 0). Every skip is
+// wave-uniform and every wave reaches both barriers. Without lengths (VARLEN false) every such test
+// is a compile-time constant and the kernel is the full-length one.
+// (The length-aware copy asks for two waves per SIMD: left alone the compiler takes 233 + 80 registers
+// at NW = 4, one workgroup per CU instead of two; a minimum of 1 is the default and leaves the
+// full-length copy as it was.)
+template <int NW, bool VARLEN>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VARLEN ? 2 : 1)))
+void attn_fwd_kernel(AttnArgs a) {
   constexpr int S = 32 * NW;
   constexpr int NT = 64 * NW;
   constexpr int CH = S * 8 / NT;  // 16-B chunks per lane per tile (= 4)
@@ -148,19 +171,31 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
   auto fetch = [&](int bh) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
+    const int Lf = item_len<VARLEN>(a, b, S);
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = threadIdx.x + i * NT, r = c >> 3, ch = c & 7;
-      pk[i] = *reinterpret_cast<const u32x4*>(base + HD + (int64_t)r * qkv_rs + ch * 8);
-      pv[i] = *reinterpret_cast<const u32x4*>(base + 2 * HD + (int64_t)r * qkv_rs + ch * 8);
+      u32x4 k4 = zero4(), v4 = zero4();
+      if (!VARLEN || r < Lf) {
+        k4 = *reinterpret_cast<const u32x4*>(base + HD + (int64_t)r * qkv_rs + ch * 8);
+        v4 = *reinterpret_cast<const u32x4*>(base + 2 * HD + (int64_t)r * qkv_rs + ch * 8);
+      }
+      pk[i] = k4;
+      pv[i] = v4;
     }
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) pq[ks] = *reinterpret_cast<const u32x4*>(base + (int64_t)q * qkv_rs + 16 * ks + 8 * hh);
+    for (int ks = 0; ks < 4; ++ks) {
+      u32x4 q4 = zero4();
+      if (!VARLEN || q < Lf) q4 = *reinterpret_cast<const u32x4*>(base + (int64_t)q * qkv_rs + 16 * ks + 8 * hh);
+      pq[ks] = q4;
+    }
   };
   if ((int)blockIdx.x < nitems) fetch(blockIdx.x);
 
   for (int bh = blockIdx.x; bh < nitems; bh += gridDim.x) {
     const int b = bh / a.H, h = bh % a.H;
+    const int L = item_len<VARLEN>(a, b, S);
+    const int nb = (L + 31) >> 5;  // key / query blocks with a valid row
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = threadIdx.x + i * NT, r = c >> 3, ch = c & 7;
@@ -173,63 +208,88 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
     __syncthreads();
     if (bh + (int)gridDim.x < nitems) fetch(bh + gridDim.x);  // in flight during this item
 
-    af32x16 sc[NW];  // S^T tiles: lane owns query q, keys 32j + acc_row(i)
+    if (!VARLEN || q0 < L) {
+      const bool vq = !VARLEN || q < L;  // a padded query of the partial block: zero q, stores zeros
+      af32x16 sc[NW];  // S^T tiles: lane owns query q, keys 32j + acc_row(i)
 #pragma unroll
-    for (int j = 0; j < NW; ++j) {
-      sc[j] = zero16();
+      for (int j = 0; j < NW; ++j) {
+        if (VARLEN && j >= nb) continue;
+        sc[j] = zero16();
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
+        for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
+        if constexpr (VARLEN) {
+          if (j == nb - 1) {  // the partial key block: keys >= L leave the max and the sum
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+              if (32 * j + acc_row(i, hh) >= L) sc[j][i] = -INFINITY;
+          }
+        }
+      }
+      float m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        if (VARLEN && j >= nb) continue;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m = fmaxf(m, sc[j][i]);
+      }
+      m = fmaxf(m, __shfl_xor(m, 32));
+      float l = 0.f;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        if (VARLEN && j >= nb) continue;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          sc[j][i] = exp2f((sc[j][i] - m) * sl);
+          l += sc[j][i];
+        }
+      }
+      l += __shfl_xor(l, 32);
+      if (hh == 0) a.lse[(int64_t)bh * S + q] = vq ? m * a.scale + logf(l) : 0.f;
+      const float inv = 1.f / l;
+      const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
+      // O^T[d][q] = sum_key V^T[d][key] P^T[key][q]: B = this lane's probabilities (query q, keys in
+      // accumulator-row order), A = V^T read in that order; no P round trip through LDS
+      af32x16 ot[2] = {zero16(), zero16()};
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        if (VARLEN && j >= nb) continue;
+#pragma unroll
+        for (int ks2 = 0; ks2 < 2; ++ks2) {
+          float v[8];
+          bool kp[8];
+          if (drop) {  // elements e, e + 1 (e even) are keys kk, kk + 1 with kk even: one hash per pair
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) akeep2(key, rowidx + 32 * j + acc_row(8 * ks2 + e, hh), a.thresh, kp[e], kp[e + 1]);
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            v[e] = sc[j][8 * ks2 + e] * inv;
+            if (drop) v[e] = kp[e] ? v[e] * a.rescale : 0.f;
+          }
+          const abf16x8 pb = __builtin_bit_cast(
+              abf16x8, u32x4{pack_bf16x2_rne(v[0], v[1]), pack_bf16x2_rne(v[2], v[3]), pack_bf16x2_rne(v[4], v[5]),
+                             pack_bf16x2_rne(v[6], v[7])});
+#pragma unroll
+          for (int dt = 0; dt < 2; ++dt) ot[dt] = mfma(trfrag_accrows(Vs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), pb, ot[dt]);
+        }
+      }
+      // lane: query q, d = 32 dt + acc_row(i): 4 consecutive d per 4 accumulators -> 8-B stores
+      uint16_t* out = a.o + ((int64_t)b * S + q) * HD + h * D;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<uint2*>(out + 32 * dt + 8 * g + 4 * hh) =
+              vq ? make_uint2(pack_bf16x2_rne(ot[dt][4 * g], ot[dt][4 * g + 1]), pack_bf16x2_rne(ot[dt][4 * g + 2], ot[dt][4 * g + 3]))
+                 : make_uint2(0u, 0u);
+    } else {  // the whole query block is padding: zero O and lse, no MFMA
+      if (hh == 0) a.lse[(int64_t)bh * S + q] = 0.f;
+      uint16_t* out = a.o + ((int64_t)b * S + q) * HD + h * D;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(out + 32 * dt + 8 * g + 4 * hh) = make_uint2(0u, 0u);
     }
-    float m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NW; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) m = fmaxf(m, sc[j][i]);
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float l = 0.f;
-#pragma unroll
-    for (int j = 0; j < NW; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        sc[j][i] = exp2f((sc[j][i] - m) * sl);
-        l += sc[j][i];
-      }
-    l += __shfl_xor(l, 32);
-    if (hh == 0) a.lse[(int64_t)bh * S + q] = m * a.scale + logf(l);
-    const float inv = 1.f / l;
-    const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
-    // O^T[d][q] = sum_key V^T[d][key] P^T[key][q]: B = this lane's probabilities (query q, keys in
-    // accumulator-row order), A = V^T read in that order; no P round trip through LDS
-    af32x16 ot[2] = {zero16(), zero16()};
-#pragma unroll
-    for (int j = 0; j < NW; ++j)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        float v[8];
-        bool kp[8];
-        if (drop) {  // elements e, e + 1 (e even) are keys kk, kk + 1 with kk even: one hash per pair
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) akeep2(key, rowidx + 32 * j + acc_row(8 * ks2 + e, hh), a.thresh, kp[e], kp[e + 1]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[e] = sc[j][8 * ks2 + e] * inv;
-          if (drop) v[e] = kp[e] ? v[e] * a.rescale : 0.f;
-        }
-        const abf16x8 pb = __builtin_bit_cast(
-            abf16x8, u32x4{pack_bf16x2_rne(v[0], v[1]), pack_bf16x2_rne(v[2], v[3]), pack_bf16x2_rne(v[4], v[5]),
-                           pack_bf16x2_rne(v[6], v[7])});
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) ot[dt] = mfma(trfrag_accrows(Vs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), pb, ot[dt]);
-      }
-    // lane: query q, d = 32 dt + acc_row(i): 4 consecutive d per 4 accumulators -> 8-B stores
-    uint16_t* out = a.o + ((int64_t)b * S + q) * HD + h * D;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<uint2*>(out + 32 * dt + 8 * g + 4 * hh) =
-            make_uint2(pack_bf16x2_rne(ot[dt][4 * g], ot[dt][4 * g + 1]), pack_bf16x2_rne(ot[dt][4 * g + 2], ot[dt][4 * g + 3]));
     __syncthreads();  // K, V of this item read by every wave before the next item's stores
   }
 }
@@ -243,7 +303,14 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
 // computed, so the HBM time of one item hides behind the MFMA/LDS work of the previous one (a
 // workgroup per item loaded, synchronised and computed strictly in turn: 189 us per BERT layer,
 // ~2 TB/s, profiles/bert_base_b256_r4 profile).
-template <int NW>
+//
+// VARLEN (a.lens given; L, nb as in the forward): rows >= L of Q, K, V, dO, O and lse are never loaded,
+// zeros are staged over the whole tile height instead, so nothing of a previous, longer item is left
+// in those five tiles (and D_s, lse_s). Pd and dS are written in phase 1 for key blocks < nb and
+// query blocks < nb only, with zeros at masked keys and padded queries, and phases 2 and 3 read
+// exactly that region (chunks < 2 nb of blocks < nb); what the previous item left outside it is
+// never read. Blocks >= nb store zero dK, dV / dQ and zero column sums. All skips are wave-uniform.
+template <int NW, bool VARLEN>
 __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
   constexpr int S = 32 * NW, LDP = S + 8;
   constexpr int NT = 128 * NW;
@@ -276,21 +343,29 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     const int64_t ob = (int64_t)b * S * HD + h * D;
+    const int Lf = item_len<VARLEN>(a, b, S);
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = threadIdx.x + i * NT, r = c >> 3, ch = c & 7;
+      if (!VARLEN || r < Lf) {
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
-        pf[t][i] = *reinterpret_cast<const u32x4*>(base + t * HD + (int64_t)r * qkv_rs + ch * 8);
-      pf[3][i] = *reinterpret_cast<const u32x4*>(a.dout + ob + (int64_t)r * HD + ch * 8);
-      pf[4][i] = *reinterpret_cast<const u32x4*>(a.o + ob + (int64_t)r * HD + ch * 8);
+        for (int t = 0; t < 3; ++t)
+          pf[t][i] = *reinterpret_cast<const u32x4*>(base + t * HD + (int64_t)r * qkv_rs + ch * 8);
+        pf[3][i] = *reinterpret_cast<const u32x4*>(a.dout + ob + (int64_t)r * HD + ch * 8);
+        pf[4][i] = *reinterpret_cast<const u32x4*>(a.o + ob + (int64_t)r * HD + ch * 8);
+      } else {
+#pragma unroll
+        for (int t = 0; t < 5; ++t) pf[t][i] = zero4();
+      }
     }
-    if (threadIdx.x < S) plse = a.lse[(int64_t)bh * S + threadIdx.x];
+    if (threadIdx.x < S) plse = (!VARLEN || (int)threadIdx.x < Lf) ? a.lse[(int64_t)bh * S + threadIdx.x] : 0.f;
   };
   if ((int)blockIdx.x < nitems) fetch(blockIdx.x);
 
   for (int bh = blockIdx.x; bh < nitems; bh += gridDim.x) {
     const int b = bh / a.H, h = bh % a.H;
+    const int L = item_len<VARLEN>(a, b, S);
+    const int nb = (L + 31) >> 5;  // key / query blocks with a valid row
     // the prefetched item -> LDS; D[q] = sum_d dO[q, d] O[q, d] (8 lanes per row)
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
@@ -318,46 +393,52 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
     // phase 1: waves (w, sub) own keys k0..k0+31; recompute S^T and dP^T against the query blocks
     // t = sub, sub + 2, ...
     const int k0 = 32 * w;
-    abf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      kf[ks] = rowfrag(Ks, LDT * 2, k0, 16 * ks);
-      vf[ks] = rowfrag(Vs, LDT * 2, k0, 16 * ks);
-    }
-#pragma unroll
-    for (int t = sub; t < NW; t += 2) {
-      af32x16 st = zero16(), dpt = zero16();
+    if (!VARLEN || w < nb) {
+      abf16x8 kf[4], vf[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        st = mfma(kf[ks], rowfrag(Qs, LDT * 2, 32 * t, 16 * ks), st);
-        dpt = mfma(vf[ks], rowfrag(dOs, LDT * 2, 32 * t, 16 * ks), dpt);
+        kf[ks] = rowfrag(Ks, LDT * 2, k0, 16 * ks);
+        vf[ks] = rowfrag(Vs, LDT * 2, k0, 16 * ks);
       }
-      const int q = 32 * t + (lane & 31);
-      const float lse2 = lse_s[q] * 1.4426950408889634f, Dq = D_s[q];
-      const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float pv[4], dv[4];
-        bool kp[4];
-        if (drop) {  // keys k0 + 8g + 4hh + e: pairs (0, 1), (2, 3) share one hash
-          akeep2(key, rowidx + k0 + 8 * g + 4 * hh, a.thresh, kp[0], kp[1]);
-          akeep2(key, rowidx + k0 + 8 * g + 4 * hh + 2, a.thresh, kp[2], kp[3]);
+      for (int t = sub; t < NW; t += 2) {
+        if (VARLEN && t >= nb) continue;
+        af32x16 st = zero16(), dpt = zero16();
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          st = mfma(kf[ks], rowfrag(Qs, LDT * 2, 32 * t, 16 * ks), st);
+          dpt = mfma(vf[ks], rowfrag(dOs, LDT * 2, 32 * t, 16 * ks), dpt);
         }
+        const int q = 32 * t + (lane & 31);
+        const float lse2 = lse_s[q] * 1.4426950408889634f, Dq = D_s[q];
+        const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int i = 4 * g + e;
-          const float p = exp2f(st[i] * sl - lse2);
-          float pd = p, dp = dpt[i];
-          if (drop) {
-            pd = kp[e] ? p * a.rescale : 0.f;
-            dp = kp[e] ? dp * a.rescale : 0.f;
+        for (int g = 0; g < 4; ++g) {
+          float pv[4], dv[4];
+          bool kp[4];
+          if (drop) {  // keys k0 + 8g + 4hh + e: pairs (0, 1), (2, 3) share one hash
+            akeep2(key, rowidx + k0 + 8 * g + 4 * hh, a.thresh, kp[0], kp[1]);
+            akeep2(key, rowidx + k0 + 8 * g + 4 * hh + 2, a.thresh, kp[2], kp[3]);
           }
-          pv[e] = pd;
-          dv[e] = p * (dp - Dq);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int i = 4 * g + e;
+            const float p = exp2f(st[i] * sl - lse2);
+            float pd = p, dp = dpt[i];
+            if (drop) {
+              pd = kp[e] ? p * a.rescale : 0.f;
+              dp = kp[e] ? dp * a.rescale : 0.f;
+            }
+            pv[e] = pd;
+            dv[e] = p * (dp - Dq);
+            if constexpr (VARLEN) {  // masked key or padded query: exact zeros into Pd and dS
+              if (q >= L || k0 + 8 * g + 4 * hh + e >= L) pv[e] = dv[e] = 0.f;
+            }
+          }
+          const int off = q * LDP * 2 + (k0 + 8 * g + 4 * hh) * 2;
+          *reinterpret_cast<uint2*>(Pd + off) = make_uint2(pack_bf16x2_rne(pv[0], pv[1]), pack_bf16x2_rne(pv[2], pv[3]));
+          *reinterpret_cast<uint2*>(dS + off) = make_uint2(pack_bf16x2_rne(dv[0], dv[1]), pack_bf16x2_rne(dv[2], dv[3]));
         }
-        const int off = q * LDP * 2 + (k0 + 8 * g + 4 * hh) * 2;
-        *reinterpret_cast<uint2*>(Pd + off) = make_uint2(pack_bf16x2_rne(pv[0], pv[1]), pack_bf16x2_rne(pv[2], pv[3]));
-        *reinterpret_cast<uint2*>(dS + off) = make_uint2(pack_bf16x2_rne(dv[0], dv[1]), pack_bf16x2_rne(dv[2], dv[3]));
       }
     }
     __syncthreads();
@@ -370,6 +451,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       af32x16 dv = zero16(), dk = zero16();
 #pragma unroll
       for (int ks = 0; ks < S / 16; ++ks) {
+        if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a key block past L keeps its zeros
         dv = mfma(trfrag(Pd, LDP * 2, 16 * ks, k0), trfrag(dOs, LDT * 2, 16 * ks, 32 * dt), dv);
         dk = mfma(trfrag(dS, LDP * 2, 16 * ks, k0), trfrag(Qs, LDT * 2, 16 * ks, 32 * dt), dk);
       }
@@ -398,7 +480,10 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       const int dt = sub;
       af32x16 dq = zero16();
 #pragma unroll
-      for (int ks = 0; ks < S / 16; ++ks) dq = mfma(rowfrag(dS, LDP * 2, q0, 16 * ks), trfrag(Ks, LDT * 2, 16 * ks, 32 * dt), dq);
+      for (int ks = 0; ks < S / 16; ++ks) {
+        if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a query block past L keeps its zeros
+        dq = mfma(rowfrag(dS, LDP * 2, q0, 16 * ks), trfrag(Ks, LDT * 2, 16 * ks, 32 * dt), dq);
+      }
       const int d = 32 * dt + (lane & 31);
       float sq = 0.f;
 #pragma unroll
@@ -431,49 +516,51 @@ bool attn_supported(int S, int head_dim) { return head_dim == D && S >= 32 && S 
 static int fwd_lds(int S) { return 2 * S * LDT * 2; }
 static int bwd_lds(int S) { return 4 * S * LDT * 2 + 2 * S * (S + 8) * 2 + 2 * S * 4 + (S / 32) * 3 * 64 * 4; }
 
-template <int NW>
+template <int NW, bool VARLEN>
 static hipError_t launch_fwd_t(const AttnArgs& a, hipStream_t st) {
   const int lds = fwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items bh, bh + grid, ...
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW>), 64 * NW,
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN>), 64 * NW,
                                                    lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  const int grid = std::min(a.B * a.H, per_cu * attn_cus());
-  hipLaunchKernelGGL(attn_fwd_kernel<NW>, dim3(grid), dim3(64 * NW), lds, st, a);
+  int grid = std::min(a.B * a.H, per_cu * attn_cus());
+  if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
+  hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN>), dim3(grid), dim3(64 * NW), lds, st, a);
   return hipGetLastError();
 }
-template <int NW>
+template <int NW, bool VARLEN>
 static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
   const int lds = bwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW, VARLEN>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: one workgroup per CU (the LDS image admits one), each walks items bh, bh + grid, ...
-  const int grid = std::min(a.B * a.H, attn_cus());
-  hipLaunchKernelGGL(attn_bwd_kernel<NW>, dim3(grid), dim3(128 * NW), lds, st, a);
+  int grid = std::min(a.B * a.H, attn_cus());
+  if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
+  hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN>), dim3(grid), dim3(128 * NW), lds, st, a);
   return hipGetLastError();
 }
 
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
   switch (a.S / 32) {
-    case 1: return launch_fwd_t<1>(a, st);
-    case 2: return launch_fwd_t<2>(a, st);
-    case 3: return launch_fwd_t<3>(a, st);
-    default: return launch_fwd_t<4>(a, st);
+    case 1: return a.lens ? launch_fwd_t<1, true>(a, st) : launch_fwd_t<1, false>(a, st);
+    case 2: return a.lens ? launch_fwd_t<2, true>(a, st) : launch_fwd_t<2, false>(a, st);
+    case 3: return a.lens ? launch_fwd_t<3, true>(a, st) : launch_fwd_t<3, false>(a, st);
+    default: return a.lens ? launch_fwd_t<4, true>(a, st) : launch_fwd_t<4, false>(a, st);
   }
 }
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
   switch (a.S / 32) {
-    case 1: return launch_bwd_t<1>(a, st);
-    case 2: return launch_bwd_t<2>(a, st);
-    case 3: return launch_bwd_t<3>(a, st);
-    default: return launch_bwd_t<4>(a, st);
+    case 1: return a.lens ? launch_bwd_t<1, true>(a, st) : launch_bwd_t<1, false>(a, st);
+    case 2: return a.lens ? launch_bwd_t<2, true>(a, st) : launch_bwd_t<2, false>(a, st);
+    case 3: return a.lens ? launch_bwd_t<3, true>(a, st) : launch_bwd_t<3, false>(a, st);
+    default: return a.lens ? launch_bwd_t<4, true>(a, st) : launch_bwd_t<4, false>(a, st);
   }
 }
 

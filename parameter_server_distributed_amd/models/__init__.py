@@ -88,9 +88,10 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
         m = prepare(BertForMLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")}),
                     device, dtype)
         seq = kw.get("seq_len", 128)
+        min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
 
         def make(batch, device, seed=0):
-            return bert_batch(batch, seq, m.vocab, device, seed)
+            return bert_batch(batch, seq, m.vocab, device, seed, min_len=min_len)
 
         return ModelSpec(name, m, make, m.loss, "sequences")
     raise KeyError(f"unknown model {name!r}; available: {MODELS}")

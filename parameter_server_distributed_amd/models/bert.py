@@ -41,10 +41,10 @@ class BertLayer(nn.Module):
         self.ln2 = FusedAddLayerNorm(hidden, eps=1e-12, p=dropout, seed=2 * index + 2)
         self.p = dropout
 
-    def forward(self, x):
+    def forward(self, x, lens=None):
         # each residual LayerNorm hands the gradient of its x input to the Linear that also reads x
         # (folded into that Linear's bwd-data GEMM, ops/layernorm.py)
-        x = self.ln1(x, self.proj(self.attn(self.qkv(x))), x_grad_to=self.qkv)
+        x = self.ln1(x, self.proj(self.attn(self.qkv(x), lens)), x_grad_to=self.qkv)
         return self.ln2(x, self.ffn2(self.ffn1(x)), x_grad_to=self.ffn1)
 
 
@@ -70,11 +70,14 @@ class BertForMLM(nn.Module):
                 nn.init.normal_(m.weight, std=0.02)
 
     def forward(self, batch):
-        ids, types, mlm_pos = batch
+        # (ids, types, mlm_pos) or, for a padded batch, (ids, types, mlm_pos, lens): int32 [B] lengths,
+        # positions >= lens[b] are padding that no attention key or query row reads
+        ids, types, mlm_pos = batch[:3]
+        lens = batch[3] if len(batch) > 3 else None
         bump_step(self)
         x = self.emb(ids, types)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x, lens)
         # MLM head only on the masked positions (max_predictions_per_seq per sequence, as in the
         # original BERT pre-training): 6-7x less head/decoder/softmax work than all tokens
         x = x.reshape(-1, x.shape[-1]).index_select(0, mlm_pos)
@@ -85,14 +88,35 @@ class BertForMLM(nn.Module):
         return cross_entropy(logits, labels)  # fused bf16 softmax-CE kernels (ops/loss.py)
 
 
-def bert_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, mask_prob: float = 0.15):
+def bert_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, mask_prob: float = 0.15,
+               min_len: int | None = None):
     """Synthetic pre-training batch: random ids, sentence-B types for the second half, and
-    round(mask_prob * seq) masked positions per sequence (flat indices) with their labels."""
+    round(mask_prob * seq) masked positions per sequence (flat indices) with their labels.
+
+    With ``min_len`` the sequences are padded: lengths are uniform in [min_len, seq], ids past a
+    length are 0, the masked positions are drawn among the valid ones, and the batch tuple gains
+    ``lens`` (int32 [B]). The prediction count per sequence stays round(mask_prob * seq) (the
+    original BERT's max_predictions_per_seq): surplus slots point at position 0 with label -100,
+    which the loss ignores."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     ids = torch.randint(0, vocab, (batch, seq), generator=g)
     types = (torch.arange(seq)[None, :] >= seq // 2).long().expand(batch, seq).contiguous()
     npred = max(1, round(mask_prob * seq))
-    cols = torch.stack([torch.randperm(seq, generator=g)[:npred].sort().values for _ in range(batch)])
+    if min_len is None:
+        cols = torch.stack([torch.randperm(seq, generator=g)[:npred].sort().values for _ in range(batch)])
+        flat = (cols + torch.arange(batch)[:, None] * seq).reshape(-1)
+        labels = ids.reshape(-1)[flat]
+        return (ids.to(device), types.to(device), flat.to(device)), labels.to(device)
+    if not 1 <= int(min_len) <= seq:
+        raise ValueError(f"min_len must be in [1, {seq}], got {min_len}")
+    lens = torch.randint(int(min_len), seq + 1, (batch,), generator=g)
+    ids = ids * (torch.arange(seq)[None, :] < lens[:, None])
+    cols = torch.zeros(batch, npred, dtype=torch.long)
+    used = torch.zeros(batch, npred, dtype=torch.bool)
+    for b in range(batch):
+        c = torch.randperm(int(lens[b]), generator=g)[:npred].sort().values
+        cols[b, :c.numel()] = c
+        used[b, :c.numel()] = True
     flat = (cols + torch.arange(batch)[:, None] * seq).reshape(-1)
-    labels = ids.reshape(-1)[flat]
-    return (ids.to(device), types.to(device), flat.to(device)), labels.to(device)
+    labels = torch.where(used.reshape(-1), ids.reshape(-1)[flat], torch.full_like(flat, -100))
+    return (ids.to(device), types.to(device), flat.to(device), lens.to(torch.int32).to(device)), labels.to(device)

@@ -10,8 +10,13 @@ Attention dropout uses the counter hash shared with the fused LayerNorm (per-sit
 model's device step counter, see ``ops/layernorm.bump_step``): masks are regenerated in backward
 and a replayed hipGraph draws fresh ones each step.
 
+Variable-length batches pass ``lens`` (int32 ``[B]`` on qkv's device): sequence ``b`` has valid
+tokens ``0 .. lens[b]-1`` (clamped to ``[0, S]`` on the device, never read back by the host). Keys
+past the length get probability exactly 0, output and gradient rows past it are exact zeros, and
+padded rows of qkv / dO are never read.
+
 CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128} use SDPA -- the reference
-the tests compare against.
+the tests compare against -- with the same length semantics.
 """
 from __future__ import annotations
 
@@ -26,15 +31,15 @@ from .. import native
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, mod, p):
+    def forward(ctx, qkv, mod, p, lens=None):
         # qkv straight from an MfmaLinear with a bias (ops/linear.py tags its output): backward also
         # sums dqkv's columns -- that Linear's bias gradient -- and hands it over
         src = getattr(qkv, "_psd_src", None) if _feat("attn_bias") else None
         ctx.src = src if (src is not None and src[0].bias is not None and src[0].act in (None, "none")
                           and src[0]._psd_tok == src[1]) else None
         qkv = qkv.contiguous()
-        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step)
-        ctx.mod, ctx.p = mod, p
+        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens)
+        ctx.mod, ctx.p, ctx.lens = mod, p, lens
         ctx.save_for_backward(qkv, o, lse)
         return o
 
@@ -49,10 +54,10 @@ class _AttnFn(torch.autograd.Function):
             db = sink(lin.bias) if sink is not None else None
             if db is None:
                 db = torch.empty_like(lin.bias)
-        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db)
+        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens)
         if db is not None:
             ctx.src[0]._psd_bias_hand = (ctx.src[1], dqkv.data_ptr(), db)
-        return dqkv, None, None
+        return dqkv, None, None, None
 
 
 class FusedSelfAttention(nn.Module):
@@ -70,12 +75,22 @@ class FusedSelfAttention(nn.Module):
         return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0
                 and E // (3 * self.heads) == 64 and S % 32 == 0 and 32 <= S <= 128)
 
-    def forward(self, qkv):
+    def forward(self, qkv, lens=None):
         p = self.p if self.training else 0.0
         if self._kernel_ok(qkv):
-            return _AttnFn.apply(qkv, self, p)
+            return _AttnFn.apply(qkv, self, p, lens)
         B, S, E = qkv.shape
         H = self.heads
         q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)
-        a = F.scaled_dot_product_attention(q, k, v, dropout_p=p)
+        if lens is None:
+            a = F.scaled_dot_product_attention(q, k, v, dropout_p=p)
+            return a.transpose(1, 2).reshape(B, S, E // 3)
+        valid = torch.arange(S, device=qkv.device)[None, :] < lens.clamp(0, S)[:, None]  # [B, S]
+        row = valid[:, None, :, None]
+        # padded rows never enter a product (where, not a multiply: 0 * NaN = NaN)
+        q, k, v = (torch.where(row, t, torch.zeros((), dtype=t.dtype, device=t.device)) for t in (q, k, v))
+        # padded queries see every key (their zero q gives a finite uniform row, also at L = 0) and
+        # are multiplied by zero below
+        mask = valid[:, None, None, :] | ~row
+        a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p) * row.to(q.dtype)
         return a.transpose(1, 2).reshape(B, S, E // 3)
