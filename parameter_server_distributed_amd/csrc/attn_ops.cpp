@@ -1,4 +1,5 @@
-// Tensor glue for the fused self-attention kernels (kernels/attention.hip).
+// Tensor glue for the fused self-attention kernels: kernels/attention.hip (S <= 128, the whole head in
+// LDS) and kernels/attention_long.hip (128 < S <= 512, streaming); attn_fwd / attn_bwd dispatch on S.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -23,7 +24,9 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                    const c10::optional<at::Tensor>& lens, int64_t grid_cap) {
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
   const int64_t dh = qkv.size(2) / (3 * heads);
-  TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh), "psd attn: needs head dim 64 and S in {32, 64, 96, 128}");
+  TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh) || attn_long_supported((int)qkv.size(1), (int)dh),
+              "psd attn: needs head dim 64 and S in {32, 64, 96, 128} (whole-head kernels) or in "
+              "{192, 256, 320, 384, 448, 512} (streaming kernels)");
   TORCH_CHECK(p >= 0.0 && p < 1.0, "psd attn: dropout p must be in [0, 1)");
   AttnArgs a{};
   a.qkv = reinterpret_cast<const uint16_t*>(qkv.data_ptr());
@@ -56,14 +59,16 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.lse = lse.data_ptr<float>();
-  hipError_t e = launch_attn_fwd(a, attn_stream(qkv));
+  hipError_t e = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads))) ? launch_attn_long_fwd(a, attn_stream(qkv))
+                                                                            : launch_attn_fwd(a, attn_stream(qkv));
   TORCH_CHECK(e == hipSuccess, "psd attn fwd: ", hipGetErrorString(e));
   return {o, lse};
 }
 
 // bias_out (optional, [3*H*Dh] bf16/fp32): also the QKV Linear's bias gradient = the column sums of
-// dqkv, from per-sequence partials the kernel writes + one deterministic column reduce (with lens the
-// padded rows of dqkv are written as zeros, so the same sums hold).
+// dqkv, from per-sequence (streaming kernels: per 128-row tile) partials the kernel writes + one
+// deterministic column reduce (with lens the padded rows of dqkv are written as zeros, so the same
+// sums hold).
 // lens (optional, int32 [B]): valid rows per sequence; grid_cap > 0 bounds the persistent grid (tests).
 at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
@@ -86,18 +91,26 @@ at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::
   a.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
   a.dqkv = reinterpret_cast<uint16_t*>(dqkv.data_ptr());
   const bool bias = bias_out.has_value() && bias_out->defined();
+  const bool is_long = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads)));
+  const int prows = is_long ? attn_long_bpart_rows(a.B, a.S) : a.B;  // partial rows: one per work item of a sequence
   at::Tensor bpart;
   if (bias) {
     TORCH_CHECK(bias_out->is_cuda() && bias_out->is_contiguous() && bias_out->numel() == qkv.size(2) &&
                     (bias_out->scalar_type() == at::kBFloat16 || bias_out->scalar_type() == at::kFloat),
                 "psd attn bwd: bias_out must be a contiguous [3*H*Dh] bf16/fp32 tensor");
-    bpart = at::empty({(int64_t)a.B, qkv.size(2)}, qkv.options().dtype(at::kFloat));
+    bpart = at::empty({(int64_t)prows, qkv.size(2)}, qkv.options().dtype(at::kFloat));
     a.bpart = bpart.data_ptr<float>();
   }
-  hipError_t e = launch_attn_bwd(a, attn_stream(qkv));
+  hipError_t e;
+  if (is_long) {  // D = rowsum(dO . O): written by the dQ pass, read by the dK/dV pass
+    at::Tensor dsum = at::empty({(int64_t)a.B, heads, (int64_t)a.S}, qkv.options().dtype(at::kFloat));
+    e = launch_attn_long_bwd(a, dsum.data_ptr<float>(), attn_stream(qkv));
+  } else {
+    e = launch_attn_bwd(a, attn_stream(qkv));
+  }
   TORCH_CHECK(e == hipSuccess, "psd attn bwd: ", hipGetErrorString(e));
   if (bias) {
-    e = launch_colsum_final(a.bpart, a.B, (int)qkv.size(2), bias_out->data_ptr(),
+    e = launch_colsum_final(a.bpart, prows, (int)qkv.size(2), bias_out->data_ptr(),
                             bias_out->scalar_type() == at::kBFloat16, 0, attn_stream(qkv));
     TORCH_CHECK(e == hipSuccess, "psd attn bwd bias: ", hipGetErrorString(e));
   }

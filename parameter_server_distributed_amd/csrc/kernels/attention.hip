@@ -16,6 +16,9 @@
 // Padded batches pass per-sequence lengths (AttnArgs::lens): separate VARLEN instantiations skip the
 // 32-row blocks past a length, mask the partial one and never read a padded row; without lengths the
 // launchers pick the VARLEN = false instantiations, which are the full-length kernels unchanged.
+// Longer sequences (128 < S <= 512, S % 64 == 0) do not fit this whole-head image; they run the
+// streaming kernels of attention_long.hip under the same contracts (launch_attn_fwd / launch_attn_bwd
+// serve S <= 128 only; the tensor glue in attn_ops.cpp picks the family by S).
 //
 // Replaces what the reference's stub gradient (src/worker.cpp:316-329) stands in for: the model's
 // real forward/backward; the attention is BERT's (BASELINE config 4).
@@ -23,85 +26,13 @@
 
 #include "common.h"
 #include "launchers_attn.h"
+#include "attn_frag.h"
 
 namespace psd {
 
 namespace {
 
-typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
-typedef short as16x4 __attribute__((ext_vector_type(4)));
-typedef float af32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) as16x4 alds_s16x4;
-
-constexpr int D = 64;                 // head dim
-constexpr int LDT = D + 8;            // Q/K/V/dO tile row stride (elements): 144 B
-
-__device__ __forceinline__ uint32_t amix32(uint32_t h) {  // murmur3 finalizer (as layernorm.hip)
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-// (common.h drop_keep: one hash per element pair, 16 bits each; fwd and bwd index elements alike)
-// keep flags of the element pair (idx, idx + 1), idx even, from ONE hash -- drop_keep's mask bit for bit.
-// (Calling drop_keep per element hashed every pair twice: dropout cost the forward 57 % of its
-// time, 48.6 -> 76.2 us per BERT layer, tools/attn_bench.py.)
-__device__ __forceinline__ void akeep2(uint32_t key, uint64_t idx, uint32_t thresh, bool& k0, bool& k1) {
-  const uint32_t h = drop_pair_bits(key, idx);
-  k0 = (h & 0xffffu) >= (thresh >> 16);
-  k1 = (h >> 16) >= (thresh >> 16);
-}
-__device__ __forceinline__ uint32_t attn_key(uint32_t seed, const int64_t* step) {
-  return amix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
-}
-
-// A/B fragment whose 8 k-values are contiguous in LDS: lane -> row r0 + lane%32, k = k0 + 8*(lane/32) + e
-__device__ __forceinline__ abf16x8 rowfrag(const uint8_t* base, int stride_b, int r0, int k0) {
-  const int lane = threadIdx.x & 63;
-  const u32x4 w = *reinterpret_cast<const u32x4*>(base + (r0 + (lane & 31)) * stride_b + (k0 + 8 * (lane >> 5)) * 2);
-  return __builtin_bit_cast(abf16x8, w);
-}
-// Same fragment from a [k][col] tile (col contiguous): ds_read_b64_tr_b16 transposes within 16 lanes.
-// lane -> col c0 + lane%32, k = k0 + 8*(lane/32) + e
-__device__ __forceinline__ abf16x8 trfrag(const uint8_t* base, int stride_b, int k0, int c0) {
-  const int lane = threadIdx.x & 63;
-  const int G = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int k = k0 + 8 * (G >> 1) + q;
-  const int col = c0 + 16 * (G & 1) + 4 * p;
-  const as16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((alds_s16x4*)(base + k * stride_b + col * 2));
-  const as16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((alds_s16x4*)(base + (k + 4) * stride_b + col * 2));
-  as16x4 both[2] = {lo, hi};
-  return __builtin_bit_cast(abf16x8, both);
-}
-
-// trfrag with the key order of a 32x32 accumulator's rows: k-slot e of lane half hh is key
-// kb + 8*(e/4) + 4*hh + e%4 -- exactly the keys acc_row(8*ks2 + e, hh) a lane holds in registers, so the
-// softmax probabilities feed the P V MFMA as its B operand straight from the S^T accumulators
-// (the k sum is order-free; A = V^T is read in the same permuted order)
-__device__ __forceinline__ abf16x8 trfrag_accrows(const uint8_t* base, int stride_b, int kb, int c0) {
-  const int lane = threadIdx.x & 63;
-  const int G = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int k = kb + 4 * (G >> 1) + q;
-  const int col = c0 + 16 * (G & 1) + 4 * p;
-  const as16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((alds_s16x4*)(base + k * stride_b + col * 2));
-  const as16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((alds_s16x4*)(base + (k + 8) * stride_b + col * 2));
-  as16x4 both[2] = {lo, hi};
-  return __builtin_bit_cast(abf16x8, both);
-}
-
-__device__ __forceinline__ af32x16 mfma(abf16x8 a, abf16x8 b, af32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ af32x16 zero16() {
-  af32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// accumulator element i of a 32x32 tile: row (i&3) + 8*(i>>2) + 4*(lane/32), col lane%32
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
+// (fragment, dropout-hash and length helpers: attn_frag.h, shared with attention_long.hip)
 
 // rows [0, S) of a [.., S, 3, H, 64] (or [.., S, H, 64]) tensor -> LDS tile [S][LDT]
 __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, int64_t row_stride, int S) {
@@ -111,15 +42,6 @@ __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, in
         *reinterpret_cast<const u32x4*>(src + (int64_t)r * row_stride + ch * 8);
   }
 }
-
-// valid rows of sequence b: S without lengths; else lens[b] clamped to [0, S] here, on the device (the
-// host never reads lens, so a replayed graph sees the current values)
-template <bool VARLEN>
-__device__ __forceinline__ int item_len(const AttnArgs& a, int b, int S) {
-  if constexpr (VARLEN) return min(max(a.lens[b], 0), S);
-  else return S;
-}
-__device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
 
 }  // namespace
 

@@ -3,7 +3,7 @@
 #include <cstdint>
 
 namespace psd {
-// Fused short-sequence self-attention (kernels/attention.hip): packed qkv [B, S, 3, H, 64] in,
+// Fused self-attention (kernels/attention.hip for S <= 128, attention_long.hip above): packed qkv [B, S, 3, H, 64] in,
 // o [B, S, H, 64] out; backward writes the packed dqkv.
 struct AttnArgs {
   const uint16_t* qkv;    // [B, S, 3, H, 64] bf16
@@ -26,4 +26,12 @@ struct AttnArgs {
 bool attn_supported(int S, int head_dim);
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t stream);
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t stream);
+
+// Streaming kernels for 128 < S <= 512, S % 64 == 0 (kernels/attention_long.hip): the same AttnArgs and
+// contracts, except that bpart has attn_long_bpart_rows(B, S) rows of [3*H*64] (one per 128-row tile
+// of a sequence) and backward takes an fp32 [B, H, S] scratch for D = rowsum(dO . O).
+bool attn_long_supported(int S, int head_dim);
+int attn_long_bpart_rows(int B, int S);
+hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);
+hipError_t launch_attn_long_bwd(const AttnArgs& a, float* dsum, hipStream_t stream);
 }  // namespace psd

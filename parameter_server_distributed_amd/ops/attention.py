@@ -1,10 +1,14 @@
-"""Multi-head self-attention on the fused gfx950 kernels of ``csrc/kernels/attention.hip``.
+"""Multi-head self-attention on the fused gfx950 kernels of ``csrc/kernels/attention.hip`` (S <= 128)
+and ``csrc/kernels/attention_long.hip`` (S in 192 .. 512, a multiple of 64).
 
 Input is the packed QKV projection output ``[B, S, 3*H*64]`` exactly as the QKV Linear writes it;
 output is ``[B, S, H*64]`` exactly as the output projection reads it. Backward returns the packed
 ``dQKV``. Compared with ``F.scaled_dot_product_attention`` on q/k/v views this removes the
-transpose copy of the output, the stack/cat of dq/dk/dv and the layout copy in backward, and runs
-the whole head (S <= 128) out of LDS in one kernel per direction.
+transpose copy of the output, the stack/cat of dq/dk/dv and the layout copy in backward. Up to
+S = 128 the whole head runs out of LDS in one kernel per direction; from S = 192 to 512 (steps of 64)
+streaming kernels keep Q (backward: also K, V) fragments in registers and walk the other operand in
+64-row chunks with an online softmax -- same layouts, ``lse``, ``lens``, dropout hash and QKV-bias
+hand-over (feature ``attn_long``; off: those lengths take SDPA as well).
 
 Attention dropout uses the counter hash shared with the fused LayerNorm (per-site seed + the
 model's device step counter, see ``ops/layernorm.bump_step``): masks are regenerated in backward
@@ -15,8 +19,8 @@ tokens ``0 .. lens[b]-1`` (clamped to ``[0, S]`` on the device, never read back 
 past the length get probability exactly 0, output and gradient rows past it are exact zeros, and
 padded rows of qkv / dO are never read.
 
-CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128} use SDPA -- the reference
-the tests compare against -- with the same length semantics.
+CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128, 192, 256, 320, 384, 448, 512}
+use SDPA -- the reference the tests compare against -- with the same length semantics.
 """
 from __future__ import annotations
 
@@ -75,10 +79,24 @@ class FusedSelfAttention(nn.Module):
         return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0
                 and E // (3 * self.heads) == 64 and S % 32 == 0 and 32 <= S <= 128)
 
+    @staticmethod
+    def long_kernel_shape_ok(S: int, head_dim: int) -> bool:
+        """Shapes of the streaming kernels (attention_long.hip): head dim 64, S = 192, 256, .., 512."""
+        return head_dim == 64 and 128 < S <= 512 and S % 64 == 0
+
+    def _long_kernel_ok(self, qkv) -> bool:
+        B, S, E = qkv.shape
+        return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0
+                and self.long_kernel_shape_ok(S, E // (3 * self.heads)) and _feat("attn_long"))
+
     def forward(self, qkv, lens=None):
         p = self.p if self.training else 0.0
-        if self._kernel_ok(qkv):
+        if self._kernel_ok(qkv) or self._long_kernel_ok(qkv):
             return _AttnFn.apply(qkv, self, p, lens)
+        return self._sdpa(qkv, lens, p)
+
+    def _sdpa(self, qkv, lens, p):
+        """``F.scaled_dot_product_attention`` on transposed views (what no kernel takes; tools/attn_bench.py --sdpa)."""
         B, S, E = qkv.shape
         H = self.heads
         q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)

@@ -109,6 +109,8 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "linear_tune": (True, "per-shape MFMA / hipBLASLt choice for Linear layers; off: MFMA only"),
     "gelu_fuse": (True, "GELU backward in the consumer Linear's bwd-data GEMM epilogue"),
     "attn_bias": (True, "QKV bias gradient handed over by the attention backward"),
+    "attn_long": (True, "streaming fused attention kernels for S = 192 .. 512 (multiples of 64); off: SDPA on "
+                        "transposed views there, as for every other S > 128"),
 }
 
 _FEAT_ENV: str | None = None

@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
-"""Time the fused attention kernels (csrc/kernels/attention.hip) at BERT-base pre-training shape
-(B 256, S 128, 12 heads of 64) with and without attention dropout: us per call, the compulsory HBM
-bytes over that time, and the MFMA rate.
+"""Time the fused attention kernels (csrc/kernels/attention.hip, attention_long.hip) with and without
+attention dropout: us per call, the compulsory HBM bytes over that time, and the MFMA rate. The
+default shape is BERT-base pre-training (B 256, S 128, 12 heads of 64).
 
   python tools/attn_bench.py
   python tools/attn_bench.py --min-len 16   # padded batch: lengths uniform in [16, S], passed as lens
+  python tools/attn_bench.py --seq 512 --batch 64 --sdpa   # the streaming kernels against the SDPA path
 
 With --min-len the bytes count the valid rows only (what the variable-length kernels have to move)
 and the FLOP rate counts the valid (query, key) pairs.
+
+--sdpa also times the module's SDPA path (F.scaled_dot_product_attention on transposed views, through
+autograd, with its layout copies and, with lengths, its mask) on the same data as a second pair of
+columns; both paths are then timed alternately in --windows windows and every figure is the median
+(min - max) over the windows. TB/s and TF/s are from the kernel path's median.
 """
 import argparse
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,14 +37,25 @@ def t_us(fn, it=20):
     return s.elapsed_time(e) / it * 1e3
 
 
+def _fmt(ts):
+    if len(ts) == 1:
+        return f"{ts[0]:.1f}"
+    return f"{statistics.median(ts):.1f} ({min(ts):.1f} - {max(ts):.1f})"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--min-len", type=int, default=None, help="draw lengths uniformly in [N, S] and pass them as lens")
     ap.add_argument("--iters", type=int, default=20, help="timed calls per figure")
+    ap.add_argument("--seq", type=int, default=128, help="sequence length S")
+    ap.add_argument("--batch", type=int, default=256, help="batch size B")
+    ap.add_argument("--sdpa", action="store_true", help="also time the module's SDPA path on the same data")
+    ap.add_argument("--windows", type=int, default=None, help="timing windows per figure (default 1, with --sdpa 5)")
     args = ap.parse_args()
     C = native()
     dev = torch.device("cuda")
-    B, S, H, D = 256, 128, 12, 64
+    B, S, H, D = args.batch, args.seq, 12, 64
+    nwin = args.windows if args.windows is not None else (5 if args.sdpa else 1)
     qkv = (torch.randn(B, S, 3 * H * D, device=dev) * 0.5).to(torch.bfloat16)
     do = torch.randn(B, S, H * D, device=dev).to(torch.bfloat16)
     step = torch.tensor([3], device=dev, dtype=torch.int64)
@@ -54,15 +72,36 @@ def main():
         flop_f = 4 * H * D * int((lc * lc).sum())
         print(f"lens uniform in [{args.min_len}, {S}]: mean {lc.float().mean():.1f}, valid rows {int(lc.sum())} of {B * S}")
     it = args.iters
-    print("| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |")
-    print("|---:|---:|---:|---:|---:|---:|---:|")
+    print(f"B {B}, S {S}, H {H}, D {D}; {nwin} window(s) of {it} calls")
+    head = "| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |"
+    if args.sdpa:
+        from parameter_server_distributed_amd.ops.attention import FusedSelfAttention
+
+        mod = FusedSelfAttention(H).to(dev)
+        xg = qkv.clone().requires_grad_(True)
+        head += " sdpa fwd us | sdpa bwd us | fwd+bwd us | sdpa fwd+bwd us |"
+    print(head)
+    print("|" + "---:|" * (head.count("|") - 1))
     for p in (0.0, 0.1):
         o, lse = C.attn_fwd(qkv, H, p, 7, step, lens)
-        tf = t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens), it)
-        tb = t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens), it)
+        tf, tb, sf, sb = [], [], [], []
+        for _ in range(nwin):  # the paths alternate inside a window
+            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens), it))
+            if args.sdpa:
+                sf.append(t_us(lambda: mod._sdpa(xg, lens, p), it))
+            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens), it))
+            if args.sdpa:
+                so = mod._sdpa(xg, lens, p)
+                sb.append(t_us(lambda: torch.autograd.grad(so, xg, do, retain_graph=True), it))
+                del so
+        mf, mb = statistics.median(tf), statistics.median(tb)
         # fwd: read q, k, v; write o (+ lse). bwd: read q, k, v, o, dO; write dq, dk, dv
-        print(f"| {p} | {tf:.1f} | {4 * el / tf / 1e6:.2f} | {flop_f / tf / 1e6:.0f} | {tb:.1f} | "
-              f"{8 * el / tb / 1e6:.2f} | {2.5 * flop_f / tb / 1e6:.0f} |", flush=True)
+        row = (f"| {p} | {_fmt(tf)} | {4 * el / mf / 1e6:.2f} | {flop_f / mf / 1e6:.0f} | {_fmt(tb)} | "
+               f"{8 * el / mb / 1e6:.2f} | {2.5 * flop_f / mb / 1e6:.0f} |")
+        if args.sdpa:
+            row += (f" {_fmt(sf)} | {_fmt(sb)} | {_fmt([a + b for a, b in zip(tf, tb)])} | "
+                    f"{_fmt([a + b for a, b in zip(sf, sb)])} |")
+        print(row, flush=True)
 
 
 if __name__ == "__main__":
