@@ -13,7 +13,7 @@ import time
 from ..runtime.worker import Worker
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="worker_main")
     ap.add_argument("coordinator", nargs="?", default="localhost:50052")
     ap.add_argument("worker_id", nargs="?", type=int, default=0)
@@ -41,6 +41,9 @@ def main(argv=None):
                     help="elastic: no weight decay (and no trust ratio) on tensors of ndim <= 1; default: on for "
                          "lars / lamb (async plane only)")
     ap.add_argument("--lr", type=float, default=0.05)
+    ap.add_argument("--clip-grad-norm", type=float, default=0.0,
+                    help="clip each push's global gradient L2 norm at this value (0: off). gRPC workers clip "
+                         "before serialising; elastic: the async plane only (--ps-plane async)")
     ap.add_argument("--bucket-mb", type=float, default=16.0)
     ap.add_argument("--pull-dtype", default="bf16")
     ap.add_argument("--check-every", type=int, default=5, help="elastic: membership check period (steps)")
@@ -57,6 +60,11 @@ def main(argv=None):
                     help="fp8 (e4m3 MFMA) forward / e5m2 bwd-data of the ResNet bottleneck convolutions "
                          "(BASELINE config 5: Wide-ResNet-101-2 fp8)")
     ap.add_argument("--image-size", type=int, default=224, help="ResNet models: synthetic image size")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     from ..utils.config import apply_config
 
     apply_config(ap, argv)
@@ -65,7 +73,7 @@ def main(argv=None):
         return elastic_main(a)
     w = Worker(a.coordinator, a.worker_id, a.worker_addr, a.worker_port, model=a.model, batch=a.batch,
                device=a.device, heartbeat_s=a.heartbeat_s, bf16_wire=a.bf16_wire, mode=a.mode,
-               raw_wire=not a.reference_wire)
+               raw_wire=not a.reference_wire, clip_norm=a.clip_grad_norm)
     w.initialize()
 
     def _leave(signum, frame):  # scale_workers.sh down: deregister so the barrier shrinks at once
@@ -131,7 +139,8 @@ def elastic_main(a) -> int:
     dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
     spec = build_model(a, dev, dtype)
     batch = spec.make_batch(a.batch, dev, seed=1000 + a.worker_id)
-    optim = OptimConfig(a.optimizer, lr=a.lr, momentum=0.9, trust_coef=a.trust_coef, exclude_1d=a.exclude_1d)
+    optim = OptimConfig(a.optimizer, lr=a.lr, momentum=0.9, trust_coef=a.trust_coef, exclude_1d=a.exclude_1d,
+                        clip_norm=a.clip_grad_norm)
     agent = ElasticAgent(a.coordinator, a.worker_id, heartbeat_s=min(a.heartbeat_s, 1.0))
 
     def make_ps(model, transport):

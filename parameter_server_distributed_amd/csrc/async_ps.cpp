@@ -26,6 +26,7 @@ constexpr uint64_t kMagic = 0x5053444153594e43ull;  // "PSDASYNC"
 constexpr int kMaxShards = 64, kMaxWorkers = 64, kRing = 16, kMaxBuf = 8, kBins = 64, kMaxRanks = 128;
 constexpr int64_t kHbLeft = -1;  // heartbeat slot of a rank whose engine stopped on purpose
 constexpr int64_t kAlignBytes = 256;
+constexpr int64_t kScalarBytes = 256;  // one push's scalar block (element 0: its clipping coefficient)
 
 struct Msg {
   int64_t step;
@@ -134,7 +135,8 @@ bool psd_feature_on(const char* name, bool dflt) {
 
 AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers,
                          std::vector<int64_t> shard_off, std::vector<int64_t> shard_len, int staleness, int nbuf,
-                         std::string shm_name, bool create, int device, double timeout_s, int elem_bytes, bool mx)
+                         std::string shm_name, bool create, int device, double timeout_s, int elem_bytes, bool mx,
+                         bool clip)
     : rank_(rank),
       world_(world),
       S_(staleness),
@@ -143,6 +145,7 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
       timeout_s_(timeout_s),
       esz_(elem_bytes),
       mx_(mx),
+      clip_(clip),
       owners_(std::move(owners)),
       workers_(std::move(workers)),
       shard_off_(std::move(shard_off)),
@@ -235,6 +238,10 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
     for (int wi = 0; wi < W; ++wi)
       for (int s = 0; s <= S_; ++s) st.inbox.push_back(at::from_blob(inbox_ptr(k, wi, s), {shard_len_[k]}, opt));
     for (int b = 0; b < nbuf_; ++b) st.publish.push_back(at::from_blob(publish_ptr(k, b), {shard_len_[k]}, opt));
+    if (clip_)
+      for (int wi = 0; wi < W; ++wi)
+        for (int s = 0; s <= S_; ++s)
+          st.scal.push_back(at::from_blob(scalar_ptr(k, wi, s), {kScalarBytes / 4}, opt.dtype(at::kFloat)));
     st.busy.assign(nbuf_, false);
   }
   if (device_ >= 0) {
@@ -304,6 +311,8 @@ int AsyncEngine::worker_index(int rank) const {
 
 // A shard's region: W * (S + 1) inbox slots, then nbuf publish slots; with MX a publish slot also
 // holds the e4m3 copy of the snapshot and its E8M0 scales (one per 32 elements) after the bf16 one.
+// A clip engine appends W * (S + 1) scalar slots of 256 bytes (one per inbox slot); without clip the
+// layout is exactly the one above.
 int64_t AsyncEngine::pub_slot_bytes(int shard) const {
   const int64_t sb = round_up(shard_len_[shard] * esz_, kAlignBytes);
   if (!mx_) return sb;
@@ -312,7 +321,7 @@ int64_t AsyncEngine::pub_slot_bytes(int shard) const {
 
 int64_t AsyncEngine::shard_region_bytes(int shard) const {
   return (int64_t)workers_.size() * (S_ + 1) * round_up(shard_len_[shard] * esz_, kAlignBytes) +
-         nbuf_ * pub_slot_bytes(shard);
+         nbuf_ * pub_slot_bytes(shard) + (clip_ ? (int64_t)workers_.size() * (S_ + 1) * kScalarBytes : 0);
 }
 
 int64_t AsyncEngine::region_bytes_for(int rank) const {
@@ -341,6 +350,11 @@ char* AsyncEngine::publish_ptr(int shard, int buf) const {
   TORCH_CHECK(peer_base_[o], "psd async: rank ", o, " memory not attached");
   const int64_t sb = round_up(shard_len_[shard] * esz_, kAlignBytes);
   return peer_base_[o] + shard_base(o, shard) + (int64_t)workers_.size() * (S_ + 1) * sb + buf * pub_slot_bytes(shard);
+}
+
+char* AsyncEngine::scalar_ptr(int shard, int wi, int slot) const {
+  TORCH_CHECK(clip_, "psd async: scalar slots exist on clip engines only");
+  return publish_ptr(shard, 0) + nbuf_ * pub_slot_bytes(shard) + ((int64_t)wi * (S_ + 1) + slot) * kScalarBytes;
 }
 
 char* AsyncEngine::publish_q_ptr(int shard, int buf) const {
@@ -608,10 +622,11 @@ bool AsyncEngine::poll_once() {
       // arrival order (bitwise-reproducible rounds at SSP bound 0)
       std::sort(st.round.begin(), st.round.end(),
                 [](const RoundItem& x, const RoundItem& y) { return x.wi != y.wi ? x.wi < y.wi : x.step < y.step; });
-      std::vector<at::Tensor> g;
+      std::vector<at::Tensor> g, sc;
       for (RoundItem& it : st.round) {
         it.staleness = st.enq - it.pulled;
         g.push_back(st.inbox[(size_t)it.wi * (S_ + 1) + it.slot]);
+        if (clip_) sc.push_back(st.scal[(size_t)it.wi * (S_ + 1) + it.slot]);
       }
       st.enq += 1;
       st.busy[buf] = true;
@@ -619,12 +634,12 @@ bool AsyncEngine::poll_once() {
       if (device_ >= 0) {
         c10::hip::HIPStreamGuard sg(c10::hip::getStreamFromExternal(static_cast<hipStream_t>(ps_stream_),
                                                                     (c10::DeviceIndex)device_));
-        apply_into(st, g, buf);
+        apply_into(st, g, sc, buf);
         if (mx_) quant_publish(st, k, buf, ps_stream_);
         hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
         hip_ok(hipEventRecord(ev, static_cast<hipStream_t>(ps_stream_)), "hipEventRecord");
       } else {
-        apply_into(st, g, buf);
+        apply_into(st, g, sc, buf);
       }
       pending_.push_back(Pending{k, buf, std::move(st.round), ev});
       st.round.clear();
@@ -635,13 +650,16 @@ bool AsyncEngine::poll_once() {
 
 // One update: optimizer step counter, fused apply of the round's inbox slots (summed in registers,
 // scaled by the dyn grad_scale = 1/K) onto the fp32 master, and the new snapshot written into
-// publish buffer `buf` (bf16: by the apply kernel itself).
-void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in, int buf) {
+// publish buffer `buf` (bf16: by the apply kernel itself). On a clip engine each source is multiplied
+// by the coefficient in its scalar block inside the same kernels (`sc_in`, one block per source).
+void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in, const std::vector<at::Tensor>& sc_in,
+                             int buf) {
   // a round of more than 16 pushes (the fused apply kernel's source limit): each group of 16
   // inbox slots (worker order) is summed into an fp32 workspace and the apply takes the group sums
   // (fixed order, so rounds stay bitwise reproducible). With K = W every round completes -- a
   // partial round stranded at W > 16 would hold a worker's clock back forever.
   std::vector<at::Tensor> g = g_in;
+  ScaleList sc(sc_in.begin(), sc_in.end());
   if (g.size() > (size_t)kMaxSources) {
     const size_t ng = (g.size() + kMaxSources - 1) / kMaxSources;
     TORCH_CHECK(ng <= (size_t)kMaxSources, "psd async: at most 256 pushes per round");
@@ -649,10 +667,13 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
     std::vector<at::Tensor> sums;
     for (size_t gi = 0; gi < ng; ++gi) {
       const size_t b = gi * kMaxSources, e = std::min(g.size(), b + kMaxSources);
-      multi_reduce_(st.acc[gi], std::vector<at::Tensor>(g.begin() + b, g.begin() + e), 1.0);
+      // the clipping coefficients go into the group sums; the apply then takes them unscaled
+      multi_reduce_(st.acc[gi], std::vector<at::Tensor>(g.begin() + b, g.begin() + e), 1.0,
+                    sc.empty() ? ScaleList{} : ScaleList(sc.begin() + b, sc.begin() + e));
       sums.push_back(st.acc[gi]);
     }
     g = std::move(sums);
+    sc.clear();
   }
   optim_advance_(st.dyn, st.hyper.beta1, st.hyper.beta2);
   const bool bf16 = esz_ == 2;
@@ -661,7 +682,7 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
                     st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
                     bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,
                     st.hyper.momentum, st.hyper.dampening, st.hyper.nesterov, st.hyper.weight_decay, st.hyper.beta1,
-                    st.hyper.beta2, st.hyper.eps, false, st.trust_coef, st.layers, apply_cap_);
+                    st.hyper.beta2, st.hyper.eps, false, st.trust_coef, st.layers, apply_cap_, sc);
     if (!bf16) st.publish[buf].copy_(st.master);
     return;
   }
@@ -669,7 +690,7 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
                st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
                bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,
                st.hyper.momentum, st.hyper.dampening, st.hyper.nesterov, st.hyper.weight_decay, st.hyper.beta1,
-               st.hyper.beta2, st.hyper.eps, false, apply_cap_);
+               st.hyper.beta2, st.hyper.eps, false, apply_cap_, sc);
   if (!bf16) st.publish[buf].copy_(st.master);
 }
 
@@ -954,6 +975,33 @@ void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, i
   }
 }
 
+void AsyncEngine::push_scalars(int64_t step, const at::Tensor& block, int64_t stream) {
+  TORCH_CHECK(clip_, "psd async: push_scalars on an engine without clip");
+  TORCH_CHECK(my_wi_ >= 0, "psd async: rank ", rank_, " is not a worker");
+  TORCH_CHECK(block.is_contiguous() && (int64_t)block.nbytes() == kScalarBytes &&
+                  block.is_cuda() == (device_ >= 0),
+              "psd async: the scalar block is ", kScalarBytes, " contiguous bytes on the engine's device");
+  check_error();
+  const char* src = static_cast<const char*>(block.data_ptr());
+  const int slot = (int)(step % (S_ + 1));
+  const int P = (int)owners_.size();
+  void* sp = reinterpret_cast<void*>(stream);
+  const bool kernel = device_ >= 0 && xfer_kernel_;
+  // remote owners: one scatter launch, one 256-byte segment per remote shard (kernels/xfer.hip)
+  XferList L{};
+  for (int k = 0; k < P; ++k) {
+    char* dst = scalar_ptr(k, my_wi_, slot);
+    if (kernel && owners_[k] != rank_ && aligned16(src, dst)) L.seg[L.count++] = XferSeg{src, dst, kScalarBytes};
+    else copy(dst, src, kScalarBytes, sp);
+  }
+  if (L.count > 0) {
+    L.blocks_per_seg = 1;
+    L.nt_store = 1;
+    const c10::DeviceGuard g(c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)device_));
+    hip_ok(launch_xfer(L, static_cast<hipStream_t>(sp)), "launch_xfer(push_scalars)");
+  }
+}
+
 void AsyncEngine::commit(int64_t step, std::vector<int64_t> pulled, int64_t stream) {
   TORCH_CHECK(my_wi_ >= 0, "psd async: rank ", rank_, " is not a worker");
   TORCH_CHECK(pulled.size() == owners_.size(), "psd async: one pulled version per shard");
@@ -997,6 +1045,13 @@ at::Tensor AsyncEngine::inbox_view(int shard, int wi, int slot) const {
   TORCH_CHECK(shard >= 0 && shard < (int)owners_.size() && owners_[shard] == rank_, "psd async: not my shard");
   TORCH_CHECK(wi >= 0 && wi < (int)workers_.size() && slot >= 0 && slot <= S_, "psd async: bad inbox index");
   return shards_[shard].inbox[(size_t)wi * (S_ + 1) + slot];
+}
+
+at::Tensor AsyncEngine::scalar_view(int shard, int wi, int slot) const {
+  TORCH_CHECK(clip_, "psd async: scalar slots exist on clip engines only");
+  TORCH_CHECK(shard >= 0 && shard < (int)owners_.size() && owners_[shard] == rank_, "psd async: not my shard");
+  TORCH_CHECK(wi >= 0 && wi < (int)workers_.size() && slot >= 0 && slot <= S_, "psd async: bad scalar slot index");
+  return shards_[shard].scal[(size_t)wi * (S_ + 1) + slot];
 }
 
 // ------------------------------------------------------------------ introspection

@@ -55,7 +55,7 @@ class AsyncEngine {
  public:
   AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers, std::vector<int64_t> shard_off,
               std::vector<int64_t> shard_len, int staleness, int nbuf, std::string shm_name, bool create, int device,
-              double timeout_s, int elem_bytes = 2, bool mx = false);
+              double timeout_s, int elem_bytes = 2, bool mx = false, bool clip = false);
   ~AsyncEngine();
 
   // -- memory exchange (collective through the caller's store) --
@@ -100,12 +100,17 @@ class AsyncEngine {
   void set_xfer_blocks(int cap);
   int xfer_blocks_cap() const { return xfer_cap_; }
   void push(int64_t step, const at::Tensor& grads_flat, int64_t lo, int64_t hi, int64_t stream);
+  // clip engines: this worker's 256-byte scalar block of `step` (element 0: its clipping coefficient,
+  // kernels/launchers_clip.h) into its scalar slot at every shard, by the push transport; on the
+  // stream that commits, before commit(), so the scalars land behind the same event as the buckets
+  void push_scalars(int64_t step, const at::Tensor& block, int64_t stream);
   void commit(int64_t step, std::vector<int64_t> pulled, int64_t stream);
   void wait_applied(int64_t nsteps);  // this worker's pushes 0..nsteps-1 applied at every shard
   void wait_all_applied(int64_t nsteps);  // every worker's pushes 0..nsteps-1 applied at every shard
 
   // this rank's inbox slot of worker index wi at shard (owner side; start-up self-test)
   at::Tensor inbox_view(int shard, int wi, int slot) const;
+  at::Tensor scalar_view(int shard, int wi, int slot) const;  // its scalar block (64 fp32; clip engines)
 
   // -- introspection --
   std::vector<int64_t> histogram() const;  // staleness of the applies this process performed
@@ -142,6 +147,7 @@ class AsyncEngine {
     std::vector<at::Tensor> layers;   // layer table (set_shard_layers); empty: the flat apply
     double trust_coef = 0.001;
     std::vector<at::Tensor> inbox;    // [workers * (S+1)] bf16 views
+    std::vector<at::Tensor> scal;     // [workers * (S+1)] fp32 [64] views of the scalar slots (clip engines)
     std::vector<at::Tensor> publish;  // [nbuf] bf16 views
     std::vector<bool> busy;           // publish buffer is the target of an enqueued apply
     int64_t enq = 0;                  // applies enqueued (the version the next apply starts from)
@@ -160,7 +166,9 @@ class AsyncEngine {
   int64_t shard_base(int rank, int shard) const;  // byte offset of shard's region in rank's allocation
   char* inbox_ptr(int shard, int wi, int slot) const;
   char* publish_ptr(int shard, int buf) const;
-  void apply_into(ShardState& st, const std::vector<at::Tensor>& g, int buf);
+  char* scalar_ptr(int shard, int wi, int slot) const;
+  // sc: the sources' scalar blocks (clip engines), empty otherwise
+  void apply_into(ShardState& st, const std::vector<at::Tensor>& g, const std::vector<at::Tensor>& sc, int buf);
   int free_buf(int shard) const;
   bool claim_buf(int shard, int b);
   static bool done(void* event);
@@ -184,6 +192,7 @@ class AsyncEngine {
   double dead_after_s_ = 10.0;  // a peer's engine silent this long is presumed dead (PSD_ASYNC_DEAD_S)
   int esz_;
   bool mx_ = false;  // MX fp8 publish: each publish slot also holds e4m3 + E8M0 scales of the snapshot
+  bool clip_ = false;  // per-push clipping scalars: W * (S + 1) scalar slots after each shard's publish slots
   std::vector<int> owners_, workers_, my_shards_;
   std::vector<int64_t> shard_off_, shard_len_;
   int my_wi_ = -1;

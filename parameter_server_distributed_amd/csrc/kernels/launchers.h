@@ -57,11 +57,23 @@ static_assert(sizeof(OptimDyn) == 32, "OptimDyn layout is shared with Python (8 
 constexpr int kMaxSources = 16;
 
 // Sum of up to kMaxSources gradient inboxes (same dtype), optionally fused with the optimizer.
+// `scale`: one device float per source (the push's gradient-clipping coefficient), either set for
+// every source or null for every source. With scales the consumers compute
+// grad_scale * sum_k scale_k * src_k (one fma per source element, in source order) in separate
+// kernel instantiations; a scale of exactly 1 reproduces the unscaled bits.
 struct SourceList {
   const void* ptr[kMaxSources];
+  const float* scale[kMaxSources];
   int32_t count;
   int32_t dtype;  // DType of every source
 };
+
+// 0: no scales, 1: every source has one, -1: a mix (refused by every launcher)
+inline int source_scale_mode(const SourceList& s) {
+  int set = 0;
+  for (int k = 0; k < s.count; ++k) set += s.scale[k] != nullptr;
+  return set == 0 ? 0 : (set == s.count ? 1 : -1);
+}
 
 // master[i] (fp32) <- optimizer(master[i], grad = grad_scale * sum_k src_k[i], state1/2)
 // shadow (bf16, optional) <- bf16(master[i]) in the same pass (the all-gather payload).

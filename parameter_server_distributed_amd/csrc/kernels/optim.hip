@@ -12,25 +12,30 @@
 // (cdna_hip_programming.md G11/G13): 256-thread blocks (4 waves), 8 elements per lane per
 // iteration via 16-byte vector loads, grid-stride loop with <= 2048 blocks. No LDS: there is no
 // reuse to stage (T14 is null on streaming ops at high occupancy).
+//
+// Per-source scales (SourceList::scale, the per-push gradient-clipping coefficients): a separate
+// instantiation (SCALED) that multiplies each source by its device scalar inside the same pass,
+// acc = fmaf(c_k, g_k, acc); its only LDS is the K staged scalars. The unscaled instantiation is the
+// kernel as it was.
 #include "common.h"
 #include "launchers.h"
 #include "optim_update.h"
 
 namespace psd {
 
-template <int SRC_DT>
-__device__ __forceinline__ float load_source1(const SourceList& g, int64_t i, float scale) {
+template <int SRC_DT, bool SCALED = false>
+__device__ __forceinline__ float load_source1(const SourceList& g, int64_t i, float scale, const float* sc = nullptr) {
   float acc = 0.f;
   for (int k = 0; k < g.count; ++k) {
-    if (SRC_DT == DT_BF16)
-      acc += bf16_to_f32(static_cast<const uint16_t*>(g.ptr[k])[i]);
-    else
-      acc += static_cast<const float*>(g.ptr[k])[i];
+    const float x = (SRC_DT == DT_BF16) ? bf16_to_f32(static_cast<const uint16_t*>(g.ptr[k])[i])
+                                        : static_cast<const float*>(g.ptr[k])[i];
+    if (SCALED) acc = fmaf(sc[k], x, acc);
+    else acc += x;
   }
   return acc * scale;
 }
 
-template <int KIND, int SRC_DT>
+template <int KIND, int SRC_DT, bool SCALED = false>
 __global__ __launch_bounds__(256) void fused_apply_kernel(OptimHyper h, const OptimDyn* __restrict__ dyn,
                                                           float* __restrict__ master, SourceList g,
                                                           float* __restrict__ s1, float* __restrict__ s2,
@@ -42,13 +47,14 @@ __global__ __launch_bounds__(256) void fused_apply_kernel(OptimHyper h, const Op
   const bool first = dyn->step <= 1;
   const bool has_state = (KIND != OPT_SGD);
   const bool two_state = (KIND == OPT_ADAM || KIND == OPT_ADAMW);
+  const float* sc = stage_scales<SCALED>(g);
 
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
     const int64_t i = v << 3;
     float gr[8], p[8], a[8], b[8];
-    load_sources8<SRC_DT>(g, i, gs, gr);
+    load_sources8<SRC_DT, SCALED>(g, i, gs, gr, sc);
     load8_f32(master + i, p);
     if (has_state) load8_f32(s1 + i, a);
     if (two_state) load8_f32(s2 + i, b);
@@ -62,7 +68,7 @@ __global__ __launch_bounds__(256) void fused_apply_kernel(OptimHyper h, const Op
   // Tail (n % 8 elements): first block only.
   if (blockIdx.x == 0) {
     for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
-      float gr = load_source1<SRC_DT>(g, i, gs);
+      float gr = load_source1<SRC_DT, SCALED>(g, i, gs, sc);
       float p = master[i];
       float a = has_state ? s1[i] : 0.f;
       float b = two_state ? s2[i] : 0.f;
@@ -88,18 +94,24 @@ static void dispatch_src(const OptimHyper& h, const OptimDyn* dyn, float* master
   const int block = 256;
   int grid = stream_grid((n >> 3) > 0 ? (n >> 3) : 1, block);
   if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-  if (g.dtype == DT_BF16)
-    hipLaunchKernelGGL((fused_apply_kernel<KIND, DT_BF16>), dim3(grid), dim3(block), 0, st, h, dyn, master, g,
-                       s1, s2, shadow, n);
-  else
-    hipLaunchKernelGGL((fused_apply_kernel<KIND, DT_F32>), dim3(grid), dim3(block), 0, st, h, dyn, master, g,
-                       s1, s2, shadow, n);
+  const bool scaled = source_scale_mode(g) == 1;
+#define PSD_APPLY(DT, SC)                                                                                          \
+  hipLaunchKernelGGL((fused_apply_kernel<KIND, DT, SC>), dim3(grid), dim3(block), 0, st, h, dyn, master, g, s1, s2, \
+                     shadow, n)
+  if (g.dtype == DT_BF16) {
+    if (scaled) PSD_APPLY(DT_BF16, true);
+    else PSD_APPLY(DT_BF16, false);
+  } else {
+    if (scaled) PSD_APPLY(DT_F32, true);
+    else PSD_APPLY(DT_F32, false);
+  }
+#undef PSD_APPLY
 }
 
 hipError_t launch_fused_apply(const OptimHyper& h, const OptimDyn* dyn, float* master, const SourceList& g,
                               float* s1, float* s2, uint16_t* shadow, int64_t n, hipStream_t st, int grid_cap) {
   if (n <= 0) return hipSuccess;
-  if (g.count < 1 || g.count > kMaxSources) return hipErrorInvalidValue;
+  if (g.count < 1 || g.count > kMaxSources || source_scale_mode(g) < 0) return hipErrorInvalidValue;
   switch (h.kind) {
     case OPT_SGD: dispatch_src<OPT_SGD>(h, dyn, master, g, s1, s2, shadow, n, st, grid_cap); break;
     case OPT_MOMENTUM: dispatch_src<OPT_MOMENTUM>(h, dyn, master, g, s1, s2, shadow, n, st, grid_cap); break;

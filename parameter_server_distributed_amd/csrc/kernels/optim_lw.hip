@@ -19,11 +19,13 @@
 // opt_update (optim_update.h) and weight_decay * wd_mult[t].
 //
 // Regime and rules as optim.hip: HBM streaming, 256-thread blocks, 16-byte vector accesses, no LDS
-// staging of data (the only LDS is the 8-float exchange of the block reduction). A workgroup owns a
-// whole chunk (4 vectors of 8 per lane) and walks the chunk table with a grid-stride loop, and
+// staging of data (the only LDS is the 8-float exchange of the block reduction, and in the SCALED
+// instantiations the K per-source clipping scalars; both LARS reads of the sources are scaled). A
+// workgroup owns a whole chunk (4 vectors of 8 per lane) and walks the chunk table with a grid-stride loop, and
 // every sum has a fixed order (lane-sequential, xor butterfly, waves 0..3, chunks in lane order),
 // so the result does not depend on the grid, on grid_cap, or on where the buffer is cut into shards
 // as long as the cuts are tensor starts.
+#include "block_sum.h"
 #include "common.h"
 #include "launchers_optim_lw.h"
 #include "optim_update.h"
@@ -47,31 +49,6 @@ __device__ __forceinline__ LwChunk lw_chunk(const LwTable& t, int c) {
   return k;
 }
 
-// xor butterfly over the 64 lanes: every lane ends with the same sum, in an order that depends on
-// nothing but the lane ids
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kWave);
-  return x;
-}
-
-// (a, b) summed over the 256 threads of the block -> partials[2c], partials[2c + 1]
-__device__ __forceinline__ void block_sum2_store(float a, float b, float* red, float* out) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    red[wave] = a;
-    red[4 + wave] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    out[0] = ((red[0] + red[1]) + red[2]) + red[3];
-    out[1] = ((red[4] + red[5]) + red[6]) + red[7];
-  }
-  __syncthreads();  // red is reused by the block's next chunk
-}
-
 // LAMB update direction; stage 1 (norms) and stage 2 (apply) must agree bit for bit, so every
 // operation is spelled out (nothing left for the compiler to contract one way here and another there)
 __device__ __forceinline__ float lamb_u(float m, float v, float w, float bc1, float bc2_sqrt, float eps, float wd) {
@@ -81,11 +58,12 @@ __device__ __forceinline__ float lamb_u(float m, float v, float w, float bc1, fl
 
 }  // namespace
 
-template <int SRC_DT, bool LAMB>
+template <int SRC_DT, bool LAMB, bool SCALED = false>
 __global__ __launch_bounds__(256) void lw_norm_kernel(OptimHyper h, const OptimDyn* __restrict__ dyn,
                                                       const float* __restrict__ master, SourceList g,
                                                       float* __restrict__ s1, float* __restrict__ s2, LwTable t) {
   __shared__ float red[8];
+  const float* sc = stage_scales<SCALED>(g);
   const float gs = dyn->grad_scale;
   const float bc1 = dyn->bc1;
   const float bc2s = sqrtf(dyn->bc2);
@@ -96,7 +74,7 @@ __global__ __launch_bounds__(256) void lw_norm_kernel(OptimHyper h, const OptimD
     for (int v = threadIdx.x; v < ck.nvec; v += 256) {
       const int64_t i = ck.off + ((int64_t)v << 3);
       float gr[8], p[8];
-      load_sources8<SRC_DT>(g, i, gs, gr);
+      load_sources8<SRC_DT, SCALED>(g, i, gs, gr, sc);
       load8_f32(master + i, p);
       if (LAMB) {
         float a[8], b[8];
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(64) void lw_finalize_kernel(OptimHyper h, LwTable t
   }
 }
 
-template <int KIND, int SRC_DT>
+template <int KIND, int SRC_DT, bool SCALED = false>
 __global__ __launch_bounds__(256) void lw_apply_kernel(OptimHyper h, const OptimDyn* __restrict__ dyn,
                                                        float* __restrict__ master, SourceList g,
                                                        float* __restrict__ s1, float* __restrict__ s2,
@@ -166,6 +144,7 @@ __global__ __launch_bounds__(256) void lw_apply_kernel(OptimHyper h, const Optim
   const bool has_state = (KIND != OPT_SGD);
   const bool two_state = (KIND == OPT_ADAM || KIND == OPT_ADAMW || KIND == OPT_LAMB);
   const bool layerwise = (KIND == OPT_LARS || KIND == OPT_LAMB);
+  const float* sc = stage_scales<(SCALED && KIND != OPT_LAMB)>(g);
 
   for (int c = blockIdx.x; c < t.n_chunks; c += gridDim.x) {
     const LwChunk ck = lw_chunk(t, c);
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(256) void lw_apply_kernel(OptimHyper h, const Optim
     for (int v = threadIdx.x; v < ck.nvec; v += 256) {
       const int64_t i = ck.off + ((int64_t)v << 3);
       float gr[8], p[8], a[8], b[8];
-      if (KIND != OPT_LAMB) load_sources8<SRC_DT>(g, i, gs, gr);
+      if (KIND != OPT_LAMB) load_sources8<SRC_DT, SCALED>(g, i, gs, gr, sc);
       load8_f32(master + i, p);
       if (has_state) load8_f32(s1 + i, a);
       if (two_state) load8_f32(s2 + i, b);
@@ -219,12 +198,18 @@ inline bool lw_table_ok(const LwTable& t) {
 template <int KIND>
 void lw_apply_src(const OptimHyper& h, const OptimDyn* dyn, float* master, const SourceList& g, float* s1, float* s2,
                   uint16_t* shadow, const LwTable& t, hipStream_t st, int grid) {
-  if (g.dtype == DT_BF16)
-    hipLaunchKernelGGL((lw_apply_kernel<KIND, DT_BF16>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2,
-                       shadow, t);
-  else
-    hipLaunchKernelGGL((lw_apply_kernel<KIND, DT_F32>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2,
-                       shadow, t);
+  // LAMB stage 2 reads no gradient: one instantiation, scales or not
+  const bool scaled = KIND != OPT_LAMB && source_scale_mode(g) == 1;
+#define PSD_LW_APPLY(DT, SC)                                                                                        \
+  hipLaunchKernelGGL((lw_apply_kernel<KIND, DT, SC>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, shadow, t)
+  if (g.dtype == DT_BF16) {
+    if (scaled) PSD_LW_APPLY(DT_BF16, true);
+    else PSD_LW_APPLY(DT_BF16, false);
+  } else {
+    if (scaled) PSD_LW_APPLY(DT_F32, true);
+    else PSD_LW_APPLY(DT_F32, false);
+  }
+#undef PSD_LW_APPLY
 }
 
 }  // namespace
@@ -233,22 +218,28 @@ hipError_t launch_lw_norms(const OptimHyper& h, const OptimDyn* dyn, const float
                            float* s1, float* s2, const LwTable& t, hipStream_t st, int grid_cap) {
   if (!lw_table_ok(t) || g.count < 1 || g.count > kMaxSources) return hipErrorInvalidValue;
   if (g.dtype != DT_BF16 && g.dtype != DT_F32) return hipErrorInvalidValue;
+  const int mode = source_scale_mode(g);
+  if (mode < 0) return hipErrorInvalidValue;
   const int grid = lw_grid(t.n_chunks, grid_cap);
   const bool bf = g.dtype == DT_BF16;
+#define PSD_LW_NORM(DT, LAMB)                                                                                          \
+  do {                                                                                                                 \
+    if (mode == 1)                                                                                                     \
+      hipLaunchKernelGGL((lw_norm_kernel<DT, LAMB, true>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t); \
+    else                                                                                                               \
+      hipLaunchKernelGGL((lw_norm_kernel<DT, LAMB, false>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t); \
+  } while (0)
   if (h.kind == OPT_LARS) {
-    if (bf)
-      hipLaunchKernelGGL((lw_norm_kernel<DT_BF16, false>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t);
-    else
-      hipLaunchKernelGGL((lw_norm_kernel<DT_F32, false>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t);
+    if (bf) PSD_LW_NORM(DT_BF16, false);
+    else PSD_LW_NORM(DT_F32, false);
   } else if (h.kind == OPT_LAMB) {
     if (!s1 || !s2) return hipErrorInvalidValue;
-    if (bf)
-      hipLaunchKernelGGL((lw_norm_kernel<DT_BF16, true>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t);
-    else
-      hipLaunchKernelGGL((lw_norm_kernel<DT_F32, true>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t);
+    if (bf) PSD_LW_NORM(DT_BF16, true);
+    else PSD_LW_NORM(DT_F32, true);
   } else {
     return hipErrorInvalidValue;
   }
+#undef PSD_LW_NORM
   return hipGetLastError();
 }
 
@@ -269,6 +260,7 @@ hipError_t launch_lw_apply(const OptimHyper& h, const OptimDyn* dyn, float* mast
   if (!lw_table_ok(t)) return hipErrorInvalidValue;
   if (h.kind != OPT_LAMB && (g.count < 1 || g.count > kMaxSources)) return hipErrorInvalidValue;
   if (g.dtype != DT_BF16 && g.dtype != DT_F32) return hipErrorInvalidValue;
+  if (h.kind != OPT_LAMB && source_scale_mode(g) < 0) return hipErrorInvalidValue;
   const int grid = lw_grid(t.n_chunks, grid_cap);
   switch (h.kind) {
     case OPT_SGD: lw_apply_src<OPT_SGD>(h, dyn, master, g, s1, s2, shadow, t, st, grid); break;

@@ -35,8 +35,27 @@ __device__ __forceinline__ void opt_update(const OptimHyper& h, float lr, float 
   }
 }
 
-template <int SRC_DT>
-__device__ __forceinline__ void load_sources8(const SourceList& g, int64_t i, float scale, float out[8]) {
+// Per-source scales (SourceList::scale, the gradient-clipping coefficients of the pushes): thread 0
+// reads the K device scalars once into LDS and every lane takes them from there. The unscaled
+// instantiation declares no LDS and returns null.
+template <bool SCALED>
+__device__ __forceinline__ const float* stage_scales(const SourceList& g) {
+  if constexpr (SCALED) {
+    __shared__ float sc[kMaxSources];
+    if (threadIdx.x == 0)
+      for (int k = 0; k < g.count; ++k) sc[k] = *g.scale[k];
+    __syncthreads();
+    return sc;
+  } else {
+    return nullptr;
+  }
+}
+
+// out = scale * sum_k src_k[i..i+8), or with SCALED scale * sum_k sc[k] * src_k (one fma per source
+// element, in source order; sc[k] == 1 gives the unscaled bits)
+template <int SRC_DT, bool SCALED = false>
+__device__ __forceinline__ void load_sources8(const SourceList& g, int64_t i, float scale, float out[8],
+                                              const float* sc = nullptr) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) out[e] = 0.f;
   for (int k = 0; k < g.count; ++k) {
@@ -45,8 +64,14 @@ __device__ __forceinline__ void load_sources8(const SourceList& g, int64_t i, fl
       load8_bf16(static_cast<const uint16_t*>(g.ptr[k]) + i, t);
     else
       load8_f32(static_cast<const float*>(g.ptr[k]) + i, t);
+    if (SCALED) {
+      const float c = sc[k];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) out[e] += t[e];
+      for (int e = 0; e < 8; ++e) out[e] = fmaf(c, t[e], out[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) out[e] += t[e];
+    }
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) out[e] *= scale;

@@ -10,30 +10,22 @@
 // (src/worker.cpp:40-66, src/parameter_server_service.cpp:35-42,70-80) on the bulk-tensor path.
 #include "common.h"
 #include "launchers.h"
+#include "optim_update.h"
 
 namespace psd {
 
-template <int SRC_DT, int OUT_DT>
+// SCALED: out = scale * sum_k sc_k * src_k (SourceList::scale; the async plane's pre-reduce of a
+// clipped round of more than 16 pushes), one fma per source element in source order
+template <int SRC_DT, int OUT_DT, bool SCALED = false>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(SourceList s, void* __restrict__ out, float scale,
                                                            int64_t n) {
+  const float* sc = stage_scales<SCALED>(s);
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
     const int64_t i = v << 3;
     float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    for (int k = 0; k < s.count; ++k) {
-      float t[8];
-      if (SRC_DT == DT_BF16)
-        load8_bf16(static_cast<const uint16_t*>(s.ptr[k]) + i, t);
-      else
-        load8_f32(static_cast<const float*>(s.ptr[k]) + i, t);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += t[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] *= scale;
+    load_sources8<SRC_DT, SCALED>(s, i, scale, acc, sc);
     if (OUT_DT == DT_BF16)
       store8_bf16(static_cast<uint16_t*>(out) + i, acc);
     else
@@ -42,9 +34,12 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(SourceList s, void* _
   if (blockIdx.x == 0) {
     for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
       float acc = 0.f;
-      for (int k = 0; k < s.count; ++k)
-        acc += (SRC_DT == DT_BF16) ? bf16_to_f32(static_cast<const uint16_t*>(s.ptr[k])[i])
-                                   : static_cast<const float*>(s.ptr[k])[i];
+      for (int k = 0; k < s.count; ++k) {
+        const float x = (SRC_DT == DT_BF16) ? bf16_to_f32(static_cast<const uint16_t*>(s.ptr[k])[i])
+                                            : static_cast<const float*>(s.ptr[k])[i];
+        if (SCALED) acc = fmaf(sc[k], x, acc);
+        else acc += x;
+      }
       acc *= scale;
       if (OUT_DT == DT_BF16)
         static_cast<uint16_t*>(out)[i] = f32_to_bf16(acc);
@@ -58,10 +53,17 @@ hipError_t launch_multi_reduce(const SourceList& s, void* out, int32_t out_dtype
                                hipStream_t st) {
   if (n <= 0) return hipSuccess;
   if (s.count < 1 || s.count > kMaxSources) return hipErrorInvalidValue;
+  const int mode = source_scale_mode(s);
+  if (mode < 0) return hipErrorInvalidValue;
   const int block = 256;
   const int grid = stream_grid((n >> 3) > 0 ? (n >> 3) : 1, block);
-#define PSD_RED(SD, OD) \
-  hipLaunchKernelGGL((multi_reduce_kernel<SD, OD>), dim3(grid), dim3(block), 0, st, s, out, scale, n)
+#define PSD_RED(SD, OD)                                                                                          \
+  do {                                                                                                           \
+    if (mode == 1)                                                                                               \
+      hipLaunchKernelGGL((multi_reduce_kernel<SD, OD, true>), dim3(grid), dim3(block), 0, st, s, out, scale, n);  \
+    else                                                                                                         \
+      hipLaunchKernelGGL((multi_reduce_kernel<SD, OD, false>), dim3(grid), dim3(block), 0, st, s, out, scale, n); \
+  } while (0)
   if (s.dtype == DT_BF16 && out_dtype == DT_BF16) PSD_RED(DT_BF16, DT_BF16);
   else if (s.dtype == DT_BF16 && out_dtype == DT_F32) PSD_RED(DT_BF16, DT_F32);
   else if (s.dtype == DT_F32 && out_dtype == DT_BF16) PSD_RED(DT_F32, DT_BF16);

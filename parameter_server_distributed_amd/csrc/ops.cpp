@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "kernels/launchers.h"
+#include "kernels/launchers_clip.h"
 #include "kernels/launchers_optim_lw.h"
 #include "kernels/launchers_xfer.h"
 #include "optim_lw.h"
@@ -94,7 +95,8 @@ OptimDyn* dyn_ptr(const at::Tensor& dyn) {
   return reinterpret_cast<OptimDyn*>(dyn.data_ptr());
 }
 
-SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at::Device& dev) {
+SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at::Device& dev,
+                        const ScaleList& scales = {}) {
   TORCH_CHECK(!srcs.empty() && (int)srcs.size() <= kMaxSources, "psd: 1..16 gradient sources required");
   SourceList s{};
   s.count = (int32_t)srcs.size();
@@ -104,6 +106,19 @@ SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at
     TORCH_CHECK(dt_of(srcs[k]) == s.dtype, "psd: gradient sources must share a dtype");
     TORCH_CHECK(srcs[k].is_contiguous() && srcs[k].numel() == n, "psd: gradient source shape mismatch");
     s.ptr[k] = srcs[k].data_ptr();
+  }
+  // per-source scales: none, or one fp32 device scalar for every source
+  size_t set = 0;
+  for (auto& t : scales) set += t.has_value() && t->defined();
+  if (set == 0) return s;
+  TORCH_CHECK(scales.size() == srcs.size() && set == srcs.size(),
+              "psd: per-source scales must be given for every gradient source or for none (", set, " of ",
+              srcs.size(), " set)");
+  for (size_t k = 0; k < srcs.size(); ++k) {
+    const at::Tensor& t = *scales[k];
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.numel() >= 1 && t.is_contiguous() && t.device() == dev,
+                "psd: a source scale must be an fp32 tensor (element 0 is the scale) on the master's device");
+    s.scale[k] = t.data_ptr<float>();
   }
   return s;
 }
@@ -122,7 +137,7 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
                      const c10::optional<at::Tensor>& state1, const c10::optional<at::Tensor>& state2,
                      const c10::optional<at::Tensor>& shadow, const at::Tensor& dyn, int64_t kind, double momentum,
                      double dampening, bool nesterov, double weight_decay, double beta1, double beta2, double eps,
-                     bool maximize) {
+                     bool maximize, const ScaleList& scales) {
   TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous(), "psd: master must be contiguous fp32");
   ApplyArgs a;
   const int64_t n = a.n = master.numel();
@@ -155,7 +170,7 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
                 "psd: shadow must be contiguous bf16 like master");
     a.sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
   }
-  a.src = make_sources(grads, n, master.device());
+  a.src = make_sources(grads, n, master.device(), scales);
   TORCH_CHECK(dyn.device() == master.device(), "psd: dyn must live with master");
   if (master.is_cuda()) {
     check_aligned(master, "master");
@@ -167,11 +182,17 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
   return a;
 }
 
+// grad_scale * sum_k src_k[i], or with scales grad_scale * sum_k scale_k * src_k[i] (one fma per
+// source, in source order: optim_update.h load_sources8)
 inline float cpu_source(const SourceList& src, int64_t i, float gs) {
   float g = 0.f;
-  for (int k = 0; k < src.count; ++k)
-    g += src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
-                              : static_cast<const float*>(src.ptr[k])[i];
+  const bool scaled = src.scale[0] != nullptr;
+  for (int k = 0; k < src.count; ++k) {
+    const float x = src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
+                                         : static_cast<const float*>(src.ptr[k])[i];
+    if (scaled) g = std::fma(*src.scale[k], x, g);
+    else g += x;
+  }
   return g * gs;
 }
 
@@ -186,12 +207,12 @@ inline float cpu_lamb_u(float m, float v, float w, float bc1, float bc2s, float 
 void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
                   c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                   double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
-                  double eps, bool maximize, int64_t grid_cap) {
+                  double eps, bool maximize, int64_t grid_cap, const ScaleList& scales) {
   TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_ADAMW,
               "psd: fused_apply_ takes sgd / momentum / adam / adamw; lars and lamb need a layer table "
               "(fused_apply_lw_)");
   const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
-                                 weight_decay, beta1, beta2, eps, maximize);
+                                 weight_decay, beta1, beta2, eps, maximize, scales);
   const OptimHyper& h = a.h;
   const int64_t n = a.n;
   float *s1 = a.s1, *s2 = a.s2;
@@ -281,10 +302,10 @@ void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c1
                      c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                      double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
                      double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
-                     int64_t grid_cap) {
+                     int64_t grid_cap, const ScaleList& scales) {
   TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_LAMB, "psd: unknown optimizer kind ", kind);
   const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
-                                 weight_decay, beta1, beta2, eps, maximize);
+                                 weight_decay, beta1, beta2, eps, maximize, scales);
   // ---- the layer table (lw_table_build): shapes, dtypes, device, and the range it was built for
   TORCH_CHECK(layers.size() == 9, "psd: layer table must be the 9 tensors of lw_table_build");
   const at::Tensor& meta = layers[0];
@@ -423,10 +444,10 @@ void optim_advance_(at::Tensor dyn, double beta1, double beta2) {
   d->bc2 = 1.f - std::pow((float)beta2, (float)d->step);
 }
 
-void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale) {
+void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales) {
   TORCH_CHECK(out.is_contiguous(), "psd: out must be contiguous");
   const int64_t n = out.numel();
-  SourceList s = make_sources(srcs, n, out.device());
+  SourceList s = make_sources(srcs, n, out.device(), scales);
   const int32_t od = dt_of(out);
   TORCH_CHECK(od == DT_F32 || od == DT_BF16, "psd: reduce output must be fp32/bf16");
   if (out.is_cuda()) {
@@ -438,15 +459,85 @@ void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double s
   }
   at::parallel_for(0, n, 1 << 14, [&](int64_t b, int64_t e) {
     for (int64_t i = b; i < e; ++i) {
-      float acc = 0.f;
-      for (int k = 0; k < s.count; ++k)
-        acc += s.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(s.ptr[k])[i])
-                                  : static_cast<const float*>(s.ptr[k])[i];
-      acc *= (float)scale;
+      const float acc = cpu_source(s, i, (float)scale);
       if (od == DT_BF16) static_cast<uint16_t*>(out.data_ptr())[i] = f2bf(acc);
       else static_cast<float*>(out.data_ptr())[i] = acc;
     }
   });
+}
+
+// Global L2 norm of `flat` and its clipping coefficient (kernels/clip.hip): out[0] = c, out[1] = n.
+// The host path adds in the device kernels' order -- 256 lanes of sequential fmas per chunk, xor
+// butterfly, waves 0..3, then the chunk partials lane-strided and an fp64 tree -- so CPU and GPU
+// give the same bits for the same stored values.
+void grad_clip_coef_(const at::Tensor& flat, double clip_norm, at::Tensor out, at::Tensor partials, int64_t grid_cap) {
+  TORCH_CHECK(flat.is_contiguous() && (flat.scalar_type() == at::kFloat || flat.scalar_type() == at::kBFloat16),
+              "psd: grad_clip_coef_ takes a contiguous fp32 or bf16 gradient buffer");
+  TORCH_CHECK(std::isfinite(clip_norm) && clip_norm >= 0.0, "psd: clip_norm must be finite and >= 0, got ", clip_norm);
+  const int64_t n = flat.numel(), C = clip_chunks(n);
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.numel() >= 2 && out.is_contiguous() && out.device() == flat.device(),
+              "psd: grad_clip_coef_ out must be an fp32 block of >= 2 elements on the gradient's device");
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.numel() >= C && partials.is_contiguous() &&
+                  partials.device() == flat.device(),
+              "psd: grad_clip_coef_ partials must be fp32 [>= ", C, "] (one per 8192 elements) on the gradient's device");
+  const int32_t dt = dt_of(flat);
+  if (flat.is_cuda()) {
+    const c10::DeviceGuard g(flat.device());
+    check_aligned(flat, "flat gradient");
+    hipStream_t st = cur_stream(flat);
+    hip_check(launch_sumsq_partials(flat.data_ptr(), dt, n, partials.data_ptr<float>(), st, (int)grid_cap), "sumsq_partials");
+    hip_check(launch_clip_finalize(partials.data_ptr<float>(), C, (float)clip_norm, out.data_ptr<float>(), st),
+              "clip_finalize");
+    return;
+  }
+  float* part = partials.data_ptr<float>();
+  const void* gp = flat.data_ptr();
+  auto at_i = [&](int64_t i) {
+    return dt == DT_BF16 ? bf16f(static_cast<const uint16_t*>(gp)[i]) : static_cast<const float*>(gp)[i];
+  };
+  at::parallel_for(0, C, 4, [&](int64_t cb, int64_t ce) {
+    for (int64_t c = cb; c < ce; ++c) {
+      const int64_t off = c * kClipChunk;
+      const int len = (int)std::min<int64_t>(n - off, kClipChunk), nvec = len >> 3;
+      float lane[256];
+      for (int l = 0; l < 256; ++l) {
+        float acc = 0.f;
+        for (int v = l; v < nvec; v += 256)
+          for (int e = 0; e < 8; ++e) {
+            const float x = at_i(off + ((int64_t)v << 3) + e);
+            acc = std::fma(x, x, acc);
+          }
+        lane[l] = acc;
+      }
+      for (int64_t i = off + ((int64_t)nvec << 3); i < off + len; ++i) {  // the n % 8 tail: lane 255
+        const float x = at_i(i);
+        lane[255] = std::fma(x, x, lane[255]);
+      }
+      float w[4];
+      for (int wv = 0; wv < 4; ++wv) {  // xor butterfly of one wave: every lane ends with the same sum
+        float* x = lane + 64 * wv;
+        for (int m = 32; m >= 1; m >>= 1) {
+          float y[64];
+          for (int l = 0; l < 64; ++l) y[l] = x[l] + x[l ^ m];
+          std::memcpy(x, y, sizeof(y));
+        }
+        w[wv] = x[0];
+      }
+      part[c] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+  });
+  double sh[256];
+  for (int l = 0; l < 256; ++l) {
+    double a = 0.0;
+    for (int64_t c = l; c < C; c += 256) a += (double)part[c];
+    sh[l] = a;
+  }
+  for (int s = 128; s >= 1; s >>= 1)
+    for (int l = 0; l < s; ++l) sh[l] += sh[l + s];
+  const float nrm = (float)std::sqrt(sh[0]);
+  const float q = (float)clip_norm / (nrm + 1e-6f);
+  out.data_ptr<float>()[0] = q > 1.f ? 1.f : q;
+  out.data_ptr<float>()[1] = nrm;
 }
 
 void xfer_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts, int64_t blocks_per_seg,

@@ -5,10 +5,15 @@
 
 namespace psd {
 
+// Per-source scales of a multi-source consumer (kernels/launchers.h SourceList::scale): empty / all
+// null, or one fp32 tensor per gradient source on the master's device whose element 0 multiplies
+// that source. A mix of null and set entries is refused.
+using ScaleList = std::vector<c10::optional<at::Tensor>>;
+
 void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
                   c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                   double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
-                  double eps, bool maximize, int64_t grid_cap = 0);
+                  double eps, bool maximize, int64_t grid_cap = 0, const ScaleList& scales = {});
 // The layer table of one contiguous flat range of `n` elements (kernels/launchers_optim_lw.h): tensors
 // (offset relative to the range, numel, ndim), every start on an `align`-element boundary. With
 // exclude_1d, tensors of ndim <= 1 get wd_mult 0 and adapt 0. Returns {meta (CPU: n, segments,
@@ -23,9 +28,14 @@ void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c1
                      c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                      double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
                      double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
-                     int64_t grid_cap = 0);
+                     int64_t grid_cap = 0, const ScaleList& scales = {});
 void optim_advance_(at::Tensor dyn, double beta1, double beta2);
-void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale);
+void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales = {});
+// Global-norm clipping scalars of a flat gradient (kernels/launchers_clip.h): out[0] = c =
+// min(1, clip_norm / (n + 1e-6)), out[1] = n = ||flat||_2. `partials`: fp32 scratch, one element per
+// 8192 elements of `flat`. Two launches on the current stream, no allocation.
+void grad_clip_coef_(const at::Tensor& flat, double clip_norm, at::Tensor out, at::Tensor partials,
+                     int64_t grid_cap = 0);
 void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts);
 // the async plane's scatter kernel (kernels/xfer.hip) on explicit segments, on the current stream:
 // dsts[i] <- srcs[i] bytewise, blocks_per_seg workgroups per segment (transport measurements)

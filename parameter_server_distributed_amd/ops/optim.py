@@ -19,6 +19,7 @@ struct (``OptimDyn``) so a captured hipGraph replays with the current values.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import asdict, dataclass
 
 import torch
@@ -44,6 +45,9 @@ class OptimConfig:
     trust_coef: float = 0.001  # LARS eta (lamb ignores it)
     # tensors of ndim <= 1 take no weight decay and no trust ratio; None: True for lars / lamb, else False
     exclude_1d: bool | None = None
+    # global-norm gradient clipping, per push (async plane): each worker's gradient is scaled by
+    # min(1, clip_norm / (||g||_2 + 1e-6)) before the round is averaged; 0: off
+    clip_norm: float = 0.0
 
     def __post_init__(self):
         if self.kind not in KINDS:
@@ -53,6 +57,9 @@ class OptimConfig:
         if self.exclude_1d is None:
             self.exclude_1d = self.kind in LAYERWISE
         self.exclude_1d = bool(self.exclude_1d)
+        self.clip_norm = float(self.clip_norm)
+        if not math.isfinite(self.clip_norm) or self.clip_norm < 0.0:
+            raise ValueError(f"clip_norm must be finite and >= 0 (0: no clipping), got {self.clip_norm}")
 
     @property
     def code(self) -> int:
@@ -143,13 +150,18 @@ class LayerTable:
 
 
 def fused_apply_(cfg: OptimConfig, dyn: OptimDyn, master: torch.Tensor, grads, state1=None, state2=None,
-                 shadow=None, advance: bool = True, layers: LayerTable | None = None, grid_cap: int = 0) -> None:
+                 shadow=None, advance: bool = True, layers: LayerTable | None = None, grid_cap: int = 0,
+                 scales=None) -> None:
     """In-place fused update of ``master`` from the sum of ``grads`` (list or tensor). ``layers``:
     the ``LayerTable`` of ``master``'s range -- required for lars / lamb and with ``exclude_1d``,
-    rejected otherwise (a table that changes nothing would only hide a configuration mistake)."""
+    rejected otherwise (a table that changes nothing would only hide a configuration mistake).
+    ``scales``: one fp32 tensor per gradient source on ``master``'s device (element 0 is used): the
+    update then sees ``grad_scale * sum_k scales[k] * grads[k]``, multiplied inside the same kernel
+    pass (the per-push clipping coefficients of the async plane). ``None``: the unscaled kernels."""
     C = native()
     if isinstance(grads, torch.Tensor):
         grads = [grads]
+    scales = _check_scales(scales, len(grads))
     if cfg.needs_layers and layers is None:
         raise ValueError(f"optimizer {cfg.kind!r} (exclude_1d={cfg.exclude_1d}) needs the tensor boundaries: pass "
                          f"layers=LayerTable(...)")
@@ -163,11 +175,45 @@ def fused_apply_(cfg: OptimConfig, dyn: OptimDyn, master: torch.Tensor, grads, s
         C.optim_advance_(dyn.t, cfg.beta1, cfg.beta2)
     if layers is None:
         C.fused_apply_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
-                       cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, grid_cap)
+                       cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, grid_cap, scales)
     else:
         C.fused_apply_lw_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
                           cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, cfg.trust_coef,
-                          layers.t, grid_cap)
+                          layers.t, grid_cap, scales)
+
+
+def _check_scales(scales, k: int) -> list:
+    """``[]`` for no scales, else one tensor per source; a partial list is the caller's mistake."""
+    if scales is None:
+        return []
+    scales = list(scales)
+    if len(scales) != k or any(s is None for s in scales):
+        raise ValueError(f"scales must hold one tensor for each of the {k} gradient sources (or be None), got "
+                         f"{sum(s is not None for s in scales)} of {len(scales)} set")
+    return scales
+
+
+def multi_reduce_(out: torch.Tensor, srcs, scale: float = 1.0, scales=None) -> None:
+    """``out = scale * sum_k srcs[k]``, or with ``scales`` ``scale * sum_k scales[k] * srcs[k]``."""
+    srcs = list(srcs)
+    native().multi_reduce_(out, srcs, scale, _check_scales(scales, len(srcs)))
+
+
+def clip_chunks(n: int) -> int:
+    """Elements of the ``partials`` scratch ``grad_clip_coef_`` needs for ``n`` gradient elements."""
+    return max(1, (int(n) + 8191) // 8192)
+
+
+def grad_clip_coef_(flat: torch.Tensor, clip_norm: float, out: torch.Tensor, partials: torch.Tensor,
+                    grid_cap: int = 0) -> None:
+    """``out[1] = n = ||flat||_2`` and ``out[0] = c = min(1, clip_norm / (n + 1e-6))`` (the formula of
+    ``torch.nn.utils.clip_grad_norm_``; a non-finite norm propagates) of a flat bf16 / fp32 gradient
+    buffer, on the current stream (gfx950 kernels ``csrc/kernels/clip.hip``: a streaming pass with
+    one fp32 partial per 8192 elements, then one workgroup that adds them in fp64). ``out``: fp32,
+    at least 2 elements (the async plane passes its 256-byte push-scalar block); ``partials``: fp32
+    scratch of ``clip_chunks(n)`` elements. No allocation, no sync; the result's bits do not depend
+    on ``grid_cap``."""
+    native().grad_clip_coef_(flat, float(clip_norm), out, partials, grid_cap)
 
 
 def advance_(cfg: OptimConfig, dyn: OptimDyn) -> None:

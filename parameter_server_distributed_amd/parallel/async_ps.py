@@ -35,6 +35,13 @@ Optimizer semantics (``semantics``):
           displacement -- lower latency, approximate. Both are pinned against the synchronous
           trajectory in tests/test_async_ps.py.
 
+Gradient clipping (``OptimConfig.clip_norm > 0``) is per push: the buckets leave raw while backward
+runs; ``finish_step`` then runs the norm pass over the whole flat gradient (``grad_clip_coef_``,
+csrc/kernels/clip.hip), sends the resulting 256-byte scalar block after the buckets
+(``engine.push_scalars``, same transport, ahead of the commit) and the owner's fused apply multiplies
+each source of a round by its worker's coefficient ``min(1, clip_norm / (||g|| + 1e-6))`` in the
+pass that sums them. ``grad_norm()`` reports the last step's (norm, coefficient).
+
 Layout: the parameters live in one flat working buffer (``.data`` views, reverse registration
 order, 64-element aligned) split into P contiguous shards (cut at the nearest tensor starts when the
 optimizer needs tensor boundaries: lars, lamb, ``exclude_1d``; each owner then applies with the
@@ -59,7 +66,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import native
-from ..ops.optim import LAYERWISE, LayerTable, OptimConfig, OptimDyn
+from ..ops.optim import LAYERWISE, LayerTable, OptimConfig, OptimDyn, clip_chunks, grad_clip_coef_
 from ..utils.config import fault, feature
 from .collective_ps import ALIGN, _flat_view, _round, install_fp8_weights, zero_grads_, zero_plan
 
@@ -221,6 +228,13 @@ class AsyncPS:
             if self.pull_mx else []
         self.grads = [torch.zeros(total, dtype=param_dtype, device=dev) for _ in range(2)]
         self.gb = 0
+        # per-push global-norm clipping (OptimConfig.clip_norm > 0): the push scalars -- 256-byte
+        # blocks [c, ||g||, 0...] -- alternate with the gradient buffers (step t-2's push may still be
+        # reading the other one); one scratch of per-chunk partial sums. Off: nothing is allocated.
+        self.clip = optim.clip_norm > 0
+        self.scal = [torch.zeros(64, dtype=torch.float32, device=dev) for _ in range(2)] if self.clip else []
+        self.clip_partials = torch.zeros(clip_chunks(total), dtype=torch.float32, device=dev) if self.clip else None
+        self._last_scal = None
         f32 = dict(dtype=torch.float32, device=dev)
         # per-push hyperparameters (module docstring)
         if semantics not in ("round", "push"):
@@ -300,7 +314,7 @@ class AsyncPS:
             self.store.wait([f"{key}/ctl"])
         self.engine = C.AsyncEngine(self.rank, self.world, self.owners, self.worker_ranks, self.shard_off,
                                     self.shard_len, self.S, nbuf, shm, self.rank == 0, devidx, timeout_s,
-                                    torch.finfo(param_dtype).bits // 8, self.pull_mx)
+                                    torch.finfo(param_dtype).bits // 8, self.pull_mx, self.clip)
         if self.rank == 0:
             self.store.set(f"{key}/ctl", b"1")
         try:
@@ -377,6 +391,9 @@ class AsyncPS:
         if self.is_worker:
             pat = (torch.arange(self.total, device=dev) % 251 + (self.rank + 1)).to(self.param_dtype)
             self.engine.push(0, pat, 0, self.total, self._stream_ptr())
+            if self.clip:  # the scalar slots travel by the same transport: round-trip a block too
+                blk = torch.arange(64, dtype=torch.float32, device=dev) + 0.5 * (self.rank + 1)
+                self.engine.push_scalars(0, blk, self._stream_ptr())
             got = torch.empty_like(self.params_flat)
             self.engine.pull(0, got, self._stream_ptr())
             if self.is_cuda:
@@ -401,6 +418,11 @@ class AsyncPS:
                 if not torch.equal(v, want):
                     ok, why = False, f"rank {self.rank}: shard {k} inbox of worker {w} holds wrong data"
                 v.zero_()
+                if self.clip:
+                    sv = self.engine.scalar_view(k, wi, 0)
+                    if not torch.equal(sv, torch.arange(64, dtype=torch.float32, device=dev) + 0.5 * (w + 1)):
+                        ok, why = False, f"rank {self.rank}: shard {k} scalar slot of worker {w} holds wrong data"
+                    sv.zero_()
         if self.is_cuda:
             torch.cuda.synchronize(dev)
         self._agree("selftest", "" if ok else why, attempt=tag)
@@ -559,6 +581,18 @@ class AsyncPS:
         while self._next < len(self.buckets):
             self._push(self.buckets[self._next])
             self._next += 1
+        if self.clip:
+            # the whole gradient is in the buffer now (the buckets above are already on their way):
+            # one read-only pass -> this push's scalar, which follows the buckets on the comm stream
+            # ahead of the commit, so it lands behind the same release as they do
+            blk = self.scal[self.gb]
+            grad_clip_coef_(self.grads[self.gb], self.cfg.clip_norm, blk, self.clip_partials)
+            if self.is_cuda:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                self.comm_stream.wait_event(ev)
+            self.engine.push_scalars(self.step_idx, blk, self.comm_stream.cuda_stream if self.is_cuda else 0)
+            self._last_scal = blk
         if self.is_cuda:
             for cs in self.comm_streams[1:]:  # the commit posts after every push copy has landed
                 ev = torch.cuda.Event()
@@ -579,6 +613,17 @@ class AsyncPS:
 
     def idle_step(self):
         pass
+
+    def grad_norm(self) -> tuple:
+        """``(norm, coef)`` of this worker's last finished step: the L2 norm of its whole gradient
+        as pushed and the clipping coefficient the owners applied to it. For logs and tests: reads
+        the device, so it synchronises; the step itself never calls it."""
+        if not self.clip:
+            raise RuntimeError("grad_norm() needs OptimConfig.clip_norm > 0 (the norm pass runs only then)")
+        if self._last_scal is None:
+            raise RuntimeError("grad_norm() before the first finished step")
+        c, n = self._last_scal[:2].tolist()
+        return n, c
 
     # ------------------------------------------------------------------ end of run / reporting
     def drain(self):

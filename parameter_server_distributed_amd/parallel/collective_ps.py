@@ -135,6 +135,13 @@ class CollectivePS:
             raise ValueError(f"optimizer {optim.kind!r} with exclude_1d={optim.exclude_1d} needs per-tensor shards: "
                              f"the collective plane cuts buckets into equal slices; use the async plane "
                              f"(parallel.async_ps.AsyncPS), which puts shard boundaries on tensor starts")
+        if optim.clip_norm > 0:
+            # clipping is per push: by the time an owner sees a bucket here the reduce-scatter has
+            # already summed the workers' gradients, and no worker's norm is known before its last bucket
+            raise ValueError(f"clip_norm={optim.clip_norm} is not supported on the collective plane: the "
+                             f"reduce-scatter has summed the workers' buckets before any gradient norm is known; "
+                             f"use the async plane (parallel.async_ps.AsyncPS), which clips each push inside the "
+                             f"owner's fused apply")
         self.model = model
         self.cfg = optim
         self.t = transport or LocalTransport()

@@ -41,7 +41,7 @@ class Worker:
     def __init__(self, coordinator: str, worker_id: int, worker_addr: str = "", worker_port: int = 0,
                  model: str = "mlp", batch: int = 64, device: str = "cpu", heartbeat_s: float = 5.0,
                  rpc_timeout: float = 60.0, sync_wait_s: float = 30.0, seed: int = 0, bf16_wire: bool = False,
-                 raw_wire: bool = True, mode: str = "sync"):
+                 raw_wire: bool = True, mode: str = "sync", clip_norm: float = 0.0):
         self.log = get_logger(f"worker{worker_id}")
         self.coordinator_addr = coordinator
         self.worker_id = int(worker_id)
@@ -51,6 +51,9 @@ class Worker:
         self.rpc_timeout = rpc_timeout
         self.sync_wait_ms = int(sync_wait_s * 1000)
         self.bf16_wire, self.raw_wire = bf16_wire, raw_wire
+        self.clip_norm = float(clip_norm)
+        if not (self.clip_norm >= 0.0 and self.clip_norm != float("inf")):
+            raise ValueError(f"clip_norm must be finite and >= 0 (0: no clipping), got {clip_norm}")
         self.device = torch.device(device)
         torch.manual_seed(seed)  # identical init on every worker (only worker 0's is used)
         dtype = torch.float32 if self.device.type == "cpu" else torch.bfloat16
@@ -166,7 +169,14 @@ class Worker:
         x, y = self.batch
         loss = self.spec.loss(self.model(x), y)
         loss.backward()
-        return float(loss.detach().float()), [(n, p.grad.detach()) for n, p in self.model.named_parameters()]
+        grads = [(n, p.grad.detach()) for n, p in self.model.named_parameters()]
+        if self.clip_norm > 0:
+            # per-push global-norm clipping with the async plane's formula (ops/optim.py
+            # grad_clip_coef_), before the gradients are serialised; a host path: plain torch
+            norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g.float()) for _n, g in grads]))
+            coef = torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0)
+            grads = [(n, (g.float() * coef).to(g.dtype)) for n, g in grads]
+        return float(loss.detach().float()), grads
 
     def push(self, iteration: int, grads):
         delay = fault("push_delay_ms")
