@@ -2,20 +2,17 @@
 // LDS) and kernels/attention_long.hip (128 < S <= 512, streaming); attn_fwd / attn_bwd dispatch on S.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
 #include <cmath>
 #include <vector>
 
+#include "glue.h"
 #include "kernels/launchers_attn.h"
 #include "kernels/launchers_gemm.h"
 
 namespace psd {
 
 namespace {
-inline hipStream_t attn_stream(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
 void check_attn(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd attn: ", what,
               " must be a contiguous bf16 device tensor");
@@ -37,8 +34,8 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
   a.thresh = p > 0.0 ? (uint32_t)std::min(4294967295.0, std::floor(p * 4294967296.0)) : 0u;
   a.rescale = (float)(1.0 / (1.0 - p));
   a.seed = (uint32_t)seed;
-  a.step = (step.has_value() && step->defined()) ? step->data_ptr<int64_t>() : nullptr;
-  if (lens.has_value() && lens->defined()) {  // per-sequence lengths, clamped and read on the device only
+  a.step = given(step) ? step->data_ptr<int64_t>() : nullptr;
+  if (given(lens)) {  // per-sequence lengths, clamped and read on the device only
     TORCH_CHECK(lens->scalar_type() == at::kInt && lens->is_contiguous() && lens->numel() == qkv.size(0) &&
                     lens->device() == qkv.device(),
                 "psd attn: lens must be a contiguous int32 [B] tensor on qkv's device");
@@ -59,9 +56,9 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.lse = lse.data_ptr<float>();
-  hipError_t e = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads))) ? launch_attn_long_fwd(a, attn_stream(qkv))
-                                                                            : launch_attn_fwd(a, attn_stream(qkv));
-  TORCH_CHECK(e == hipSuccess, "psd attn fwd: ", hipGetErrorString(e));
+  hipError_t e = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads))) ? launch_attn_long_fwd(a, stream_of(qkv))
+                                                                            : launch_attn_fwd(a, stream_of(qkv));
+  check_hip(e, "psd attn fwd");
   return {o, lse};
 }
 
@@ -90,7 +87,7 @@ at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::
   a.lse = lse.data_ptr<float>();
   a.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
   a.dqkv = reinterpret_cast<uint16_t*>(dqkv.data_ptr());
-  const bool bias = bias_out.has_value() && bias_out->defined();
+  const bool bias = given(bias_out);
   const bool is_long = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads)));
   const int prows = is_long ? attn_long_bpart_rows(a.B, a.S) : a.B;  // partial rows: one per work item of a sequence
   at::Tensor bpart;
@@ -104,15 +101,15 @@ at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::
   hipError_t e;
   if (is_long) {  // D = rowsum(dO . O): written by the dQ pass, read by the dK/dV pass
     at::Tensor dsum = at::empty({(int64_t)a.B, heads, (int64_t)a.S}, qkv.options().dtype(at::kFloat));
-    e = launch_attn_long_bwd(a, dsum.data_ptr<float>(), attn_stream(qkv));
+    e = launch_attn_long_bwd(a, dsum.data_ptr<float>(), stream_of(qkv));
   } else {
-    e = launch_attn_bwd(a, attn_stream(qkv));
+    e = launch_attn_bwd(a, stream_of(qkv));
   }
-  TORCH_CHECK(e == hipSuccess, "psd attn bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd attn bwd");
   if (bias) {
     e = launch_colsum_final(a.bpart, prows, (int)qkv.size(2), bias_out->data_ptr(),
-                            bias_out->scalar_type() == at::kBFloat16, 0, attn_stream(qkv));
-    TORCH_CHECK(e == hipSuccess, "psd attn bwd bias: ", hipGetErrorString(e));
+                            bias_out->scalar_type() == at::kBFloat16, 0, stream_of(qkv));
+    check_hip(e, "psd attn bwd bias");
   }
   return dqkv;
 }

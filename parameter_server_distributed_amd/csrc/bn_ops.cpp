@@ -1,10 +1,10 @@
 // Tensor glue for the fused NHWC BatchNorm kernels (kernels/bn.hip).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
 #include <vector>
 
+#include "glue.h"
 #include "kernels/launchers_bn.h"
 #include "ops.h"
 #include "kernels/launchers_stem.h"
@@ -13,8 +13,6 @@ namespace psd {
 
 namespace {
 
-inline hipStream_t stream_of(const at::Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
-
 at::Tensor nhwc(const at::Tensor& t) {
   if (t.dim() == 4) return t.contiguous(at::MemoryFormat::ChannelsLast);
   return t.contiguous();
@@ -22,13 +20,8 @@ at::Tensor nhwc(const at::Tensor& t) {
 
 int64_t channels(const at::Tensor& t) { return t.dim() == 4 ? t.size(1) : t.size(-1); }
 
-template <typename T>
-T* opt_ptr(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
-}
-
 void check_vec(const c10::optional<at::Tensor>& t, int64_t C, at::ScalarType st, const char* name) {
-  if (!t.has_value() || !t->defined()) return;
+  if (!given(t)) return;
   TORCH_CHECK(t->numel() == C && t->scalar_type() == st && t->is_contiguous(), "psd bn: ", name, " must be [C] ",
               st);
 }
@@ -53,13 +46,13 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x_in, c10::optional<at::Tensor>
   check_vec(running_mean, C, at::kFloat, "running_mean");
   check_vec(running_var, C, at::kFloat, "running_var");
   at::Tensor res;
-  if (residual.has_value() && residual->defined()) {
+  if (given(residual)) {
     res = nhwc(*residual);
     TORCH_CHECK(res.sizes() == x.sizes() && res.scalar_type() == at::kBFloat16, "psd bn: residual shape/dtype");
   }
   auto f32 = x.options().dtype(at::kFloat);
   TORCH_CHECK(!stats_only || training, "psd bn: stats_only needs training mode");
-  const bool rss = residual_ss.has_value() && residual_ss->defined();
+  const bool rss = given(residual_ss);
   if (rss)
     TORCH_CHECK(res.defined() && relu && residual_ss->numel() == 2 * C && residual_ss->scalar_type() == at::kFloat &&
                     residual_ss->is_contiguous(),
@@ -70,7 +63,7 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x_in, c10::optional<at::Tensor>
   at::Tensor mean = at::empty({C}, f32), invstd = at::empty({C}, f32);
   at::Tensor ss;
   at::Tensor part, fold;
-  const bool have_part = part_in.has_value() && part_in->defined();
+  const bool have_part = given(part_in);
   if (training) {
     ss = at::empty({2 * C}, f32);
     if (have_part) {  // statistics partials from the producing convolution's epilogue (kernels/convn.hip)
@@ -112,21 +105,21 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x_in, c10::optional<at::Tensor>
   a.eps = (float)eps;
   a.res_ss = rss ? residual_ss->data_ptr<float>() : nullptr;
   a.stats_only = stats_only;
-  if (q8_out.has_value() && q8_out->defined()) {
+  if (given(q8_out)) {
     const at::Tensor& q = *q8_out;
-    const bool laid = q.dim() == 4 ? q.is_contiguous(at::MemoryFormat::ChannelsLast) : q.is_contiguous();
+    const bool laid = nhwc_laid(q);
     TORCH_CHECK(!stats_only && relu && q.scalar_type() == at::kFloat8_e4m3fn && q.sizes() == x.sizes() && laid &&
                     (reinterpret_cast<uintptr_t>(q.data_ptr()) & 7) == 0,
                 "psd bn: q8_out must be an e4m3fn tensor laid out like x (ReLU BNs)");
     a.q8 = reinterpret_cast<uint8_t*>(q.data_ptr());
     // MX: E8M0 per 32 channels
-    TORCH_CHECK(q8_mx.has_value() && q8_mx->defined() && q8_mx->scalar_type() == at::kByte && q8_mx->is_contiguous() &&
+    TORCH_CHECK(given(q8_mx) && q8_mx->scalar_type() == at::kByte && q8_mx->is_contiguous() &&
                     q8_mx->numel() * 32 == x.numel() && C % 32 == 0 && q8_mx->device() == x.device(),
                 "psd bn: q8_out needs q8_mx uint8 [numel / 32] (channels % 32 == 0)");
     a.q8mx = q8_mx->data_ptr<uint8_t>();
   }
   hipError_t e = launch_bn_fwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn fwd: ", hipGetErrorString(e));
+  check_hip(e, "psd bn fwd");
   return {y, mean, invstd, ss, mbits};
 }
 
@@ -140,7 +133,7 @@ at::Tensor bn_reduce_(const at::Tensor& x_in, const at::Tensor& shift) {
   at::Tensor part = at::empty({(int64_t)bn_reduce_blocks(M, (int)C), 2, C}, x.options().dtype(at::kFloat));
   const hipError_t e = launch_bn_reduce(reinterpret_cast<const uint16_t*>(x.data_ptr()), M, (int)C,
                                         shift.data_ptr<float>(), part.data_ptr<float>(), stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_reduce: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_reduce");
   return part;
 }
 
@@ -149,11 +142,11 @@ namespace {
 void set_dq(c10::optional<at::Tensor>& dq, c10::optional<at::Tensor>& dqmx, const at::Tensor& x, uint8_t*& q,
             uint8_t*& sc) {
   q = sc = nullptr;
-  if (!(dq.has_value() && dq->defined())) return;
+  if (!given(dq)) return;
   const at::Tensor& t = *dq;
-  const bool laid = t.dim() == 4 ? t.is_contiguous(at::MemoryFormat::ChannelsLast) : t.is_contiguous();
-  TORCH_CHECK(t.scalar_type() == at::kFloat8_e5m2 && t.sizes() == x.sizes() && laid && dqmx.has_value() &&
-                  dqmx->defined() && dqmx->scalar_type() == at::kByte && dqmx->is_contiguous() &&
+  const bool laid = nhwc_laid(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat8_e5m2 && t.sizes() == x.sizes() && laid && given(dqmx) &&
+                  dqmx->scalar_type() == at::kByte && dqmx->is_contiguous() &&
                   dqmx->numel() * 32 == x.numel() && channels(x) % 32 == 0,
               "psd bn bwd: dq must be e5m2 laid out like x with uint8 [numel / 32] scales (channels % 32 == 0)");
   q = reinterpret_cast<uint8_t*>(t.data_ptr());
@@ -171,7 +164,7 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& dy_in, const at::Tensor& x_in, 
   const c10::DeviceGuard g(x_in.device());
   at::Tensor x = nhwc(x_in), dy = nhwc(dy_in);
   at::Tensor dy2;
-  if (dy2_in.has_value() && dy2_in->defined()) {
+  if (given(dy2_in)) {
     dy2 = nhwc(*dy2_in);
     TORCH_CHECK(dy2.sizes() == x.sizes() && dy2.scalar_type() == at::kBFloat16, "psd bn bwd: dy2 shape/dtype");
   }
@@ -182,15 +175,15 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& dy_in, const at::Tensor& x_in, 
   if (relu) {
     // ReLU mask source: the forward bit-mask, the forward output y, or (no residual) x with the
     // forward scale/shift
-    if (mbits_in.has_value() && mbits_in->defined()) {
+    if (given(mbits_in)) {
       mbits = *mbits_in;
       TORCH_CHECK(need_dr, "psd bn bwd: the bit-mask path is for residual BNs");
       TORCH_CHECK(mbits.scalar_type() == at::kByte && mbits.is_contiguous() && mbits.numel() == M * C / 8,
                   "psd bn bwd: mbits must be uint8 [M*C/8]");
-    } else if (y_in.has_value() && y_in->defined()) {
+    } else if (given(y_in)) {
       y = nhwc(*y_in);
     } else {
-      TORCH_CHECK(ss_in.has_value() && ss_in->defined(), "psd bn bwd: relu needs the forward output or scale/shift");
+      TORCH_CHECK(given(ss_in), "psd bn bwd: relu needs the forward output or scale/shift");
       TORCH_CHECK(!need_dr, "psd bn bwd: a residual ReLU mask needs the forward output");
       ss = ss_in->contiguous();
       TORCH_CHECK(ss.numel() == 2 * C && ss.scalar_type() == at::kFloat, "psd bn bwd: ss must be fp32 [2C]");
@@ -200,9 +193,9 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& dy_in, const at::Tensor& x_in, 
   at::Tensor dx = at::empty_like(x);
   at::Tensor dr = need_dr ? at::empty_like(x) : at::Tensor();
   at::Tensor dgamma, dbeta;
-  if (gamma.has_value() && gamma->defined()) {
-    dgamma = (dgamma_out.has_value() && dgamma_out->defined()) ? *dgamma_out : at::empty({C}, x.options());
-    dbeta = (dbeta_out.has_value() && dbeta_out->defined()) ? *dbeta_out : at::empty({C}, x.options());
+  if (given(gamma)) {
+    dgamma = given(dgamma_out) ? *dgamma_out : at::empty({C}, x.options());
+    dbeta = given(dbeta_out) ? *dbeta_out : at::empty({C}, x.options());
     TORCH_CHECK(dgamma.numel() == C && dgamma.scalar_type() == at::kBFloat16 && dgamma.is_contiguous(),
                 "psd bn bwd: dgamma buffer");
     TORCH_CHECK(dbeta.numel() == C && dbeta.scalar_type() == at::kBFloat16 && dbeta.is_contiguous(),
@@ -231,7 +224,7 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& dy_in, const at::Tensor& x_in, 
   a.relu = relu;
   set_dq(dq, dqmx, x, a.dq, a.dqmx);
   hipError_t e = launch_bn_bwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd bn bwd");
   return {dx, dr, dgamma, dbeta};
 }
 
@@ -248,7 +241,7 @@ at::Tensor bn_bwd_reduce_(const at::Tensor& dy_in, const at::Tensor& x_in, const
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16 &&
                   C % 8 == 0 && save_mean.numel() == C,
               "psd bn_bwd_reduce: dy like x (bf16, C % 8 == 0), mean [C]");
-  const bool bits = mbits_in.has_value() && mbits_in->defined();
+  const bool bits = given(mbits_in);
   at::Tensor dy2, ss, mbits, dr;
   if (bits) {
     mbits = *mbits_in;
@@ -256,10 +249,10 @@ at::Tensor bn_bwd_reduce_(const at::Tensor& dy_in, const at::Tensor& x_in, const
                 "psd bn_bwd_reduce: mbits must be uint8 [M*C/8]");
     dr = at::empty_like(x);
   } else {
-    TORCH_CHECK(ss_in.has_value() && ss_in->defined() && ss_in->numel() == 2 * C, "psd bn_bwd_reduce: ss [2C]");
+    TORCH_CHECK(given(ss_in) && ss_in->numel() == 2 * C, "psd bn_bwd_reduce: ss [2C]");
     ss = ss_in->contiguous();
   }
-  if (dy2_in.has_value() && dy2_in->defined()) {
+  if (given(dy2_in)) {
     dy2 = nhwc(*dy2_in);
     TORCH_CHECK(dy2.sizes() == x.sizes() && dy2.scalar_type() == at::kBFloat16, "psd bn_bwd_reduce: dy2 like x");
   }
@@ -278,7 +271,7 @@ at::Tensor bn_bwd_reduce_(const at::Tensor& dy_in, const at::Tensor& x_in, const
   a.relu = 1;
   a.reduce_only = 1;
   const hipError_t e = launch_bn_bwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_bwd_reduce: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_bwd_reduce");
   return part;
 }
 
@@ -301,9 +294,9 @@ std::vector<at::Tensor> bn_bwd_pre(const at::Tensor& g_in, const at::Tensor& x_i
   auto f32 = x.options().dtype(at::kFloat);
   at::Tensor dx = at::empty_like(x);
   at::Tensor dgamma, dbeta;
-  if (gamma.has_value() && gamma->defined()) {
-    dgamma = (dgamma_out.has_value() && dgamma_out->defined()) ? *dgamma_out : at::empty({C}, x.options());
-    dbeta = (dbeta_out.has_value() && dbeta_out->defined()) ? *dbeta_out : at::empty({C}, x.options());
+  if (given(gamma)) {
+    dgamma = given(dgamma_out) ? *dgamma_out : at::empty({C}, x.options());
+    dbeta = given(dbeta_out) ? *dbeta_out : at::empty({C}, x.options());
   }
   at::Tensor coef = at::empty({3 * C}, f32);
   at::Tensor fold = rows > kFoldRows ? at::empty({(int64_t)kFoldRows * 2 * C}, f32) : at::Tensor();
@@ -316,7 +309,7 @@ std::vector<at::Tensor> bn_bwd_pre(const at::Tensor& g_in, const at::Tensor& x_i
       dgamma.defined() ? reinterpret_cast<uint16_t*>(dgamma.data_ptr()) : nullptr,
       dbeta.defined() ? reinterpret_cast<uint16_t*>(dbeta.data_ptr()) : nullptr, coef.data_ptr<float>(),
       reinterpret_cast<uint16_t*>(dx.data_ptr()), M, (int)C, stream_of(x), q8, q8mx);
-  TORCH_CHECK(e == hipSuccess, "psd bn_bwd_pre: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_bwd_pre");
   return {dx, dgamma, dbeta};
 }
 
@@ -338,7 +331,7 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy_in, const at::Tensor& x
                   dy.scalar_type() == at::kBFloat16 && xd.scalar_type() == at::kBFloat16,
               "psd bn bwd_dual: dy / xd like x (bf16)");
   at::Tensor dy2;
-  if (dy2_in.has_value() && dy2_in->defined()) {
+  if (given(dy2_in)) {
     dy2 = nhwc(*dy2_in);
     TORCH_CHECK(dy2.sizes() == x.sizes() && dy2.scalar_type() == at::kBFloat16, "psd bn bwd_dual: dy2 shape/dtype");
   }
@@ -347,7 +340,7 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy_in, const at::Tensor& x
   for (const at::Tensor* t : {&save_mean, &save_invstd, &mean_d, &invstd_d})
     TORCH_CHECK(t->numel() == C && t->scalar_type() == at::kFloat && t->is_contiguous(), "psd bn bwd_dual: stats [C]");
   auto grad_buf = [&](const c10::optional<at::Tensor>& o) {
-    at::Tensor t = (o.has_value() && o->defined()) ? *o : at::empty({C}, x.options());
+    at::Tensor t = given(o) ? *o : at::empty({C}, x.options());
     TORCH_CHECK(t.numel() == C && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd bn bwd_dual: grad buffer");
     return t;
   };
@@ -386,7 +379,7 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy_in, const at::Tensor& x
   a.coef_d = coef_d.data_ptr<float>();
   a.part_d = part_d.data_ptr<float>();
   hipError_t e = launch_bn_bwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn bwd_dual: ", hipGetErrorString(e));
+  check_hip(e, "psd bn bwd_dual");
   if (fold) return {dx, dxd, dgamma, dbeta, dgamma_d, dbeta_d, coef, dr};
   return {dx, dxd, dgamma, dbeta, dgamma_d, dbeta_d};
 }
@@ -411,14 +404,14 @@ std::vector<at::Tensor> bn_bwd_coef(const at::Tensor& dy_in, const at::Tensor& x
     TORCH_CHECK(t->numel() == C && t->scalar_type() == at::kFloat && t->is_contiguous(), "psd bn_bwd_coef: stats [C]");
   auto f32 = x.options().dtype(at::kFloat);
   auto grad_buf = [&](const c10::optional<at::Tensor>& o) {
-    at::Tensor t = (o.has_value() && o->defined()) ? *o : at::empty({C}, x.options());
+    at::Tensor t = given(o) ? *o : at::empty({C}, x.options());
     TORCH_CHECK(t.numel() == C && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd bn_bwd_coef: grad buffer");
     return t;
   };
   at::Tensor dgamma = grad_buf(dgamma_out), dbeta = grad_buf(dbeta_out);
   at::Tensor coef = at::empty({3 * C}, f32);
   const uint16_t* gam = reinterpret_cast<const uint16_t*>(gamma.data_ptr());
-  if (part.has_value() && part->defined()) {
+  if (given(part)) {
     TORCH_CHECK(part->scalar_type() == at::kFloat && part->is_contiguous() && rows > 0 && part->numel() >= rows * 2 * C,
                 "psd bn_bwd_coef: part must be fp32 [rows, 2, C]");
     at::Tensor fold = rows > kFoldRows ? at::empty({(int64_t)kFoldRows * 2 * C}, f32) : at::Tensor();
@@ -427,14 +420,14 @@ std::vector<at::Tensor> bn_bwd_coef(const at::Tensor& dy_in, const at::Tensor& x
         save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), part->data_ptr<float>(), (int)rows,
         fold.defined() ? fold.data_ptr<float>() : nullptr, reinterpret_cast<uint16_t*>(dgamma.data_ptr()),
         reinterpret_cast<uint16_t*>(dbeta.data_ptr()), coef.data_ptr<float>(), nullptr, M, (int)C, stream_of(x));
-    TORCH_CHECK(e == hipSuccess, "psd bn_bwd_coef: ", hipGetErrorString(e));
+    check_hip(e, "psd bn_bwd_coef");
     return {dy, coef, dgamma, dbeta};
   }
-  TORCH_CHECK(mbits_in.has_value() && mbits_in->defined() && mbits_in->scalar_type() == at::kByte &&
+  TORCH_CHECK(given(mbits_in) && mbits_in->scalar_type() == at::kByte &&
                   mbits_in->is_contiguous() && mbits_in->numel() == M * C / 8,
               "psd bn_bwd_coef: without partials the forward bit-mask (uint8 [M*C/8]) is required");
   at::Tensor dy2;
-  if (dy2_in.has_value() && dy2_in->defined()) {
+  if (given(dy2_in)) {
     dy2 = nhwc(*dy2_in);
     TORCH_CHECK(dy2.sizes() == x.sizes() && dy2.scalar_type() == at::kBFloat16, "psd bn_bwd_coef: dy2 shape/dtype");
   }
@@ -458,7 +451,7 @@ std::vector<at::Tensor> bn_bwd_coef(const at::Tensor& dy_in, const at::Tensor& x
   a.relu = 1;
   a.coef_only = 1;
   const hipError_t e = launch_bn_bwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_bwd_coef: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_bwd_coef");
   return {g, coef, dgamma, dbeta};
 }
 
@@ -505,7 +498,7 @@ std::vector<at::Tensor> bn_pool_fwd(const at::Tensor& x_in, const at::Tensor& ga
   a.momentum = (float)momentum;
   a.eps = (float)eps;
   hipError_t e = launch_bn_fwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_pool fwd: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_pool fwd");
   return {y, arg, mean, invstd, ss};
 }
 
@@ -540,7 +533,7 @@ std::vector<at::Tensor> stem_fwd(const at::Tensor& x_in, const at::Tensor& w, co
                                   reinterpret_cast<const uint16_t*>(wk.data_ptr()),
                                   reinterpret_cast<uint16_t*>(conv.data_ptr()), running_mean.data_ptr<float>(),
                                   part.data_ptr<float>(), (int)N, (int)H, (int)W, (int)Ho, (int)Wo, st);
-  TORCH_CHECK(e == hipSuccess, "psd stem conv: ", hipGetErrorString(e));
+  check_hip(e, "psd stem conv");
   at::Tensor y = at::empty({N, 64, Ho / 2, Wo / 2}, cl);
   at::Tensor arg = at::empty({N, 64, Ho / 2, Wo / 2}, cl.dtype(at::kByte));
   at::Tensor mean = at::empty({64}, f32), invstd = at::empty({64}, f32), ss = at::empty({128}, f32);
@@ -568,7 +561,7 @@ std::vector<at::Tensor> stem_fwd(const at::Tensor& x_in, const at::Tensor& w, co
   a.momentum = (float)momentum;
   a.eps = (float)eps;
   e = launch_bn_fwd(a, st);
-  TORCH_CHECK(e == hipSuccess, "psd stem bn_pool: ", hipGetErrorString(e));
+  check_hip(e, "psd stem bn_pool");
   return {y, arg, mean, invstd, ss, conv};
 }
 
@@ -589,7 +582,7 @@ at::Tensor stem_wgrad(const at::Tensor& x_in, const at::Tensor& dy_in) {
                                    reinterpret_cast<const uint16_t*>(dy.data_ptr()), part.data_ptr<float>(),
                                    reinterpret_cast<uint16_t*>(dw.data_ptr()), (int)N, (int)H, (int)W, (int)Ho, (int)Wo,
                                    stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd stem wgrad: ", hipGetErrorString(e));
+  check_hip(e, "psd stem wgrad");
   return dw;
 }
 
@@ -609,15 +602,15 @@ std::vector<at::Tensor> bn_pool_bwd(const at::Tensor& gpool_in, c10::optional<at
               "psd bn_pool bwd: argmax shape");
   TORCH_CHECK(ss.numel() == 2 * C && ss.scalar_type() == at::kFloat && ss.is_contiguous(), "psd bn_pool bwd: ss");
   at::Tensor gp2;
-  if (gpool2_in.has_value() && gpool2_in->defined()) {
+  if (given(gpool2_in)) {
     gp2 = nhwc(*gpool2_in);
     TORCH_CHECK(gp2.sizes() == ps && gp2.scalar_type() == at::kBFloat16, "psd bn_pool bwd: gpool2 shape/dtype");
   }
   const int64_t M = N * H * W;
   auto f32 = x.options().dtype(at::kFloat);
   at::Tensor dx = at::empty_like(x);
-  at::Tensor dgamma = (dgamma_out.has_value() && dgamma_out->defined()) ? *dgamma_out : at::empty({C}, x.options());
-  at::Tensor dbeta = (dbeta_out.has_value() && dbeta_out->defined()) ? *dbeta_out : at::empty({C}, x.options());
+  at::Tensor dgamma = given(dgamma_out) ? *dgamma_out : at::empty({C}, x.options());
+  at::Tensor dbeta = given(dbeta_out) ? *dbeta_out : at::empty({C}, x.options());
   TORCH_CHECK(dgamma.numel() == C && dgamma.scalar_type() == at::kBFloat16 && dgamma.is_contiguous(), "psd bn_pool: dgamma");
   TORCH_CHECK(dbeta.numel() == C && dbeta.scalar_type() == at::kBFloat16 && dbeta.is_contiguous(), "psd bn_pool: dbeta");
   at::Tensor coef = at::empty({3 * C}, f32);
@@ -643,7 +636,7 @@ std::vector<at::Tensor> bn_pool_bwd(const at::Tensor& gpool_in, c10::optional<at
   a.C = (int32_t)C;
   a.relu = 1;
   hipError_t e = launch_bn_bwd(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_pool bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_pool bwd");
   return {dx, dgamma, dbeta};
 }
 
@@ -662,7 +655,7 @@ std::vector<at::Tensor> maxpool3s2_fwd(const at::Tensor& x_in) {
   at::Tensor arg = at::empty({N, C, Ho, Wo}, x.options().dtype(at::kByte).memory_format(at::MemoryFormat::ChannelsLast));
   hipError_t e = launch_maxpool_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()), reinterpret_cast<uint16_t*>(y.data_ptr()),
                                     arg.data_ptr<uint8_t>(), N, H, W, C, Ho, Wo, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd maxpool fwd: ", hipGetErrorString(e));
+  check_hip(e, "psd maxpool fwd");
   return {y, arg};
 }
 at::Tensor maxpool3s2_bwd(const at::Tensor& dy_in, const at::Tensor& arg, int64_t H, int64_t W,
@@ -672,7 +665,7 @@ at::Tensor maxpool3s2_bwd(const at::Tensor& dy_in, const at::Tensor& arg, int64_
   const int N = dy.size(0), C = dy.size(1), Ho = dy.size(2), Wo = dy.size(3);
   TORCH_CHECK(arg.is_contiguous(at::MemoryFormat::ChannelsLast) && arg.sizes() == dy.sizes(), "psd maxpool bwd: argmax shape");
   at::Tensor dy2;
-  if (dy2_in.has_value() && dy2_in->defined()) {
+  if (given(dy2_in)) {
     dy2 = dy2_in->contiguous(at::MemoryFormat::ChannelsLast);
     TORCH_CHECK(dy2.sizes() == dy.sizes() && dy2.scalar_type() == at::kBFloat16, "psd maxpool bwd: dy2 shape/dtype");
   }
@@ -681,7 +674,7 @@ at::Tensor maxpool3s2_bwd(const at::Tensor& dy_in, const at::Tensor& arg, int64_
                                     dy2.defined() ? reinterpret_cast<const uint16_t*>(dy2.data_ptr()) : nullptr,
                                     arg.data_ptr<uint8_t>(),
                                     reinterpret_cast<uint16_t*>(dx.data_ptr()), N, (int)H, (int)W, C, Ho, Wo, stream_of(dy));
-  TORCH_CHECK(e == hipSuccess, "psd maxpool bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd maxpool bwd");
   return dx;
 }
 }  // namespace psd
@@ -697,7 +690,7 @@ at::Tensor gap_fwd(const at::Tensor& x_in) {
   at::Tensor y = at::empty({N, C}, x.options());
   hipError_t e = launch_gap_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()), reinterpret_cast<uint16_t*>(y.data_ptr()),
                                 N, HW, C, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd gap fwd: ", hipGetErrorString(e));
+  check_hip(e, "psd gap fwd");
   return y;
 }
 at::Tensor gap_bwd(const at::Tensor& dy_in, int64_t H, int64_t W) {
@@ -709,7 +702,7 @@ at::Tensor gap_bwd(const at::Tensor& dy_in, int64_t H, int64_t W) {
   at::Tensor dx = at::empty({N, C, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   hipError_t e = launch_gap_bwd(reinterpret_cast<const uint16_t*>(dy.data_ptr()), reinterpret_cast<uint16_t*>(dx.data_ptr()),
                                 N, (int)(H * W), C, stream_of(dy));
-  TORCH_CHECK(e == hipSuccess, "psd gap bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd gap bwd");
   return dx;
 }
 at::Tensor subsample2(const at::Tensor& x) {
@@ -722,7 +715,7 @@ at::Tensor subsample2(const at::Tensor& x) {
                            x.options().memory_format(at::MemoryFormat::ChannelsLast));
   hipError_t e = launch_subsample2(reinterpret_cast<const uint16_t*>(x.data_ptr()), reinterpret_cast<uint16_t*>(y.data_ptr()),
                                    (int)x.size(0), (int)x.size(2), (int)x.size(3), (int)x.size(1), stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd subsample2: ", hipGetErrorString(e));
+  check_hip(e, "psd subsample2");
   return y;
 }
 // ---- BN-backward fold of a 1x1 conv -> BN pair (kernels/bnfold.hip)
@@ -751,7 +744,7 @@ std::vector<at::Tensor> bnfold_dgrad_weights(const at::Tensor& w_in, const at::T
   hipError_t e = launch_bnfold_prep(reinterpret_cast<const uint16_t*>(w.data_ptr()), coef.data_ptr<float>(), (int)Cout,
                                     (int)Cin, reinterpret_cast<uint16_t*>(w2.data_ptr()), (int)(Cout + Cin),
                                     reinterpret_cast<uint16_t*>(bw.data_ptr()), bvec.data_ptr<float>(), stream_of(w));
-  TORCH_CHECK(e == hipSuccess, "psd bnfold prep: ", hipGetErrorString(e));
+  check_hip(e, "psd bnfold prep");
   // M = (B o W)^T W (Cin x Cin, symmetric) into the right block of w2 (the MFMA GEMM, TN layout)
   gemm_(bw, w, false, false, w2.narrow(1, Cout, Cin), c10::nullopt, 0, c10::nullopt, c10::nullopt, c10::nullopt);
   return {w2, bvec};
@@ -775,7 +768,7 @@ void bnfold_combine(const at::Tensor& P, const at::Tensor& w_in, const at::Tenso
   hipError_t e = launch_bnfold_combine(P.data_ptr<float>(), reinterpret_cast<const uint16_t*>(w.data_ptr()),
                                        coef.data_ptr<float>(), (int)Cout, (int)Cin,
                                        reinterpret_cast<uint16_t*>(out.data_ptr()), accumulate ? 1 : 0, stream_of(w));
-  TORCH_CHECK(e == hipSuccess, "psd bnfold combine: ", hipGetErrorString(e));
+  check_hip(e, "psd bnfold combine");
 }
 
 // row [2, Cout] (a view into a partials buffer) = (0, sum_i W[c][i] P[c][i]): the sum g y of a BN
@@ -792,7 +785,7 @@ void bnfold_rowdot(const at::Tensor& P, const at::Tensor& w_in, at::Tensor row) 
               "psd bnfold rowdot: row must be a contiguous fp32 [2, Cout]");
   hipError_t e = launch_bnfold_rowdot(P.data_ptr<float>(), reinterpret_cast<const uint16_t*>(w.data_ptr()), (int)Cout,
                                       (int)Cin, row.data_ptr<float>(), stream_of(w));
-  TORCH_CHECK(e == hipSuccess, "psd bnfold rowdot: ", hipGetErrorString(e));
+  check_hip(e, "psd bnfold rowdot");
 }
 
 // row [2, Cout] = the shifted batch statistics of y = x W^T from P = convw(x, x) in fold mode (the
@@ -813,7 +806,7 @@ void bnfold_gram_stats(const at::Tensor& P, const at::Tensor& w_in, const at::Te
   hipError_t e = launch_bnfold_gram_stats(P.data_ptr<float>(), reinterpret_cast<const uint16_t*>(w.data_ptr()),
                                           shift.data_ptr<float>(), (int)Cout, (int)Cin, M, row.data_ptr<float>(),
                                           stream_of(w));
-  TORCH_CHECK(e == hipSuccess, "psd bnfold gram stats: ", hipGetErrorString(e));
+  check_hip(e, "psd bnfold gram stats");
 }
 
 // The dual tail's apply operands from both convolutions' weights and both BNs' scale/shift
@@ -835,7 +828,7 @@ std::vector<at::Tensor> bnfold_dual_weights(const at::Tensor& w3_in, const at::T
                                             ssd.data_ptr<float>(), (int)Cout, (int)C3, (int)Cd,
                                             reinterpret_cast<uint16_t*>(wcat.data_ptr()), ss.data_ptr<float>(),
                                             stream_of(w3));
-  TORCH_CHECK(e == hipSuccess, "psd bnfold dual weights: ", hipGetErrorString(e));
+  check_hip(e, "psd bnfold dual weights");
   return {wcat, ss};
 }
 
@@ -875,7 +868,7 @@ std::vector<at::Tensor> bn_finalize(const at::Tensor& part, int64_t rows, int64_
   a.eps = (float)eps;
   a.stats_only = true;
   const hipError_t e = launch_bn_fwd(a, stream_of(part));
-  TORCH_CHECK(e == hipSuccess, "psd bn_finalize: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_finalize");
   return {mean, invstd, ss};
 }
 
@@ -890,7 +883,7 @@ at::Tensor bn_elemt_coef(const at::Tensor& g_in, const at::Tensor& x_in, const a
   const hipError_t e = launch_bn_elemt_coef(reinterpret_cast<const uint16_t*>(g.data_ptr()),
                                             reinterpret_cast<const uint16_t*>(x.data_ptr()), coef.data_ptr<float>(),
                                             reinterpret_cast<uint16_t*>(dx.data_ptr()), M, (int)C, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_elemt_coef: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_elemt_coef");
   return dx;  // empty_like keeps the channels_last layout
 }
 
@@ -916,7 +909,7 @@ std::vector<at::Tensor> bn_bwd_dual_pre(const at::Tensor& g_in, const at::Tensor
                     t->numel() >= (derive_d && t == &part_d ? 2 : rows * 2) * C,
                 "psd bn_bwd_dual_pre: partials must be fp32 [rows, 2, C] (derive_d: part_d [2, C])");
   auto grad_buf = [&](const c10::optional<at::Tensor>& o) {
-    at::Tensor t = (o.has_value() && o->defined()) ? *o : at::empty({C}, x.options());
+    at::Tensor t = given(o) ? *o : at::empty({C}, x.options());
     TORCH_CHECK(t.numel() == C && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd bn_bwd_dual_pre: grad buffer");
     return t;
   };
@@ -958,7 +951,7 @@ std::vector<at::Tensor> bn_bwd_dual_pre(const at::Tensor& g_in, const at::Tensor
   a.M = M;
   a.C = (int)C;
   const hipError_t e = launch_bn_bwd_dual_pre(a, stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd bn_bwd_dual_pre: ", hipGetErrorString(e));
+  check_hip(e, "psd bn_bwd_dual_pre");
   return {dx, dxd, dgamma, dbeta, dgamma_d, dbeta_d, coef, coef_d};
 }
 

@@ -1,10 +1,11 @@
 #include "comm.h"
 
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 #include <rccl/rccl.h>
 
 #include <cstring>
+
+#include "glue.h"
 
 namespace psd {
 
@@ -42,7 +43,7 @@ ncclRedOp_t nccl_op(const std::string& op) {
 
 hipStream_t pick_stream(const at::Tensor& t, int64_t stream) {
   if (stream != 0) return reinterpret_cast<hipStream_t>(stream);
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
+  return stream_of(t);
 }
 
 void need_cuda(const at::Tensor& t) {

@@ -1,8 +1,8 @@
 // Tensor glue for the embedding weight gradient (kernels/embed.hip).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
+#include "glue.h"
 #include "kernels/launchers_embed.h"
 
 namespace psd {
@@ -24,9 +24,8 @@ void embed_bwd_(const at::Tensor& sorted, const at::Tensor& perm, const at::Tens
   at::Tensor part = at::empty({(T + kEmbedChunk - 1) / kEmbedChunk, dy.size(1)}, dy.options().dtype(at::kFloat));
   hipError_t e = launch_embed_bwd(sorted.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
                                   reinterpret_cast<const uint16_t*>(dy.data_ptr()), T, (int)dy.size(1),
-                                  part.data_ptr<float>(), reinterpret_cast<uint16_t*>(out.data_ptr()),
-                                  c10::hip::getCurrentHIPStream(dy.device().index()).stream());
-  TORCH_CHECK(e == hipSuccess, "psd embed_bwd: ", hipGetErrorString(e));
+                                  part.data_ptr<float>(), reinterpret_cast<uint16_t*>(out.data_ptr()), stream_of(dy));
+  check_hip(e, "psd embed_bwd");
 }
 
 }  // namespace psd

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "cu_count.h"
 #include "launchers_attn.h"
 #include "attn_frag.h"
 
@@ -44,17 +45,6 @@ __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, in
 }
 
 }  // namespace
-
-static int attn_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
 
 // Persistent (as many workgroups per CU as registers and the 36 KiB K + V image allow): the next
 // (batch, head) item's K, V rows and this lane's Q fragments are loaded into registers while the
@@ -449,7 +439,7 @@ static hipError_t launch_fwd_t(const AttnArgs& a, hipStream_t st) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN>), 64 * NW,
                                                    lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  int grid = std::min(a.B * a.H, per_cu * attn_cus());
+  int grid = std::min(a.B * a.H, per_cu * cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
   hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN>), dim3(grid), dim3(64 * NW), lds, st, a);
   return hipGetLastError();
@@ -461,7 +451,7 @@ static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: one workgroup per CU (the LDS image admits one), each walks items bh, bh + grid, ...
-  int grid = std::min(a.B * a.H, attn_cus());
+  int grid = std::min(a.B * a.H, cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
   hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN>), dim3(grid), dim3(128 * NW), lds, st, a);
   return hipGetLastError();

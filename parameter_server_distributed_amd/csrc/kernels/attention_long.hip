@@ -36,6 +36,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "cu_count.h"
 #include "launchers_attn.h"
 #include "attn_frag.h"
 
@@ -119,17 +120,6 @@ __device__ __forceinline__ float wave_colsum(float* red, const af32x16 (&t)[2]) 
 }
 
 }  // namespace
-
-static int attn_long_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
 
 // Forward. Persistent over items (bh, query tile); LDS: K and V chunk tiles, two buffers.
 template <bool VARLEN>
@@ -507,7 +497,7 @@ static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), NT, 0) != hipSuccess || per_cu < 1)
     per_cu = 1;
   const int64_t nitems = (int64_t)a.B * a.H * ((a.S + 127) / 128);
-  int grid = (int)std::min<int64_t>(nitems, (int64_t)per_cu * attn_long_cus());
+  int grid = (int)std::min<int64_t>(nitems, (int64_t)per_cu * cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
   if (grid < 1) return hipSuccess;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), 0, st, a, extra...);

@@ -18,14 +18,6 @@ typedef __attribute__((address_space(3))) as16x4 alds_s16x4;
 constexpr int D = 64;                 // head dim
 constexpr int LDT = D + 8;            // Q/K/V/dO tile row stride (elements): 144 B
 
-__device__ __forceinline__ uint32_t amix32(uint32_t h) {  // murmur3 finalizer (as layernorm.hip)
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
 // (common.h drop_keep: one hash per element pair, 16 bits each; fwd and bwd index elements alike)
 // keep flags of the element pair (idx, idx + 1), idx even, from ONE hash -- drop_keep's mask bit for bit.
 // (Calling drop_keep per element hashed every pair twice: dropout cost the forward 57 % of its
@@ -36,7 +28,7 @@ __device__ __forceinline__ void akeep2(uint32_t key, uint64_t idx, uint32_t thre
   k1 = (h >> 16) >= (thresh >> 16);
 }
 __device__ __forceinline__ uint32_t attn_key(uint32_t seed, const int64_t* step) {
-  return amix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
+  return drop_mix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
 }
 
 // A/B fragment whose 8 k-values are contiguous in LDS: lane -> row r0 + lane%32, k = k0 + 8*(lane/32) + e

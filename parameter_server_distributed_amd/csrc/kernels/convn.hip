@@ -41,38 +41,21 @@
 // Gathering every K-tile's A rows re-reads each input pixel R*R times through L2 (layer1's 3x3:
 // 9 x 0.41 GB per pass); the persistent HALO kernel below (convh_kernel) stages each input window
 // once and reads the taps as shifted rows.
-#include "common.h"
+#include "mfma_common.h"
+#include "cu_count.h"
 #include "launchers_convn.h"
 
 namespace psd {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
 constexpr int kBM = 128;  // output pixels per tile
 constexpr int kBK = 64;   // k per K-tile (one (r, s), 64 channels)
-constexpr uint32_t kOOB = 0xFFFFFFF0u;  // past every descriptor's range: the load returns zeros
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ int kmaj_off(int row, int kc) {  // byte offset in a [rows][64] bf16 tile
-  return row * 128 + ((kc ^ ((row >> 1) & 7)) << 4);
-}
 
 // 16x16x32 fragment of row block rb, k-step ks: lane holds row rb*16 + (lane & 15), k 8*(lane>>4)..+7
 __device__ __forceinline__ bf16x8 frag(const uint8_t* lds, int rb, int ks, int lane) {
   const int row = rb * 16 + (lane & 15);
   return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lds + kmaj_off(row, ks * 4 + (lane >> 4))));
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // wait until at most `ahead` K-tiles (DPSK loads each) of this wave are still in flight
@@ -84,42 +67,6 @@ __device__ __forceinline__ void wait_ahead(int ahead) {
     if (ahead >= A) wait_vm<A * DPSK>();
     else wait_ahead<DPSK, A - 1>(ahead);
   }
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  // bijective: blocks with equal bid % 8 (one XCD under round-robin dispatch) get a contiguous range
-  const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
-// 4x4 transpose inside a lane quad: in v[r] = C[row r][col L]; out w[c] = C[row L][col c]
-template <int CTRL>
-__device__ __forceinline__ float dpp_q(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ void quad_t4(const f32x4 v, int L, float (&w)[4]) {
-  const bool o1 = L & 1, o2 = (L >> 1) & 1;
-  const float r0 = dpp_q<0xB1>(o1 ? v[0] : v[1]);  // quad_perm [1,0,3,2]: partner L^1
-  const float r1 = dpp_q<0xB1>(o1 ? v[2] : v[3]);
-  const float a0 = o1 ? r0 : v[0], a1 = o1 ? v[1] : r0;
-  const float b0 = o1 ? r1 : v[2], b1 = o1 ? v[3] : r1;
-  const float q0 = dpp_q<0x4E>(o2 ? a0 : b0);  // quad_perm [2,3,0,1]: partner L^2
-  const float q1 = dpp_q<0x4E>(o2 ? a1 : b1);
-  w[0] = o2 ? q0 : a0;
-  w[1] = o2 ? q1 : a1;
-  w[2] = o2 ? b0 : q0;
-  w[3] = o2 ? b1 : q1;
-}
-
-// x[lane ^ 16] / x[lane ^ 32] through the gfx950 half-row / half-wave swaps (VALU, no LDS round
-// trip: the statistics reduction of a one-K-tile convolution is on its critical path)
-__device__ __forceinline__ float xor16(float x, int lane) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((lane & 16) ? r[0] : r[1]);
-}
-__device__ __forceinline__ float xor32(float x, int lane) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((lane & 32) ? r[0] : r[1]);
 }
 
 template <int N>
@@ -1040,16 +987,7 @@ static bool convh_ok(const ConvnArgs& a) {
          a.W == a.Wo && a.Wo + 2 <= 64 && !a.x2 && a.K == 576 && a.ldc == 64;
 }
 
-static int convh_grid(int ntiles) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return ntiles < cus ? ntiles : cus;
-}
+static int convh_grid(int ntiles) { return ntiles < cu_count() ? ntiles : cu_count(); }
 
 template <bool STATS, int BWD>
 static hipError_t convh_launch_t(const ConvnArgs& a, hipStream_t st) {
@@ -1074,17 +1012,6 @@ static hipError_t convh_launch(const ConvnArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ persistent 1x1: host side
-static int cu_count_cached() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // convp geometry per output-tile width: (WNT, waves, LDS bytes) -- NSLOT 3 ring
 template <int BN>
 struct P1Cfg;
@@ -1113,7 +1040,7 @@ constexpr int p1_lds() {
 // than the M tiles -- both forms run one 512-thread workgroup per CU (LDS), and the partial-row
 // count (convn_part_rows) must not depend on which form the launch takes
 static int convp_grid_x(int tiles_m, int tiles_n) {
-  int g = cu_count_cached() / (tiles_n > 0 ? tiles_n : 1);
+  int g = cu_count() / (tiles_n > 0 ? tiles_n : 1);
   if (g < 1) g = 1;
   return g < tiles_m ? g : tiles_m;
 }

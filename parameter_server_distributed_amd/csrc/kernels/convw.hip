@@ -28,7 +28,8 @@
 //     its fp32 partial tile to a slab, the deterministic slab reduce (gemm.hip) writes bf16 dW.
 #include <algorithm>
 
-#include "common.h"
+#include "mfma_common.h"
+#include "cu_count.h"
 #include "launchers_convw.h"
 #include "launchers_gemm.h"
 
@@ -36,18 +37,8 @@ namespace psd {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
 constexpr int kBP = 64;                  // output pixels per stage (two 32-deep MFMA k-steps)
 constexpr int kSub = 64 * 128;           // one [64 px][64 ch] bf16 sub-image
-constexpr uint32_t kOOB = 0xFFFFFFF0u;   // past every descriptor's range: the load returns zeros
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
 
 // 16-B chunk c of sub-image row r is stored at chunk c ^ swz(r). A ds_read_b64_tr_b16 fragment read
 // touches, per 32-lane half, rows {q, q + 8} (q = 0..3, plus a multiple of 16) with one 32-B segment
@@ -65,37 +56,6 @@ __device__ __forceinline__ bf16x8 trfrag(const uint8_t* sub, int ks, int cb, int
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sub + r1 * 128 + ((c ^ swz(r1)) << 4) + b));
   const s16x4 both[2] = {lo, hi};
   return __builtin_bit_cast(bf16x8, both);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  // bijective: blocks with equal bid % 8 (one XCD under round-robin dispatch) get a contiguous range
-  const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
-// 4x4 transpose inside a lane quad: in v[r] = C[row r][col L]; out w[c] = C[row L][col c]
-template <int CTRL>
-__device__ __forceinline__ float dpp_q(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ void quad_t4(const f32x4 v, int L, float (&w)[4]) {
-  const bool o1 = L & 1, o2 = (L >> 1) & 1;
-  const float r0 = dpp_q<0xB1>(o1 ? v[0] : v[1]);
-  const float r1 = dpp_q<0xB1>(o1 ? v[2] : v[3]);
-  const float a0 = o1 ? r0 : v[0], a1 = o1 ? v[1] : r0;
-  const float b0 = o1 ? r1 : v[2], b1 = o1 ? v[3] : r1;
-  const float q0 = dpp_q<0x4E>(o2 ? a0 : b0);
-  const float q1 = dpp_q<0x4E>(o2 ? a1 : b1);
-  w[0] = o2 ? q0 : a0;
-  w[1] = o2 ? q1 : a1;
-  w[2] = o2 ? b0 : q0;
-  w[3] = o2 ? b1 : q1;
 }
 
 template <int TCO, int TKK, int WR, int NSLOT, int NAR = -1>
@@ -433,17 +393,6 @@ constexpr int nslot_of(int tco, int tkk) {
 int lds_of(int tco, int tkk, bool two = false) {
   if (tco == 384) return (two ? 2 : 4) * (256 + 64) / 64 * kSub;  // the single-tile fold: 4 dY + 1 x sub-images
   return (two ? 2 : nslot_of(tco, tkk)) * (tco + tkk) / 64 * kSub;
-}
-
-int cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
 }
 
 template <int TCO, int TKK, int WR, int NSLOT, int NAR = -1>

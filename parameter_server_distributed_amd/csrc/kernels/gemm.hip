@@ -21,7 +21,8 @@
 // Epilogues: bf16 output with optional bias (bf16 [N]) and ReLU / GELU(tanh) (GELU also stores
 // the pre-activation for backward); or fp32 split-K slabs reduced by gemm_splitk_reduce (which
 // can write bf16 straight into the PS flat-gradient buffer).
-#include "common.h"
+#include "mfma_common.h"
+#include "cu_count.h"
 #include "launchers_gemm.h"
 
 #include <algorithm>
@@ -31,16 +32,10 @@ namespace psd {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int BK = 64;
 
-__device__ __forceinline__ int kmaj_off(int row, int kc) {  // byte offset in a [rows][64] tile
-  return row * 128 + ((kc ^ ((row >> 1) & 7)) << 4);
-}
 template <int ROWS>
 __device__ __forceinline__ int mnmaj_off(int k, int col) {  // byte offset in a [64][ROWS] tile
   constexpr int mask = ROWS >= 128 ? 3 : (ROWS >= 64 ? 1 : 0);
@@ -124,12 +119,6 @@ __device__ __forceinline__ bf16x8 frag(const uint8_t* lds, int r0, int ks) {
     s16x4 both[2] = {lo, hi};
     return __builtin_bit_cast(bf16x8, both);
   }
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  // bijective: blocks with equal bid%8 (one XCD under round-robin dispatch) get a contiguous range
-  const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
 }  // namespace
@@ -318,13 +307,6 @@ __device__ __forceinline__ int half_to_tile(int r, int h) {
   return (r / SEG) * (2 * SEG) + h * SEG + (r % SEG);
 }
 
-// Buffer-descriptor LDS-DMA staging: per piece the lane's byte offset = (scalar tile/k origin) +
-// (per-lane part, loop-invariant); rows past the operand's end fall outside the descriptor's range
-// and load zeros (only garbage rows/cols of C, never stored, depend on them), so no per-lane clamp.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
 // per-lane byte offsets of one operand's pieces (piece i of half h), loop-invariant. VR: the valid
 // rows (K-major) / columns (M/N-major) of a half image (BM = 192: 96 of its 128; the rest of the
 // padded image is never read): the pieces / lanes past them get kMasked, an offset past every
@@ -397,51 +379,13 @@ __device__ __forceinline__ i32x8 frag8_f8(const uint8_t* lds, int rb, int lane) 
 }
 
 template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
 __device__ __forceinline__ void wait_lgkm() {
   static_assert(N >= 0, "lgkmcnt");
   if constexpr (N >= 15) asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");  // the counter saturates at 15
   else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_q(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// 4x4 transpose inside a lane quad: in v[r] = C[row r][col L]; out w[c] = C[row L][col c]
-__device__ __forceinline__ void quad_t4(const f32x4 v, int L, float (&w)[4]) {
-  const bool o1 = L & 1, o2 = (L >> 1) & 1;
-  const float r0 = dpp_q<0xB1>(o1 ? v[0] : v[1]);  // quad_perm [1,0,3,2]: partner L^1
-  const float r1 = dpp_q<0xB1>(o1 ? v[2] : v[3]);
-  const float a0 = o1 ? r0 : v[0], a1 = o1 ? v[1] : r0;  // row L&1,     cols (L&~1, L|1)
-  const float b0 = o1 ? r1 : v[2], b1 = o1 ? v[3] : r1;  // row (L&1)+2, same cols
-  const float q0 = dpp_q<0x4E>(o2 ? a0 : b0);            // quad_perm [2,3,0,1]: partner L^2
-  const float q1 = dpp_q<0x4E>(o2 ? a1 : b1);
-  w[0] = o2 ? q0 : a0;
-  w[1] = o2 ? q1 : a1;
-  w[2] = o2 ? b0 : q0;
-  w[3] = o2 ? b1 : q1;
-}
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// lane-group sums for the statistics epilogue: x of lane ^ 16 / lane ^ 32 (the gfx950 half-row /
-// half-wave swaps)
-__device__ __forceinline__ float st_xor16(float x, int lane) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((lane & 16) ? r[0] : r[1]);
-}
-__device__ __forceinline__ float st_xor32(float x, int lane) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((lane & 32) ? r[0] : r[1]);
-}
 
 // grouped tile order inside one XCD's contiguous range: 4 tile-rows share each B panel
 __device__ __forceinline__ void tile_of(int wg, int tiles_m, int tiles_n, int& tm, int& tn) {
@@ -1107,10 +1051,10 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs g) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             float a1 = t1[qn][j][0] + t1[qn][j][1], a2 = t2[qn][j][0] + t2[qn][j][1];
-            a1 += st_xor16(a1, lane);
-            a2 += st_xor16(a2, lane);
-            a1 += st_xor32(a1, lane);
-            a2 += st_xor32(a2, lane);
+            a1 += xor16(a1, lane);
+            a2 += xor16(a2, lane);
+            a1 += xor32(a1, lane);
+            a2 += xor32(a2, lane);
             const float k = shk[qn][j];
             a2 = fmaf(-k, fmaf(-cnt, k, 2.f * a1), a2);
             a1 = fmaf(-cnt, k, a1);
@@ -1311,17 +1255,6 @@ static hipError_t launch_t(const GemmArgs& g, int splits, hipStream_t st) {
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
   hipLaunchKernelGGL((gemm_kernel<TM, TN, AK, BKM, MODE>), dim3(nwg, 1, splits), dim3(256), lds, st, g);
   return hipGetLastError();
-}
-
-static int cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      return 256;
-    return cus;
-  }();
-  return n;
 }
 
 // workgroups of the persistent 8-phase grid: one per CU (the kernel's LDS allows no second)

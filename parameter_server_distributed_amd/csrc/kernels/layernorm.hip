@@ -23,15 +23,6 @@ namespace psd {
 
 namespace {
 
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {  // murmur3 finalizer
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-
 // the lane's E keep flags (common.h drop_keep's mask: 16 bits of one hash per element pair; off is
 // even -- a lane's E columns start at an even index -- so each pair's hash is computed once here)
 template <int E>
@@ -72,7 +63,7 @@ __device__ __forceinline__ void store_e(uint16_t* p, const float v[E]) {
 }
 
 __device__ __forceinline__ uint32_t dropout_key(uint32_t seed, const int64_t* step) {
-  return mix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
+  return drop_mix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
 }
 
 }  // namespace

@@ -1,16 +1,15 @@
 // Tensor glue for the fused residual + dropout + LayerNorm kernels (kernels/layernorm.hip).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
 #include <vector>
 
+#include "glue.h"
 #include "kernels/launchers_ln.h"
 
 namespace psd {
 
 namespace {
-inline hipStream_t ln_stream(const at::Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
 inline const uint16_t* cu16(const at::Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
 inline uint16_t* u16(const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 void check_bf16(const at::Tensor& t, const char* what) {
@@ -42,14 +41,14 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
   a.s = u16(s);
   a.mean = mean.data_ptr<float>();
   a.rstd = rstd.data_ptr<float>();
-  a.step = (step.has_value() && step->defined()) ? step->data_ptr<int64_t>() : nullptr;
+  a.step = given(step) ? step->data_ptr<int64_t>() : nullptr;
   a.rows = rows;
   a.H = (int32_t)H;
   a.eps = (float)eps;
   a.p = (float)p;
   a.seed = (uint32_t)seed;
-  hipError_t e = launch_ln_fwd(a, ln_stream(x));
-  TORCH_CHECK(e == hipSuccess, "psd ln fwd: ", hipGetErrorString(e));
+  hipError_t e = launch_ln_fwd(a, stream_of(x));
+  check_hip(e, "psd ln fwd");
   return {y, s, mean, rstd};
 }
 
@@ -67,11 +66,11 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
   const int64_t rows = s.numel() / H;
   TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows, "psd ln bwd: statistics");
   at::Tensor dx = at::empty_like(s), dh = at::empty_like(s);
-  at::Tensor dgamma = (dgamma_out.has_value() && dgamma_out->defined()) ? *dgamma_out : at::empty({H}, s.options());
-  at::Tensor dbeta = (dbeta_out.has_value() && dbeta_out->defined()) ? *dbeta_out : at::empty({H}, s.options());
+  at::Tensor dgamma = given(dgamma_out) ? *dgamma_out : at::empty({H}, s.options());
+  at::Tensor dbeta = given(dbeta_out) ? *dbeta_out : at::empty({H}, s.options());
   check_bf16(dgamma, "dgamma");
   check_bf16(dbeta, "dbeta");
-  const bool hs = dhsum_out.has_value() && dhsum_out->defined();
+  const bool hs = given(dhsum_out);
   if (hs) {
     check_bf16(*dhsum_out, "dhsum");
     TORCH_CHECK(dhsum_out->numel() == H, "psd ln bwd: dhsum must be [H]");
@@ -89,13 +88,13 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
   a.dbeta = u16(dbeta);
   a.part = part.data_ptr<float>();
   a.dhsum = hs ? u16(*dhsum_out) : nullptr;
-  a.step = (step.has_value() && step->defined()) ? step->data_ptr<int64_t>() : nullptr;
+  a.step = given(step) ? step->data_ptr<int64_t>() : nullptr;
   a.rows = rows;
   a.H = (int32_t)H;
   a.p = (float)p;
   a.seed = (uint32_t)seed;
-  hipError_t e = launch_ln_bwd(a, ln_stream(s));
-  TORCH_CHECK(e == hipSuccess, "psd ln bwd: ", hipGetErrorString(e));
+  hipError_t e = launch_ln_bwd(a, stream_of(s));
+  check_hip(e, "psd ln bwd");
   return {dx, dh, dgamma, dbeta};
 }
 
@@ -124,7 +123,7 @@ EmbLnArgs emb_args(const at::Tensor& ids, const at::Tensor& types, const at::Ten
   a.P = cu16(P);
   a.T = cu16(T);
   a.gamma = cu16(gamma);
-  a.step = (step.has_value() && step->defined()) ? step->data_ptr<int64_t>() : nullptr;
+  a.step = given(step) ? step->data_ptr<int64_t>() : nullptr;
   a.rows = ids.numel();
   a.V = W.size(0);
   a.S = (int32_t)S;
@@ -152,8 +151,8 @@ std::vector<at::Tensor> emb_ln_fwd(const at::Tensor& ids, const at::Tensor& type
   a.mean = mean.data_ptr<float>();
   a.rstd = rstd.data_ptr<float>();
   a.eps = (float)eps;
-  hipError_t e = launch_emb_ln_fwd(a, ln_stream(W));
-  TORCH_CHECK(e == hipSuccess, "psd emb ln fwd: ", hipGetErrorString(e));
+  hipError_t e = launch_emb_ln_fwd(a, stream_of(W));
+  check_hip(e, "psd emb ln fwd");
   return {y, mean, rstd};
 }
 
@@ -172,15 +171,15 @@ std::vector<at::Tensor> emb_ln_bwd(const at::Tensor& dy_in, const at::Tensor& id
   const c10::DeviceGuard g(W.device());
   const int64_t H = a.H;
   at::Tensor dx = at::empty({a.rows, H}, W.options());
-  at::Tensor dgamma = (dgamma_out.has_value() && dgamma_out->defined()) ? *dgamma_out : at::empty({H}, W.options());
-  at::Tensor dbeta = (dbeta_out.has_value() && dbeta_out->defined()) ? *dbeta_out : at::empty({H}, W.options());
+  at::Tensor dgamma = given(dgamma_out) ? *dgamma_out : at::empty({H}, W.options());
+  at::Tensor dbeta = given(dbeta_out) ? *dbeta_out : at::empty({H}, W.options());
   check_bf16(dgamma, "dgamma");
   check_bf16(dbeta, "dbeta");
   TORCH_CHECK(dgamma.numel() == H && dbeta.numel() == H, "psd emb ln bwd: dgamma / dbeta");
   // the type table's gradient rides in the same pass for <= 2 types (else: none here, the caller sums)
   at::Tensor dT;
   if (a.NT <= 2) {
-    dT = (dT_out.has_value() && dT_out->defined()) ? *dT_out : at::empty({(int64_t)a.NT, H}, W.options());
+    dT = given(dT_out) ? *dT_out : at::empty({(int64_t)a.NT, H}, W.options());
     check_bf16(dT, "dT");
     TORCH_CHECK(dT.numel() == a.NT * H, "psd emb ln bwd: dT");
   }
@@ -194,8 +193,8 @@ std::vector<at::Tensor> emb_ln_bwd(const at::Tensor& dy_in, const at::Tensor& id
   a.dbeta = u16(dbeta);
   a.dT = dT.defined() ? u16(dT) : nullptr;
   a.part = part.data_ptr<float>();
-  hipError_t e = launch_emb_ln_bwd(a, ln_stream(W));
-  TORCH_CHECK(e == hipSuccess, "psd emb ln bwd: ", hipGetErrorString(e));
+  hipError_t e = launch_emb_ln_bwd(a, stream_of(W));
+  check_hip(e, "psd emb ln bwd");
   return {dx, dgamma, dbeta, dT.defined() ? dT : at::Tensor()};
 }
 

@@ -8,11 +8,11 @@
 
 #include <ATen/Parallel.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
 #include <cmath>
 #include <cstring>
 
+#include "glue.h"
 #include "kernels/launchers.h"
 #include "kernels/launchers_clip.h"
 #include "kernels/launchers_optim_lw.h"
@@ -22,10 +22,6 @@
 namespace psd {
 
 namespace {
-
-inline hipStream_t cur_stream(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
 
 inline void hip_check(hipError_t e, const char* what) {
   TORCH_CHECK(e == hipSuccess, "psd: ", what, " failed: ", hipGetErrorString(e));
@@ -109,7 +105,7 @@ SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at
   }
   // per-source scales: none, or one fp32 device scalar for every source
   size_t set = 0;
-  for (auto& t : scales) set += t.has_value() && t->defined();
+  for (auto& t : scales) set += given(t);
   if (set == 0) return s;
   TORCH_CHECK(scales.size() == srcs.size() && set == srcs.size(),
               "psd: per-source scales must be given for every gradient source or for none (", set, " of ",
@@ -164,7 +160,7 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
                 "psd: optimizer needs fp32 state2 like master");
     a.s2 = state2->data_ptr<float>();
   }
-  if (shadow.has_value() && shadow->defined()) {
+  if (given(shadow)) {
     TORCH_CHECK(shadow->scalar_type() == at::kBFloat16 && shadow->numel() == n && shadow->is_contiguous() &&
                     shadow->device() == master.device(),
                 "psd: shadow must be contiguous bf16 like master");
@@ -221,7 +217,7 @@ void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::
 
   if (master.is_cuda()) {
     const c10::DeviceGuard g(master.device());
-    hip_check(launch_fused_apply(h, dyn_ptr(dyn), master.data_ptr<float>(), src, s1, s2, sh, n, cur_stream(master),
+    hip_check(launch_fused_apply(h, dyn_ptr(dyn), master.data_ptr<float>(), src, s1, s2, sh, n, stream_of(master),
                                  (int)grid_cap),
               "fused_apply");
     return;
@@ -342,7 +338,7 @@ void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c1
     TORCH_CHECK(gpu != nullptr, "psd: the gfx950 layer-table kernels are not linked into this build; only CPU tensors "
                                 "can take a layer table here");
     const c10::DeviceGuard g(master.device());
-    hipStream_t st = cur_stream(master);
+    hipStream_t st = stream_of(master);
     if (layerwise) {
       hip_check(gpu->norms(h, dyn_ptr(dyn), p, a.src, a.s1, a.s2, t, st, (int)grid_cap), "lw_norms");
       hip_check(gpu->finalize(h, t, st, (int)grid_cap), "lw_finalize");
@@ -436,7 +432,7 @@ void optim_advance_(at::Tensor dyn, double beta1, double beta2) {
   OptimDyn* d = dyn_ptr(dyn);
   if (dyn.is_cuda()) {
     const c10::DeviceGuard g(dyn.device());
-    hip_check(launch_optim_advance(d, (float)beta1, (float)beta2, cur_stream(dyn)), "optim_advance");
+    hip_check(launch_optim_advance(d, (float)beta1, (float)beta2, stream_of(dyn)), "optim_advance");
     return;
   }
   d->step += 1;
@@ -454,7 +450,7 @@ void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double s
     const c10::DeviceGuard g(out.device());
     check_aligned(out, "out");
     for (auto& t : srcs) check_aligned(t, "src");
-    hip_check(launch_multi_reduce(s, out.data_ptr(), od, (float)scale, n, cur_stream(out)), "multi_reduce");
+    hip_check(launch_multi_reduce(s, out.data_ptr(), od, (float)scale, n, stream_of(out)), "multi_reduce");
     return;
   }
   at::parallel_for(0, n, 1 << 14, [&](int64_t b, int64_t e) {
@@ -484,7 +480,7 @@ void grad_clip_coef_(const at::Tensor& flat, double clip_norm, at::Tensor out, a
   if (flat.is_cuda()) {
     const c10::DeviceGuard g(flat.device());
     check_aligned(flat, "flat gradient");
-    hipStream_t st = cur_stream(flat);
+    hipStream_t st = stream_of(flat);
     hip_check(launch_sumsq_partials(flat.data_ptr(), dt, n, partials.data_ptr<float>(), st, (int)grid_cap), "sumsq_partials");
     hip_check(launch_clip_finalize(partials.data_ptr<float>(), C, (float)clip_norm, out.data_ptr<float>(), st),
               "clip_finalize");
@@ -555,7 +551,7 @@ void xfer_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& d
   L.blocks_per_seg = (int32_t)blocks_per_seg;
   L.nt_store = nt_store ? 1 : 0;
   const c10::DeviceGuard g(srcs[0].device());
-  hip_check(launch_xfer(L, cur_stream(srcs[0])), "launch_xfer");
+  hip_check(launch_xfer(L, stream_of(srcs[0])), "launch_xfer");
 }
 
 void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts) {
@@ -598,7 +594,7 @@ void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tenso
     uint8_t* tp = table.data_ptr<uint8_t>();
     hip_check(launch_pack_cast(reinterpret_cast<const PackSeg*>(tp), reinterpret_cast<const int32_t*>(tp + seg_bytes + off_bytes),
                                reinterpret_cast<const int64_t*>(tp + seg_bytes), (int64_t)cseg.size(), sd, dd,
-                               cur_stream(srcs[0])),
+                               stream_of(srcs[0])),
               "pack_cast");
     return;
   }
@@ -622,7 +618,7 @@ void amax_(const at::Tensor& x, at::Tensor amax_out) {
   if (x.is_cuda()) {
     const c10::DeviceGuard g(x.device());
     if (x.numel() >= 8) check_aligned(x, "x");  // 16-byte vector loads
-    hip_check(launch_amax(x.data_ptr(), dt_of(x), x.numel(), amax_out.data_ptr<float>(), cur_stream(x)), "amax");
+    hip_check(launch_amax(x.data_ptr(), dt_of(x), x.numel(), amax_out.data_ptr<float>(), stream_of(x)), "amax");
     return;
   }
   float m = amax_out.data_ptr<float>()[0];
@@ -644,7 +640,7 @@ void quant_fp8_(const at::Tensor& x, const at::Tensor& amax, double fp8_max, at:
       TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 7u) == 0, "psd: fp8 out must be 8-byte aligned");
     }
     hip_check(launch_quant_fp8(x.data_ptr(), dt_of(x), x.numel(), amax.data_ptr<float>(), (float)fp8_max,
-                               reinterpret_cast<uint8_t*>(out.data_ptr()), scale_inv.data_ptr<float>(), cur_stream(x),
+                               reinterpret_cast<uint8_t*>(out.data_ptr()), scale_inv.data_ptr<float>(), stream_of(x),
                                e5 ? 1 : 0),
               "quant_fp8");
     return;
@@ -670,7 +666,7 @@ void quant_fp8_jit_(const at::Tensor& x, at::Tensor out, at::Tensor scale_inv) {
   }
   at::Tensor part = at::empty({1024}, x.options().dtype(at::kFloat));
   hip_check(launch_quant_fp8_jit(x.data_ptr(), dt_of(x), x.numel(), part.data_ptr<float>(), e5 ? 57344.f : 448.f,
-                                 reinterpret_cast<uint8_t*>(out.data_ptr()), scale_inv.data_ptr<float>(), cur_stream(x),
+                                 reinterpret_cast<uint8_t*>(out.data_ptr()), scale_inv.data_ptr<float>(), stream_of(x),
                                  e5 ? 1 : 0),
             "quant_fp8_jit");
 }
@@ -691,7 +687,7 @@ void quant_fp8_delayed_(const at::Tensor& x, at::Tensor out, at::Tensor scale_in
   }
   hip_check(launch_quant_fp8_delayed(x.data_ptr(), dt_of(x), x.numel(), hist.data_ptr<float>(), e5 ? 57344.f : 448.f,
                                      (float)margin, reinterpret_cast<uint8_t*>(out.data_ptr()),
-                                     scale_inv.data_ptr<float>(), cur_stream(x), e5 ? 1 : 0),
+                                     scale_inv.data_ptr<float>(), stream_of(x), e5 ? 1 : 0),
             "quant_fp8_delayed");
 }
 
@@ -700,7 +696,7 @@ void dequant_fp8_(const at::Tensor& x, const at::Tensor& scale_inv, at::Tensor o
   if (x.is_cuda()) {
     const c10::DeviceGuard g(x.device());
     hip_check(launch_dequant_fp8(reinterpret_cast<const uint8_t*>(x.data_ptr()), x.numel(), scale_inv.data_ptr<float>(),
-                                 out.data_ptr(), dt_of(out), cur_stream(x)),
+                                 out.data_ptr(), dt_of(out), stream_of(x)),
               "dequant_fp8");
     return;
   }
@@ -721,7 +717,7 @@ void quant_mx_(const at::Tensor& x, at::Tensor out, at::Tensor scales) {
   check_aligned(x, "x");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 7u) == 0, "psd: fp8 out must be 8-byte aligned");
   hip_check(launch_quant_mx(x.data_ptr(), dt_of(x), x.numel(), e5 ? 1 : 0, reinterpret_cast<uint8_t*>(out.data_ptr()),
-                            scales.data_ptr<uint8_t>(), cur_stream(x)),
+                            scales.data_ptr<uint8_t>(), stream_of(x)),
             "quant_mx");
 }
 
@@ -736,7 +732,7 @@ void dequant_mx_(const at::Tensor& q, const at::Tensor& scales, at::Tensor out) 
   TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 7u) == 0, "psd: fp8 q must be 8-byte aligned");
   check_aligned(out, "out");
   hip_check(launch_dequant_mx(reinterpret_cast<const uint8_t*>(q.data_ptr()), scales.data_ptr<uint8_t>(), q.numel(),
-                              out.data_ptr(), dt_of(out), cur_stream(q)),
+                              out.data_ptr(), dt_of(out), stream_of(q)),
             "dequant_mx");
 }
 

@@ -101,6 +101,10 @@ int64_t gemm_(const at::Tensor& A, const at::Tensor& B, bool a_kmajor, bool b_km
               c10::optional<at::Tensor> part, c10::optional<at::Tensor> shift);
 // statistics partial rows to allocate for a gemm_ / gemm_fp8_ / conv_fwd_ with part (any tile height)
 int64_t gemm_stats_rows_(int64_t M);
+// (glue-internal, gemm_ops.cpp) checks part / shift against out and points a launch's statistics fields at them
+struct GemmArgs;
+void set_stats(GemmArgs& a, const c10::optional<at::Tensor>& part, const c10::optional<at::Tensor>& shift,
+               const at::Tensor& out, int* rows);
 // out[N, M] = B A^T (+bias[M])(act 0-2, aux = pre-activation) on 192 x 256 tiles stored transposed
 // (A [M, K], B [N, K] K-major: Y = X W^T + b with A = W, B = X); False when the shape is outside the
 // kernel's contract (nothing launched)

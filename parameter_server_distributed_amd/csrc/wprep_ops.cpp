@@ -4,11 +4,11 @@
 #include <ATen/ATen.h>
 
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 #include <cstring>
 #include <tuple>
 #include <vector>
 
+#include "glue.h"
 #include "kernels/launchers_wprep.h"
 #include "ops.h"
 
@@ -36,8 +36,7 @@ std::tuple<at::Tensor, int64_t> wprep_table(const std::vector<at::Tensor>& srcs,
                 "psd wprep: tap subset outside the kernel window");
     TORCH_CHECK(d.is_cuda() && d.scalar_type() == at::kBFloat16 && d.is_contiguous() &&
                     d.numel() == (int64_t)ci * Rp * Sp * co && d.device() == s.device() &&
-                    (reinterpret_cast<uintptr_t>(d.data_ptr()) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(s.data_ptr()) & 15) == 0,
+                    aligned16(d) && aligned16(s),
                 "psd wprep: dst must be a contiguous 16-B aligned bf16 [ci, Rp * Sp * co] on the src's device");
     WprepJob& j = jobs[i];
     j.src = reinterpret_cast<const uint16_t*>(s.data_ptr());
@@ -59,9 +58,8 @@ void wprep_run(const at::Tensor& table, int64_t tiles) {
               "psd wprep: table must come from wprep_table");
   const c10::DeviceGuard g(table.device());
   const int njobs = (int)(table.numel() / sizeof(WprepJob));
-  hipError_t e = launch_wprep(reinterpret_cast<const WprepJob*>(table.data_ptr()), njobs, (int)tiles,
-                              c10::hip::getCurrentHIPStream(table.device().index()).stream());
-  TORCH_CHECK(e == hipSuccess, "psd wprep: ", hipGetErrorString(e));
+  hipError_t e = launch_wprep(reinterpret_cast<const WprepJob*>(table.data_ptr()), njobs, (int)tiles, stream_of(table));
+  check_hip(e, "psd wprep");
 }
 
 }  // namespace psd

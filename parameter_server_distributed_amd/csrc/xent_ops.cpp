@@ -1,17 +1,16 @@
 // Tensor glue for the fused softmax cross-entropy (kernels/xent.hip).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 
+#include "glue.h"
 #include "kernels/launchers_xent.h"
 
 namespace psd {
 
 namespace {
-inline hipStream_t stream_of(const at::Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
 void check_logits(const at::Tensor& x, const at::Tensor& labels) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.scalar_type() == at::kBFloat16 && x.stride(1) == 1 &&
-                  x.stride(0) % 8 == 0 && (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+                  x.stride(0) % 8 == 0 && aligned16(x),
               "psd xent: logits must be a 2-D bf16 device tensor with 16-B aligned rows");
   TORCH_CHECK(labels.is_cuda() && labels.dim() == 1 && labels.scalar_type() == at::kLong && labels.is_contiguous() &&
                   labels.size(0) == x.size(0),
@@ -28,7 +27,7 @@ std::vector<at::Tensor> xent_fwd(const at::Tensor& x, const at::Tensor& labels) 
   at::Tensor lse = at::empty({rows}, f32), loss_row = at::empty({rows}, f32);
   hipError_t e = launch_xent_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()), labels.data_ptr<int64_t>(), rows, V,
                                  x.stride(0), lse.data_ptr<float>(), loss_row.data_ptr<float>(), stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd xent fwd: ", hipGetErrorString(e));
+  check_hip(e, "psd xent fwd");
   return {loss_row, lse};
 }
 
@@ -44,7 +43,7 @@ at::Tensor xent_bwd(const at::Tensor& x, const at::Tensor& labels, const at::Ten
   hipError_t e = launch_xent_bwd(reinterpret_cast<const uint16_t*>(x.data_ptr()), labels.data_ptr<int64_t>(),
                                  lse.data_ptr<float>(), scale.data_ptr<float>(), rows, V, x.stride(0),
                                  reinterpret_cast<uint16_t*>(dx.data_ptr()), stream_of(x));
-  TORCH_CHECK(e == hipSuccess, "psd xent bwd: ", hipGetErrorString(e));
+  check_hip(e, "psd xent bwd");
   return dx;
 }
 
