@@ -169,10 +169,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("counter") = py::none());
   m.def("stem_wgrad", &stem_wgrad);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
-        py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0);
+        py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("heads"),
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
-        py::arg("lens") = py::none(), py::arg("grid_cap") = 0);
+        py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false);
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none());
   m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("s"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("p"),

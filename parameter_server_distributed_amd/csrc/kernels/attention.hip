@@ -57,12 +57,19 @@ __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, in
 // blocks j < nb only, with the scores of keys >= L at -inf (probability exactly 0). Every skip is
 // wave-uniform and every wave reaches both barriers. Without lengths (VARLEN false) every such test
 // is a compile-time constant and the kernel is the full-length one.
+// CAUSAL (a.causal; always with VARLEN, L = S when a.lens is null): wave w owns query block w and walks
+// key blocks j <= w only (all of them < nb, since a wave that computes has 32 w < L); in the diagonal
+// block j == w the scores of keys > q go to -inf by the same select as keys >= L. Key 32 w is visible
+// to every query of the block, so the row max is finite. Future rows of the diagonal block are staged
+// and multiplied (finite inputs give exact-zero probabilities); without a.causal every such test is a
+// compile-time constant.
 // (The length-aware copy asks for two waves per SIMD: left alone the compiler takes 233 + 80 registers
 // at NW = 4, one workgroup per CU instead of two; a minimum of 1 is the default and leaves the
 // full-length copy as it was.)
-template <int NW, bool VARLEN>
+template <int NW, bool VARLEN, bool CAUSAL>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VARLEN ? 2 : 1)))
 void attn_fwd_kernel(AttnArgs a) {
+  static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   constexpr int S = 32 * NW;
   constexpr int NT = 64 * NW;
   constexpr int CH = S * 8 / NT;  // 16-B chunks per lane per tile (= 4)
@@ -83,7 +90,7 @@ void attn_fwd_kernel(AttnArgs a) {
   auto fetch = [&](int bh) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
-    const int Lf = item_len<VARLEN>(a, b, S);
+    const int Lf = item_len<VARLEN, CAUSAL>(a, b, S);
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = threadIdx.x + i * NT, r = c >> 3, ch = c & 7;
@@ -106,7 +113,7 @@ void attn_fwd_kernel(AttnArgs a) {
 
   for (int bh = blockIdx.x; bh < nitems; bh += gridDim.x) {
     const int b = bh / a.H, h = bh % a.H;
-    const int L = item_len<VARLEN>(a, b, S);
+    const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int nb = (L + 31) >> 5;  // key / query blocks with a valid row
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
@@ -125,11 +132,17 @@ void attn_fwd_kernel(AttnArgs a) {
       af32x16 sc[NW];  // S^T tiles: lane owns query q, keys 32j + acc_row(i)
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (VARLEN && j >= nb) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
         sc[j] = zero16();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
-        if constexpr (VARLEN) {
+        if constexpr (CAUSAL) {
+          if (j == w) {  // the diagonal block (the partial key block is this one or is not walked)
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+              if (32 * j + acc_row(i, hh) > q || 32 * j + acc_row(i, hh) >= L) sc[j][i] = -INFINITY;
+          }
+        } else if constexpr (VARLEN) {
           if (j == nb - 1) {  // the partial key block: keys >= L leave the max and the sum
 #pragma unroll
             for (int i = 0; i < 16; ++i)
@@ -140,7 +153,7 @@ void attn_fwd_kernel(AttnArgs a) {
       float m = -INFINITY;
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (VARLEN && j >= nb) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
 #pragma unroll
         for (int i = 0; i < 16; ++i) m = fmaxf(m, sc[j][i]);
       }
@@ -148,7 +161,7 @@ void attn_fwd_kernel(AttnArgs a) {
       float l = 0.f;
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (VARLEN && j >= nb) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           sc[j][i] = exp2f((sc[j][i] - m) * sl);
@@ -164,7 +177,7 @@ void attn_fwd_kernel(AttnArgs a) {
       af32x16 ot[2] = {zero16(), zero16()};
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (VARLEN && j >= nb) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
 #pragma unroll
         for (int ks2 = 0; ks2 < 2; ++ks2) {
           float v[8];
@@ -222,8 +235,16 @@ void attn_fwd_kernel(AttnArgs a) {
 // query blocks < nb only, with zeros at masked keys and padded queries, and phases 2 and 3 read
 // exactly that region (chunks < 2 nb of blocks < nb); what the previous item left outside it is
 // never read. Blocks >= nb store zero dK, dV / dQ and zero column sums. All skips are wave-uniform.
-template <int NW, bool VARLEN>
+//
+// CAUSAL (always with VARLEN; L = S when a.lens is null): phase 1 writes Pd and dS for key block w
+// against query blocks w <= t < nb only, with zeros at keys > q inside the diagonal block t == w; the
+// blocks above the diagonal are written by no item. Phase 2 (key block w) reduces over the query
+// chunks 2 w <= ks < 2 nb, i.e. query blocks w .. nb - 1 of key block w, and phase 3 (query block w)
+// over the key chunks ks < 2 (w + 1) <= 2 nb, i.e. key blocks 0 .. w of query block w: both inside
+// what phase 1 of this item wrote.
+template <int NW, bool VARLEN, bool CAUSAL>
 __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
+  static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   constexpr int S = 32 * NW, LDP = S + 8;
   constexpr int NT = 128 * NW;
   constexpr int CH = S * 8 / NT;  // 16-B chunks per lane per tile (= 2)
@@ -255,7 +276,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     const int64_t ob = (int64_t)b * S * HD + h * D;
-    const int Lf = item_len<VARLEN>(a, b, S);
+    const int Lf = item_len<VARLEN, CAUSAL>(a, b, S);
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = threadIdx.x + i * NT, r = c >> 3, ch = c & 7;
@@ -276,7 +297,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
 
   for (int bh = blockIdx.x; bh < nitems; bh += gridDim.x) {
     const int b = bh / a.H, h = bh % a.H;
-    const int L = item_len<VARLEN>(a, b, S);
+    const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int nb = (L + 31) >> 5;  // key / query blocks with a valid row
     // the prefetched item -> LDS; D[q] = sum_d dO[q, d] O[q, d] (8 lanes per row)
 #pragma unroll
@@ -314,7 +335,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       }
 #pragma unroll
       for (int t = sub; t < NW; t += 2) {
-        if (VARLEN && t >= nb) continue;
+        if ((VARLEN && t >= nb) || (CAUSAL && t < w)) continue;
         af32x16 st = zero16(), dpt = zero16();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -346,6 +367,9 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
             if constexpr (VARLEN) {  // masked key or padded query: exact zeros into Pd and dS
               if (q >= L || k0 + 8 * g + 4 * hh + e >= L) pv[e] = dv[e] = 0.f;
             }
+            if constexpr (CAUSAL) {  // a future key of the diagonal block (t > w has every key <= q)
+              if (k0 + 8 * g + 4 * hh + e > q) pv[e] = dv[e] = 0.f;
+            }
           }
           const int off = q * LDP * 2 + (k0 + 8 * g + 4 * hh) * 2;
           *reinterpret_cast<uint2*>(Pd + off) = make_uint2(pack_bf16x2_rne(pv[0], pv[1]), pack_bf16x2_rne(pv[2], pv[3]));
@@ -364,6 +388,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int ks = 0; ks < S / 16; ++ks) {
         if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a key block past L keeps its zeros
+        if (CAUSAL && ks < 2 * w) continue;              // queries before the key block see none of its keys
         dv = mfma(trfrag(Pd, LDP * 2, 16 * ks, k0), trfrag(dOs, LDT * 2, 16 * ks, 32 * dt), dv);
         dk = mfma(trfrag(dS, LDP * 2, 16 * ks, k0), trfrag(Qs, LDT * 2, 16 * ks, 32 * dt), dk);
       }
@@ -394,6 +419,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int ks = 0; ks < S / 16; ++ks) {
         if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a query block past L keeps its zeros
+        if (CAUSAL && ks >= 2 * (w + 1)) break;          // keys after the query block
         dq = mfma(rowfrag(dS, LDP * 2, q0, 16 * ks), trfrag(Ks, LDT * 2, 16 * ks, 32 * dt), dq);
       }
       const int d = 32 * dt + (lane & 31);
@@ -428,52 +454,59 @@ bool attn_supported(int S, int head_dim) { return head_dim == D && S >= 32 && S 
 static int fwd_lds(int S) { return 2 * S * LDT * 2; }
 static int bwd_lds(int S) { return 4 * S * LDT * 2 + 2 * S * (S + 8) * 2 + 2 * S * 4 + (S / 32) * 3 * 64 * 4; }
 
-template <int NW, bool VARLEN>
+template <int NW, bool VARLEN, bool CAUSAL>
 static hipError_t launch_fwd_t(const AttnArgs& a, hipStream_t st) {
   const int lds = fwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items bh, bh + grid, ...
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN>), 64 * NW,
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL>), 64 * NW,
                                                    lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
   int grid = std::min(a.B * a.H, per_cu * cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
-  hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN>), dim3(grid), dim3(64 * NW), lds, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN, CAUSAL>), dim3(grid), dim3(64 * NW), lds, st, a);
   return hipGetLastError();
 }
-template <int NW, bool VARLEN>
+template <int NW, bool VARLEN, bool CAUSAL>
 static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
   const int lds = bwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW, VARLEN>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW, VARLEN, CAUSAL>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: one workgroup per CU (the LDS image admits one), each walks items bh, bh + grid, ...
   int grid = std::min(a.B * a.H, cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
-  hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN>), dim3(grid), dim3(128 * NW), lds, st, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN, CAUSAL>), dim3(grid), dim3(128 * NW), lds, st, a);
   return hipGetLastError();
 }
+
+// (VARLEN, CAUSAL): full length, lengths, causal (with or without lengths); without a.causal the choice
+// is the one made before the causal copies existed
+#define PSD_ATTN_PICK(fn, nw) \
+  (a.causal ? fn<nw, true, true>(a, st) : a.lens ? fn<nw, true, false>(a, st) : fn<nw, false, false>(a, st))
 
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
   switch (a.S / 32) {
-    case 1: return a.lens ? launch_fwd_t<1, true>(a, st) : launch_fwd_t<1, false>(a, st);
-    case 2: return a.lens ? launch_fwd_t<2, true>(a, st) : launch_fwd_t<2, false>(a, st);
-    case 3: return a.lens ? launch_fwd_t<3, true>(a, st) : launch_fwd_t<3, false>(a, st);
-    default: return a.lens ? launch_fwd_t<4, true>(a, st) : launch_fwd_t<4, false>(a, st);
+    case 1: return PSD_ATTN_PICK(launch_fwd_t, 1);
+    case 2: return PSD_ATTN_PICK(launch_fwd_t, 2);
+    case 3: return PSD_ATTN_PICK(launch_fwd_t, 3);
+    default: return PSD_ATTN_PICK(launch_fwd_t, 4);
   }
 }
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
   switch (a.S / 32) {
-    case 1: return a.lens ? launch_bwd_t<1, true>(a, st) : launch_bwd_t<1, false>(a, st);
-    case 2: return a.lens ? launch_bwd_t<2, true>(a, st) : launch_bwd_t<2, false>(a, st);
-    case 3: return a.lens ? launch_bwd_t<3, true>(a, st) : launch_bwd_t<3, false>(a, st);
-    default: return a.lens ? launch_bwd_t<4, true>(a, st) : launch_bwd_t<4, false>(a, st);
+    case 1: return PSD_ATTN_PICK(launch_bwd_t, 1);
+    case 2: return PSD_ATTN_PICK(launch_bwd_t, 2);
+    case 3: return PSD_ATTN_PICK(launch_bwd_t, 3);
+    default: return PSD_ATTN_PICK(launch_bwd_t, 4);
   }
 }
+
+#undef PSD_ATTN_PICK
 
 }  // namespace psd

@@ -31,6 +31,21 @@
 // Dropout keeps (b, h, q, key) by drop_keep over ((b*H + h)*S + q)*S + key with attn_key(seed, step) in
 // all three kernels: one hash per key pair where a lane holds both keys of a pair (forward, dQ), one
 // per element where the pair sits in two lanes (dK/dV) -- the same bits either way.
+// Causal (CAUSAL instantiations, a.causal; always length-aware, L = S when a.lens is null): query q sees
+// keys <= q and < L. Forward and dQ walk key chunks c < min(nck, 2 (qt + 1)) of query tile qt; a wave
+// (32 queries from q0) computes only in chunks with 64 c <= q0, skips the 32-key block that starts
+// past q0 and masks by element in the block that starts at q0 (blocks and q0 are multiples of 32, so
+// a block lies before, on or after the wave's queries). dK/dV starts its query-chunk walk at chunk
+// 2 kt, skips the 32-query block that ends before the wave's keys and writes exact zeros where
+// query < key in the block on them. Every skip is wave-uniform and every wave reaches every barrier.
+// Future rows inside the chunks walked are staged and multiplied: finite values there change nothing.
+// Item map of the causal copies: a query tile qt costs about (qt + 1) of a key tile's chunks, and with
+// items numbered (bh, tile) and a grid that is a multiple of the tile count every workgroup met the same
+// tile index in all its items, so the workgroups with the last tile ran as long as the full kernel
+// (measured: causal no faster than bidirectional at S = 256, 512). The causal copies number the items
+// tile-major, heaviest first (qt descending for forward / dQ, kt ascending for dK/dV): a workgroup's
+// items it, it + grid, .. then spread over the tiles. Only the item-to-workgroup map changes: every
+// item is still computed whole by one workgroup, so no result depends on it.
 // Bias hand-over: bpart[(b * ceil(S/128) + tile)][3*H*64] gets the fp32 column sums of the item's dQ
 // (dQ pass) and dK, dV (dK/dV pass), summed in a fixed order; launch_colsum_final reduces the rows.
 #include <algorithm>
@@ -122,7 +137,7 @@ __device__ __forceinline__ float wave_colsum(float* red, const af32x16 (&t)[2]) 
 }  // namespace
 
 // Forward. Persistent over items (bh, query tile); LDS: K and V chunk tiles, two buffers.
-template <bool VARLEN>
+template <bool VARLEN, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
@@ -135,13 +150,18 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
   const bool drop = a.thresh != 0u;
 
   for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const int bh = it / nqt, qt = it - bh * nqt;
+    int bh = it / nqt, qt = it - bh * nqt;
+    if constexpr (CAUSAL) {  // tile qt costs ~(qt + 1) chunks: the heavy tiles first, see item map above
+      bh = it % (a.B * a.H);
+      qt = nqt - 1 - it / (a.B * a.H);
+    }
     const int b = bh / a.H, h = bh - b * a.H;
-    const int L = item_len<VARLEN>(a, b, S);
+    const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int q0 = 128 * qt + 32 * w, q = q0 + (lane & 31);
     const bool live = q0 < L;  // this wave has a valid query (wave-uniform)
     const bool vq = q < L;
-    const int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;  // key chunks with a valid key; none for a padded tile
+    int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;  // key chunks with a valid key; none for a padded tile
+    if (CAUSAL) nck = min(nck, 2 * (qt + 1));        // and with a key <= the tile's last query
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
 
     abf16x8 qf[4];
@@ -166,24 +186,30 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         fetch_rows(pk, base + HD, qkv_rs, KC * (c + 1), L);
         fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
       }
-      if (live) {
+      // causal: a wave computes in chunks with 64 c <= q0 only and leaves m, l, ot alone in the others
+      if (live && (!CAUSAL || KC * c <= q0)) {
         const int kb0 = KC * c;
         af32x16 sc[2];  // S^T tiles: lane owns query q, keys kb0 + 32 j + acc_row(i)
         float cm = -INFINITY;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
+          if (CAUSAL && kb0 + 32 * j > q0) continue;  // every key of the block is past the wave's queries
+          // end of the keys this lane's query sees: L, and q + 1 in the block on the diagonal
+          const int kend = CAUSAL && kb0 + 32 * j == q0 ? min(L, q + 1) : L;
           sc[j] = zero16();
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            if (VARLEN && kb0 + 32 * j + acc_row(i, hh) >= L) sc[j][i] = -INFINITY;  // leaves the max and the sum
+            if (VARLEN && kb0 + 32 * j + acc_row(i, hh) >= kend) sc[j][i] = -INFINITY;  // leaves the max and the sum
             cm = fmaxf(cm, sc[j][i]);
           }
         }
         cm = fmaxf(cm, __shfl_xor(cm, 32));
-        // key kb0 is valid in every chunk walked, so cm is finite; m = -inf on the first chunk gives alpha 0
+        // key kb0 is valid in every chunk walked, so cm is finite; m = -inf on the first chunk gives alpha 0.
+        // Causal: per wave, a chunk is computed only when kb0 = 64 c <= q0 (q0 a multiple of 32, 64 c of 64),
+        // and then key kb0 <= q0 <= q is visible to every query of the wave and kb0 <= q0 < L: cm stays finite
         const float mn = fmaxf(m, cm);
         const float alpha = aexp2((m - mn) * sl);
         m = mn;
@@ -195,6 +221,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
+          if (CAUSAL && kb0 + 32 * j > q0) continue;
 #pragma unroll
           for (int ks2 = 0; ks2 < 2; ++ks2) {
             float v[8];
@@ -238,7 +265,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
 }
 
 // Backward, dQ pass: the forward's item and orientation; also writes D = rowsum(dO . O) to dsum.
-template <bool VARLEN>
+template <bool VARLEN, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __restrict__ dsum) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   float* red = reinterpret_cast<float*>(smem);
@@ -253,13 +280,18 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
   const bool drop = a.thresh != 0u;
 
   for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const int bh = it / nqt, qt = it - bh * nqt;
+    int bh = it / nqt, qt = it - bh * nqt;
+    if constexpr (CAUSAL) {  // tile qt costs ~(qt + 1) chunks: the heavy tiles first, see item map above
+      bh = it % (a.B * a.H);
+      qt = nqt - 1 - it / (a.B * a.H);
+    }
     const int b = bh / a.H, h = bh - b * a.H;
-    const int L = item_len<VARLEN>(a, b, S);
+    const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int q0 = 128 * qt + 32 * w, q = q0 + (lane & 31);
     const bool live = q0 < L;
     const bool vq = q < L;
-    const int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;
+    int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;
+    if (CAUSAL) nck = min(nck, 2 * (qt + 1));
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     const int64_t orow = ((int64_t)b * S + q) * HD + h * D;
 
@@ -299,11 +331,13 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
         fetch_rows(pk, base + HD, qkv_rs, KC * (c + 1), L);
         fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
       }
-      if (live) {
+      if (live && (!CAUSAL || KC * c <= q0)) {
         const int kb0 = KC * c;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
+          if (CAUSAL && kb0 + 32 * j > q0) continue;  // every key of the block is past the wave's queries
+          const int kend = CAUSAL && kb0 + 32 * j == q0 ? min(L, q + 1) : L;  // as in the forward
           af32x16 st = zero16(), dpt = zero16();
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
@@ -327,7 +361,7 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
               if (drop) dp = kp[e] ? dp * a.rescale : 0.f;
               v[e] = p * (dp - Dq);
               if constexpr (VARLEN) {  // masked key or padded query: exact zero
-                if (!vq || kb0 + 32 * j + acc_row(i, hh) >= L) v[e] = 0.f;
+                if (!vq || kb0 + 32 * j + acc_row(i, hh) >= kend) v[e] = 0.f;
               }
             }
             const abf16x8 dsb = pack8(v);
@@ -361,7 +395,7 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
 
 // Backward, dK/dV pass: item (bh, 128-key tile), the key on the lane. LDS: Q and dO chunk tiles, two
 // buffers, plus the chunk's lse and D.
-template <bool VARLEN>
+template <bool VARLEN, bool CAUSAL>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void attn_long_dkv_kernel(AttnArgs a, const float* __restrict__ dsum) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B + 2 * 2 * KC * 4];
   float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B);  // [buf][lse, D][64]
@@ -377,9 +411,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
   const bool drop = a.thresh != 0u;
 
   for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const int bh = it / nkt, kt = it - bh * nkt;
+    int bh = it / nkt, kt = it - bh * nkt;
+    if constexpr (CAUSAL) {  // key tile kt is seen by the query chunks from 2 kt on: the heavy tiles first
+      bh = it % (a.B * a.H);
+      kt = it / (a.B * a.H);
+    }
     const int b = bh / a.H, h = bh - b * a.H;
-    const int L = item_len<VARLEN>(a, b, S);
+    const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int k0 = 128 * kt + 32 * w, kg = k0 + (lane & 31);
     const bool live = k0 < L;  // this wave has a valid key (wave-uniform)
     const bool vk = kg < L;
@@ -405,14 +443,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
       put_rows(smem + bf * 2 * TILE_B + TILE_B, pd);
       if (threadIdx.x < 2 * KC) row_s[bf * 2 * KC + threadIdx.x] = pr;
     };
+    const int c0 = CAUSAL ? 2 * kt : 0;  // causal: queries before the key tile see none of it (c0 < nqc when nqc > 0)
     if (nqc > 0) {
-      fetch(0);
-      put(0);
+      fetch(c0);
+      put(c0 & 1);
     }
     __syncthreads();
 
     af32x16 dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};  // lane owns key kg, d = 32 dt + acc_row(i)
-    for (int c = 0; c < nqc; ++c) {
+    for (int c = c0; c < nqc; ++c) {
       const uint8_t* Qs = smem + (c & 1) * 2 * TILE_B;
       const uint8_t* dOs = Qs + TILE_B;
       const float* lse_s = row_s + (c & 1) * 2 * KC;
@@ -426,6 +465,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
 #pragma unroll 1
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && qb0 + 32 * j >= L) continue;
+          if (CAUSAL && qb0 + 32 * j < k0) continue;  // every query of the block is before the wave's keys
+          const int qfirst = CAUSAL && qb0 + 32 * j == k0 ? kg : 0;  // first query that sees this lane's key
           af32x16 st = zero16(), dpt = zero16();  // S and dP: rows = queries qb0 + 32 j + acc_row(i), col = key kg
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
@@ -449,7 +490,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
               pv[e] = pdv;
               dv[e] = p * (dp - D_s[ql]);
               if constexpr (VARLEN) {  // masked key or padded query: exact zeros
-                if (!vk || qg >= L) pv[e] = dv[e] = 0.f;
+                if (!vk || qg >= L || (CAUSAL && qg < qfirst)) pv[e] = dv[e] = 0.f;
               }
             }
             const abf16x8 pb = pack8(pv), dsb = pack8(dv);
@@ -504,16 +545,24 @@ static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra
   return hipGetLastError();
 }
 
+// (VARLEN, CAUSAL): full length, lengths, causal (with or without lengths); without a.causal the choice
+// is the one made before the causal copies existed
+#define PSD_ATTN_LONG_PICK(k, ...)                                               \
+  (a.causal ? launch_long(&k<true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)      \
+            : a.lens ? launch_long(&k<true, false>, a, st __VA_OPT__(, ) __VA_ARGS__) \
+                     : launch_long(&k<false, false>, a, st __VA_OPT__(, ) __VA_ARGS__))
+
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_long_supported(a.S, D)) return hipErrorInvalidValue;
-  return a.lens ? launch_long(&attn_long_fwd_kernel<true>, a, st) : launch_long(&attn_long_fwd_kernel<false>, a, st);
+  return PSD_ATTN_LONG_PICK(attn_long_fwd_kernel);
 }
 hipError_t launch_attn_long_bwd(const AttnArgs& a, float* dsum, hipStream_t st) {
   if (!attn_long_supported(a.S, D) || !dsum) return hipErrorInvalidValue;
-  hipError_t e = a.lens ? launch_long(&attn_long_dq_kernel<true>, a, st, dsum) : launch_long(&attn_long_dq_kernel<false>, a, st, dsum);
+  hipError_t e = PSD_ATTN_LONG_PICK(attn_long_dq_kernel, dsum);
   if (e != hipSuccess) return e;
-  return a.lens ? launch_long(&attn_long_dkv_kernel<true>, a, st, (const float*)dsum)
-                : launch_long(&attn_long_dkv_kernel<false>, a, st, (const float*)dsum);
+  return PSD_ATTN_LONG_PICK(attn_long_dkv_kernel, (const float*)dsum);
 }
+
+#undef PSD_ATTN_LONG_PICK
 
 }  // namespace psd

@@ -79,10 +79,18 @@ __device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i 
 
 // valid rows of sequence b: S without lengths; else lens[b] clamped to [0, S] here, on the device (the
 // host never reads lens, so a replayed graph sees the current values)
-template <bool VARLEN>
+// The causal copies always run the length-aware code and are launched with or without lengths: only
+// they test a.lens for null (L = S then).
+template <bool VARLEN, bool CAUSAL = false>
 __device__ __forceinline__ int item_len(const AttnArgs& a, int b, int S) {
-  if constexpr (VARLEN) return min(max(a.lens[b], 0), S);
-  else return S;
+  if constexpr (VARLEN) {
+    if constexpr (CAUSAL) {
+      if (!a.lens) return S;
+    }
+    return min(max(a.lens[b], 0), S);
+  } else {
+    return S;
+  }
 }
 __device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
 

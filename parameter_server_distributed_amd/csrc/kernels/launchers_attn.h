@@ -22,6 +22,7 @@ struct AttnArgs {
   const int32_t* lens;    // [B] device lengths or null (every sequence full): sequence b has valid rows
                           // 0 .. clamp(lens[b], 0, S) - 1; read by the kernel only, never by the host
   int32_t grid_cap;       // 0: the launcher's own grid; > 0: at most this many (persistent) workgroups
+  int32_t causal;         // != 0: query q sees keys <= q only (and < its length, with lens); the CAUSAL copies
 };
 bool attn_supported(int S, int head_dim);
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t stream);

@@ -94,7 +94,19 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
             return bert_batch(batch, seq, m.vocab, device, seed, min_len=min_len)
 
         return ModelSpec(name, m, make, m.loss, "sequences")
+    if name in ("gpt_small", "gpt"):
+        from .gpt import GPTForLM, gpt_batch
+
+        seq = kw.get("seq_len", 512)
+        m = prepare(GPTForLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
+                             max_pos=max(512, seq)), device, dtype)
+        min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
+
+        def make(batch, device, seed=0):
+            return gpt_batch(batch, seq, m.vocab, device, seed, min_len=min_len)
+
+        return ModelSpec("gpt_small", m, make, m.loss, "sequences")
     raise KeyError(f"unknown model {name!r}; available: {MODELS}")
 
 
-MODELS = ["mlp", "resnet50", "resnet101", "wide_resnet101_2", "bert_base"]
+MODELS = ["mlp", "resnet50", "resnet101", "wide_resnet101_2", "bert_base", "gpt_small"]

@@ -24,12 +24,12 @@ VOCAB = 30528
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0):
+    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False):
         super().__init__()
         self.heads = heads
         self.qkv = MfmaLinear(hidden, 3 * hidden)
         # packed QKV in, [B, S, hidden] out: one fused kernel per direction (ops/attention.py)
-        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index)
+        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=causal)
         self.proj = MfmaLinear(hidden, hidden)
         # LayerNorm(x + dropout(branch)) as one fused kernel family (ops/layernorm.py)
         self.ln1 = FusedAddLayerNorm(hidden, eps=1e-12, p=dropout, seed=2 * index + 1)

@@ -1,0 +1,83 @@
+"""GPT-1-shaped decoder language model (12 layers, hidden 768, 12 heads, FFN 3072, context 512) with
+a next-token head over every position. Random init, synthetic token batches.
+
+The block is ``BertLayer`` with ``causal=True``: post-LN, GELU FFN, every Linear an ``MfmaLinear`` and
+the attention the causal instantiations of the fused gfx950 kernels (``ops/attention.py``; SDPA with
+the same mask off-GPU). Deviations from the original GPT-1, stated here: the 40,478-token vocabulary
+is padded to 40512 (a multiple of 64, for the GEMM tiles); the embeddings are ``FusedBertEmbeddings``
+with all-zero token types, so the sum of the word and position rows (plus one constant type row) goes
+through an embedding LayerNorm and dropout where GPT-1 has dropout only; and the LM head is untied
+from the word embedding, for the reason ``models/bert.py`` gives (the PS data plane needs every weight
+consumed by exactly one autograd node).
+"""
+from __future__ import annotations
+
+
+import torch
+import torch.nn as nn
+
+from ..ops.embedding import FusedBertEmbeddings
+from ..ops.layernorm import bump_step
+from ..ops.linear import MfmaLinear
+from ..ops.loss import cross_entropy
+from .bert import BertLayer
+
+VOCAB = 40512
+
+
+class GPTForLM(nn.Module):
+    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1):
+        super().__init__()
+        self.vocab = vocab
+        self.emb = FusedBertEmbeddings(vocab, hidden, max_pos, 2, eps=1e-12, p=dropout, seed=4242)
+        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True) for i in range(layers)])
+        self.head = MfmaLinear(hidden, vocab)
+        self.p = dropout
+        # device step counter for the fused dropout masks (ops/layernorm.py)
+        self.register_buffer("_psd_rng_step", torch.zeros(1, dtype=torch.int64), persistent=False)
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, std=0.02)
+                nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.Embedding):
+                nn.init.normal_(m.weight, std=0.02)
+
+    def forward(self, batch):
+        # (ids,) or, for a padded batch, (ids, lens): int32 [B] lengths, positions >= lens[b] are padding
+        # that no attention key or query row reads. Logits of every position: [B*S, vocab]
+        ids = batch[0]
+        lens = batch[1] if len(batch) > 1 else None
+        bump_step(self)
+        x = self.emb(ids, torch.zeros_like(ids))
+        for layer in self.layers:
+            x = layer(x, lens)
+        return self.head(x.reshape(-1, x.shape[-1]))
+
+    @staticmethod
+    def loss(logits, labels):
+        return cross_entropy(logits, labels)  # fused bf16 softmax-CE kernels (ops/loss.py)
+
+
+def gpt_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, min_len: int | None = None):
+    """Synthetic language-model batch: random ids and the next-token labels ``[B*S]``,
+    ``labels[b, s] = ids[b, s + 1]``; the last position has no next token and gets -100, which the loss
+    ignores.
+
+    With ``min_len`` the sequences are padded: lengths are uniform in [min_len, seq], ids past a length
+    are 0, every position ``s >= L - 1`` gets label -100 and the batch tuple gains ``lens`` (int32 [B])."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    ids = torch.randint(0, vocab, (batch, seq), generator=g)
+    if min_len is None:
+        lens = torch.full((batch,), seq, dtype=torch.long)
+    else:
+        if not 1 <= int(min_len) <= seq:
+            raise ValueError(f"min_len must be in [1, {seq}], got {min_len}")
+        lens = torch.randint(int(min_len), seq + 1, (batch,), generator=g)
+        ids = ids * (torch.arange(seq)[None, :] < lens[:, None])
+    labels = torch.full((batch, seq), -100, dtype=torch.long)
+    labels[:, :-1] = ids[:, 1:]
+    labels[torch.arange(seq)[None, :] >= lens[:, None] - 1] = -100
+    labels = labels.reshape(-1).to(device)
+    if min_len is None:
+        return (ids.to(device),), labels
+    return (ids.to(device), lens.to(torch.int32).to(device)), labels

@@ -19,8 +19,14 @@ tokens ``0 .. lens[b]-1`` (clamped to ``[0, S]`` on the device, never read back 
 past the length get probability exactly 0, output and gradient rows past it are exact zeros, and
 padded rows of qkv / dO are never read.
 
+``causal=True`` adds the decoder mask: query ``q`` attends to keys ``k <= q`` (and ``k < lens[b]`` with
+``lens``). Both kernel families have causal instantiations that walk only the 32-row blocks on or below
+the diagonal; the dropout hash index is unchanged, so the kept set is the same mask restricted to
+``k <= q``. Rows ``<= j`` of the output do not depend on rows ``> j`` of a finite qkv; future rows inside
+a diagonal block are loaded, so -- unlike padding -- NaN or inf there is not covered.
+
 CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128, 192, 256, 320, 384, 448, 512}
-use SDPA -- the reference the tests compare against -- with the same length semantics.
+use SDPA -- the reference the tests compare against -- with the same length and causal semantics.
 """
 from __future__ import annotations
 
@@ -42,7 +48,7 @@ class _AttnFn(torch.autograd.Function):
         ctx.src = src if (src is not None and src[0].bias is not None and src[0].act in (None, "none")
                           and src[0]._psd_tok == src[1]) else None
         qkv = qkv.contiguous()
-        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens)
+        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens, 0, mod.causal)
         ctx.mod, ctx.p, ctx.lens = mod, p, lens
         ctx.save_for_backward(qkv, o, lse)
         return o
@@ -58,19 +64,21 @@ class _AttnFn(torch.autograd.Function):
             db = sink(lin.bias) if sink is not None else None
             if db is None:
                 db = torch.empty_like(lin.bias)
-        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens)
+        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens, 0, mod.causal)
         if db is not None:
             ctx.src[0]._psd_bias_hand = (ctx.src[1], dqkv.data_ptr(), db)
         return dqkv, None, None, None
 
 
 class FusedSelfAttention(nn.Module):
-    """softmax(Q K^T / sqrt(d)) V with dropout on the probabilities, from the packed QKV tensor."""
+    """softmax(Q K^T / sqrt(d)) V with dropout on the probabilities, from the packed QKV tensor;
+    ``causal``: query q sees keys <= q only."""
 
-    def __init__(self, heads: int, p: float = 0.1, seed: int = 0):
+    def __init__(self, heads: int, p: float = 0.1, seed: int = 0, causal: bool = False):
         super().__init__()
         self.heads = heads
         self.p = p
+        self.causal = bool(causal)
         self.seed = int(seed) & 0x7FFFFFFF
         self.step = None  # device int64 counter, set by the owning model (ops/layernorm.bump_step)
 
@@ -101,7 +109,7 @@ class FusedSelfAttention(nn.Module):
         H = self.heads
         q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)
         if lens is None:
-            a = F.scaled_dot_product_attention(q, k, v, dropout_p=p)
+            a = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=self.causal)
             return a.transpose(1, 2).reshape(B, S, E // 3)
         valid = torch.arange(S, device=qkv.device)[None, :] < lens.clamp(0, S)[:, None]  # [B, S]
         row = valid[:, None, :, None]
@@ -110,5 +118,7 @@ class FusedSelfAttention(nn.Module):
         # padded queries see every key (their zero q gives a finite uniform row, also at L = 0) and
         # are multiplied by zero below
         mask = valid[:, None, None, :] | ~row
+        if self.causal:  # key <= q and key < L; a padded query keeps key 0, so its row stays finite
+            mask = mask & torch.ones(S, S, dtype=torch.bool, device=qkv.device).tril()
         a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p) * row.to(q.dtype)
         return a.transpose(1, 2).reshape(B, S, E // 3)

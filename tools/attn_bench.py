@@ -6,9 +6,11 @@ default shape is BERT-base pre-training (B 256, S 128, 12 heads of 64).
   python tools/attn_bench.py
   python tools/attn_bench.py --min-len 16   # padded batch: lengths uniform in [16, S], passed as lens
   python tools/attn_bench.py --seq 512 --batch 64 --sdpa   # the streaming kernels against the SDPA path
+  python tools/attn_bench.py --seq 512 --batch 64 --causal # the causal instantiations (keys <= q)
 
 With --min-len the bytes count the valid rows only (what the variable-length kernels have to move)
-and the FLOP rate counts the valid (query, key) pairs.
+and the FLOP rate counts the valid (query, key) pairs. With --causal the FLOP rate counts the visible
+pairs (key <= q, and both < the length); the bytes are unchanged.
 
 --sdpa also times the module's SDPA path (F.scaled_dot_product_attention on transposed views, through
 autograd, with its layout copies and, with lengths, its mask) on the same data as a second pair of
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--seq", type=int, default=128, help="sequence length S")
     ap.add_argument("--batch", type=int, default=256, help="batch size B")
     ap.add_argument("--sdpa", action="store_true", help="also time the module's SDPA path on the same data")
+    ap.add_argument("--causal", action="store_true", help="causal mask (keys <= q), on both paths")
     ap.add_argument("--windows", type=int, default=None, help="timing windows per figure (default 1, with --sdpa 5)")
     args = ap.parse_args()
     C = native()
@@ -60,7 +63,8 @@ def main():
     do = torch.randn(B, S, H * D, device=dev).to(torch.bfloat16)
     step = torch.tensor([3], device=dev, dtype=torch.int64)
     el = B * S * H * D * 2  # bytes of one [B, S, H, 64] bf16 tensor
-    flop_f = 4 * B * H * S * S * D
+    causal = args.causal
+    flop_f = 4 * B * H * D * (S * (S + 1) // 2 if causal else S * S)
     lens = None
     if args.min_len is not None:
         if not 0 <= args.min_len <= S:
@@ -69,27 +73,27 @@ def main():
         lc = torch.randint(args.min_len, S + 1, (B,), generator=g)
         lens = lc.to(torch.int32).to(dev)
         el = int(lc.sum()) * H * D * 2  # the valid rows only
-        flop_f = 4 * H * D * int((lc * lc).sum())
+        flop_f = 4 * H * D * int((lc * (lc + 1) // 2 if causal else lc * lc).sum())
         print(f"lens uniform in [{args.min_len}, {S}]: mean {lc.float().mean():.1f}, valid rows {int(lc.sum())} of {B * S}")
     it = args.iters
-    print(f"B {B}, S {S}, H {H}, D {D}; {nwin} window(s) of {it} calls")
+    print(f"B {B}, S {S}, H {H}, D {D}{', causal' if causal else ''}; {nwin} window(s) of {it} calls")
     head = "| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |"
     if args.sdpa:
         from parameter_server_distributed_amd.ops.attention import FusedSelfAttention
 
-        mod = FusedSelfAttention(H).to(dev)
+        mod = FusedSelfAttention(H, causal=causal).to(dev)
         xg = qkv.clone().requires_grad_(True)
         head += " sdpa fwd us | sdpa bwd us | fwd+bwd us | sdpa fwd+bwd us |"
     print(head)
     print("|" + "---:|" * (head.count("|") - 1))
     for p in (0.0, 0.1):
-        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens)
+        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal)
         tf, tb, sf, sb = [], [], [], []
         for _ in range(nwin):  # the paths alternate inside a window
-            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens), it))
+            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal), it))
             if args.sdpa:
                 sf.append(t_us(lambda: mod._sdpa(xg, lens, p), it))
-            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens), it))
+            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens, 0, causal), it))
             if args.sdpa:
                 so = mod._sdpa(xg, lens, p)
                 sb.append(t_us(lambda: torch.autograd.grad(so, xg, do, retain_graph=True), it))
