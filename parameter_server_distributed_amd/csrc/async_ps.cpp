@@ -136,7 +136,7 @@ bool psd_feature_on(const char* name, bool dflt) {
 AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers,
                          std::vector<int64_t> shard_off, std::vector<int64_t> shard_len, int staleness, int nbuf,
                          std::string shm_name, bool create, int device, double timeout_s, int elem_bytes, bool mx,
-                         bool clip)
+                         bool clip, bool push_mx)
     : rank_(rank),
       world_(world),
       S_(staleness),
@@ -146,6 +146,7 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
       esz_(elem_bytes),
       mx_(mx),
       clip_(clip),
+      push_mx_(push_mx),
       owners_(std::move(owners)),
       workers_(std::move(workers)),
       shard_off_(std::move(shard_off)),
@@ -161,6 +162,12 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
     for (int k = 0; k < P; ++k)
       TORCH_CHECK(shard_off_[k] % 32 == 0 && shard_len_[k] % 32 == 0,
                   "psd async: MX shards must be 32-element aligned");
+  }
+  if (push_mx_) {
+    // a 32-element block never straddles a shard (the flat layout cuts on 64-element boundaries)
+    for (int k = 0; k < P; ++k)
+      TORCH_CHECK(shard_off_[k] % 32 == 0 && shard_len_[k] % 32 == 0,
+                  "psd async: MX gradient push needs 32-element aligned shards");
   }
   TORCH_CHECK(nbuf_ >= 2 && nbuf_ <= kMaxBuf, "psd async: 2..", kMaxBuf, " publish buffers");
   TORCH_CHECK(esz_ == 2 || esz_ == 4, "psd async: bf16 (2) or fp32 (4) elements");
@@ -235,8 +242,17 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
                                             : c10::Device(c10::kCPU));
   for (int k : my_shards_) {
     ShardState& st = shards_[k];
-    for (int wi = 0; wi < W; ++wi)
-      for (int s = 0; s <= S_; ++s) st.inbox.push_back(at::from_blob(inbox_ptr(k, wi, s), {shard_len_[k]}, opt));
+    for (int wi = 0; wi < W; ++wi) {
+      for (int s = 0; s <= S_; ++s) {
+        if (push_mx_) {
+          st.inbox.push_back(at::from_blob(inbox_ptr(k, wi, s), {shard_len_[k]}, opt.dtype(at::kFloat8_e4m3fn)));
+          st.inbox_sc.push_back(
+              at::from_blob(inbox_ptr(k, wi, s) + shard_len_[k], {shard_len_[k] / 32}, opt.dtype(at::kByte)));
+        } else {
+          st.inbox.push_back(at::from_blob(inbox_ptr(k, wi, s), {shard_len_[k]}, opt));
+        }
+      }
+    }
     for (int b = 0; b < nbuf_; ++b) st.publish.push_back(at::from_blob(publish_ptr(k, b), {shard_len_[k]}, opt));
     if (clip_)
       for (int wi = 0; wi < W; ++wi)
@@ -280,6 +296,7 @@ void AsyncEngine::close_peers() {
 void AsyncEngine::free_local() {
   // callers: stop() first, and every peer has closed its mapping (Python barrier in between)
   shards_.clear();
+  stage_.clear();
   if (local_mem_) {
     if (device_ >= 0) (void)hipFree(local_mem_);
     else {
@@ -312,7 +329,15 @@ int AsyncEngine::worker_index(int rank) const {
 // A shard's region: W * (S + 1) inbox slots, then nbuf publish slots; with MX a publish slot also
 // holds the e4m3 copy of the snapshot and its E8M0 scales (one per 32 elements) after the bf16 one.
 // A clip engine appends W * (S + 1) scalar slots of 256 bytes (one per inbox slot); without clip the
-// layout is exactly the one above.
+// layout is exactly the one above. On a push_mx engine an inbox slot is shard_len e4m3 payload bytes
+// followed by shard_len / 32 E8M0 scale bytes (33/32 bytes per element, rounded up to the slot
+// alignment only) instead of shard_len gradient elements.
+int64_t AsyncEngine::inbox_slot_bytes(int shard) const {
+  TORCH_CHECK(shard >= 0 && shard < (int)shard_len_.size(), "psd async: bad shard");
+  const int64_t n = shard_len_[shard];
+  return round_up(push_mx_ ? n + n / 32 : n * esz_, kAlignBytes);
+}
+
 int64_t AsyncEngine::pub_slot_bytes(int shard) const {
   const int64_t sb = round_up(shard_len_[shard] * esz_, kAlignBytes);
   if (!mx_) return sb;
@@ -320,7 +345,7 @@ int64_t AsyncEngine::pub_slot_bytes(int shard) const {
 }
 
 int64_t AsyncEngine::shard_region_bytes(int shard) const {
-  return (int64_t)workers_.size() * (S_ + 1) * round_up(shard_len_[shard] * esz_, kAlignBytes) +
+  return (int64_t)workers_.size() * (S_ + 1) * inbox_slot_bytes(shard) +
          nbuf_ * pub_slot_bytes(shard) + (clip_ ? (int64_t)workers_.size() * (S_ + 1) * kScalarBytes : 0);
 }
 
@@ -341,15 +366,14 @@ int64_t AsyncEngine::shard_base(int rank, int shard) const {
 char* AsyncEngine::inbox_ptr(int shard, int wi, int slot) const {
   const int o = owners_[shard];
   TORCH_CHECK(peer_base_[o], "psd async: rank ", o, " memory not attached");
-  const int64_t sb = round_up(shard_len_[shard] * esz_, kAlignBytes);
-  return peer_base_[o] + shard_base(o, shard) + ((int64_t)wi * (S_ + 1) + slot) * sb;
+  return peer_base_[o] + shard_base(o, shard) + ((int64_t)wi * (S_ + 1) + slot) * inbox_slot_bytes(shard);
 }
 
 char* AsyncEngine::publish_ptr(int shard, int buf) const {
   const int o = owners_[shard];
   TORCH_CHECK(peer_base_[o], "psd async: rank ", o, " memory not attached");
-  const int64_t sb = round_up(shard_len_[shard] * esz_, kAlignBytes);
-  return peer_base_[o] + shard_base(o, shard) + (int64_t)workers_.size() * (S_ + 1) * sb + buf * pub_slot_bytes(shard);
+  return peer_base_[o] + shard_base(o, shard) + (int64_t)workers_.size() * (S_ + 1) * inbox_slot_bytes(shard) +
+         buf * pub_slot_bytes(shard);
 }
 
 char* AsyncEngine::scalar_ptr(int shard, int wi, int slot) const {
@@ -622,10 +646,11 @@ bool AsyncEngine::poll_once() {
       // arrival order (bitwise-reproducible rounds at SSP bound 0)
       std::sort(st.round.begin(), st.round.end(),
                 [](const RoundItem& x, const RoundItem& y) { return x.wi != y.wi ? x.wi < y.wi : x.step < y.step; });
-      std::vector<at::Tensor> g, sc;
+      std::vector<at::Tensor> g, sc, mxs;
       for (RoundItem& it : st.round) {
         it.staleness = st.enq - it.pulled;
         g.push_back(st.inbox[(size_t)it.wi * (S_ + 1) + it.slot]);
+        if (push_mx_) mxs.push_back(st.inbox_sc[(size_t)it.wi * (S_ + 1) + it.slot]);
         if (clip_) sc.push_back(st.scal[(size_t)it.wi * (S_ + 1) + it.slot]);
       }
       st.enq += 1;
@@ -634,12 +659,12 @@ bool AsyncEngine::poll_once() {
       if (device_ >= 0) {
         c10::hip::HIPStreamGuard sg(c10::hip::getStreamFromExternal(static_cast<hipStream_t>(ps_stream_),
                                                                     (c10::DeviceIndex)device_));
-        apply_into(st, g, sc, buf);
+        apply_into(st, g, sc, mxs, buf);
         if (mx_) quant_publish(st, k, buf, ps_stream_);
         hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
         hip_ok(hipEventRecord(ev, static_cast<hipStream_t>(ps_stream_)), "hipEventRecord");
       } else {
-        apply_into(st, g, sc, buf);
+        apply_into(st, g, sc, mxs, buf);
       }
       pending_.push_back(Pending{k, buf, std::move(st.round), ev});
       st.round.clear();
@@ -651,15 +676,18 @@ bool AsyncEngine::poll_once() {
 // One update: optimizer step counter, fused apply of the round's inbox slots (summed in registers,
 // scaled by the dyn grad_scale = 1/K) onto the fp32 master, and the new snapshot written into
 // publish buffer `buf` (bf16: by the apply kernel itself). On a clip engine each source is multiplied
-// by the coefficient in its scalar block inside the same kernels (`sc_in`, one block per source).
+// by the coefficient in its scalar block inside the same kernels (`sc_in`, one block per source). On
+// a push_mx engine the sources are MX e4m3 slots and `mx_in` their scale bytes: the same kernels'
+// MX-source instantiations dequantise as they sum.
 void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in, const std::vector<at::Tensor>& sc_in,
-                             int buf) {
+                             const std::vector<at::Tensor>& mx_in, int buf) {
   // a round of more than 16 pushes (the fused apply kernel's source limit): each group of 16
   // inbox slots (worker order) is summed into an fp32 workspace and the apply takes the group sums
   // (fixed order, so rounds stay bitwise reproducible). With K = W every round completes -- a
   // partial round stranded at W > 16 would hold a worker's clock back forever.
   std::vector<at::Tensor> g = g_in;
   ScaleList sc(sc_in.begin(), sc_in.end());
+  MxScaleList mxs = mx_in;
   if (g.size() > (size_t)kMaxSources) {
     const size_t ng = (g.size() + kMaxSources - 1) / kMaxSources;
     TORCH_CHECK(ng <= (size_t)kMaxSources, "psd async: at most 256 pushes per round");
@@ -669,11 +697,13 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
       const size_t b = gi * kMaxSources, e = std::min(g.size(), b + kMaxSources);
       // the clipping coefficients go into the group sums; the apply then takes them unscaled
       multi_reduce_(st.acc[gi], std::vector<at::Tensor>(g.begin() + b, g.begin() + e), 1.0,
-                    sc.empty() ? ScaleList{} : ScaleList(sc.begin() + b, sc.begin() + e));
+                    sc.empty() ? ScaleList{} : ScaleList(sc.begin() + b, sc.begin() + e),
+                    mxs.empty() ? MxScaleList{} : MxScaleList(mxs.begin() + b, mxs.begin() + e));
       sums.push_back(st.acc[gi]);
     }
     g = std::move(sums);
     sc.clear();
+    mxs.clear();  // the group sums are fp32
   }
   optim_advance_(st.dyn, st.hyper.beta1, st.hyper.beta2);
   const bool bf16 = esz_ == 2;
@@ -682,7 +712,7 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
                     st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
                     bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,
                     st.hyper.momentum, st.hyper.dampening, st.hyper.nesterov, st.hyper.weight_decay, st.hyper.beta1,
-                    st.hyper.beta2, st.hyper.eps, false, st.trust_coef, st.layers, apply_cap_, sc);
+                    st.hyper.beta2, st.hyper.eps, false, st.trust_coef, st.layers, apply_cap_, sc, mxs);
     if (!bf16) st.publish[buf].copy_(st.master);
     return;
   }
@@ -690,7 +720,7 @@ void AsyncEngine::apply_into(ShardState& st, const std::vector<at::Tensor>& g_in
                st.s2.defined() ? c10::optional<at::Tensor>(st.s2) : c10::nullopt,
                bf16 ? c10::optional<at::Tensor>(st.publish[buf]) : c10::nullopt, st.dyn, st.hyper.kind,
                st.hyper.momentum, st.hyper.dampening, st.hyper.nesterov, st.hyper.weight_decay, st.hyper.beta1,
-               st.hyper.beta2, st.hyper.eps, false, apply_cap_, sc);
+               st.hyper.beta2, st.hyper.eps, false, apply_cap_, sc, mxs);
   if (!bf16) st.publish[buf].copy_(st.master);
 }
 
@@ -942,6 +972,10 @@ void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, i
   check_error();
   const char* src = static_cast<const char*>(grads_flat.data_ptr());
   const int slot = (int)(step % (S_ + 1));
+  if (push_mx_) {
+    push_mx_range(grads_flat, lo, hi, slot, stream);
+    return;
+  }
   bool remote = false, al = true;
   for (size_t k = 0; k < owners_.size(); ++k) {
     const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
@@ -972,6 +1006,68 @@ void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, i
     if (a >= b) continue;
     copy(inbox_ptr((int)k, my_wi_, slot) + (a - shard_off_[k]) * esz_, src + a * esz_, (b - a) * esz_,
          reinterpret_cast<void*>(stream));
+  }
+}
+
+// MX push of [lo, hi): every overlapped shard's slice -> e4m3 payload + E8M0 bytes in this worker's
+// inbox slot there. Kernel transport: ONE quantising scatter launch over all of them, local and
+// peer destinations alike (kernels/xfer.hip xfer_quant_kernel). Copy transport: the range is
+// quantised into the gradient buffer's staging pair by the same kernel, then one hipMemcpyAsync
+// each for a slice's payload and scales. Host engine: quantised on the host (ops.cpp
+// push_quant_mx_). The three give the same bytes.
+void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream) {
+  TORCH_CHECK(lo % 32 == 0 && hi % 32 == 0 && lo >= 0 && hi <= grads_flat.numel(),
+              "psd async: an MX push covers whole 32-element blocks of the gradient buffer, got [", lo, ", ", hi, ")");
+  const char* src = static_cast<const char*>(grads_flat.data_ptr());
+  const int P = (int)owners_.size();
+  auto q_dst = [&](int k, int64_t a) {
+    return reinterpret_cast<uint8_t*>(inbox_ptr(k, my_wi_, slot)) + (a - shard_off_[k]);
+  };
+  auto sc_dst = [&](int k, int64_t a) {
+    return reinterpret_cast<uint8_t*>(inbox_ptr(k, my_wi_, slot)) + shard_len_[k] + (a - shard_off_[k]) / 32;
+  };
+  if (device_ < 0) {
+    for (int k = 0; k < P; ++k) {
+      const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
+      if (a >= b) continue;
+      const auto bytes = at::TensorOptions().dtype(at::kByte);
+      push_quant_mx_(grads_flat.narrow(0, a, b - a), at::from_blob(q_dst(k, a), {b - a}, bytes),
+                     at::from_blob(sc_dst(k, a), {(b - a) / 32}, bytes), 0);
+    }
+    return;
+  }
+  const c10::DeviceGuard g(c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)device_));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  XferQList L{};
+  L.src_dtype = esz_ == 2 ? DT_BF16 : DT_F32;
+  if (xfer_kernel_) {
+    int64_t mx = 0;
+    for (int k = 0; k < P; ++k) {
+      const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
+      if (a >= b) continue;
+      L.seg[L.count++] = XferQSeg{src + a * esz_, q_dst(k, a), sc_dst(k, a), b - a};
+      mx = std::max(mx, b - a);
+    }
+    L.blocks_per_seg = xfer_blocks(mx * esz_, xfer_cap_);
+    hip_ok(launch_xfer_quant(L, st), "launch_xfer_quant(push)");
+    return;
+  }
+  auto it = stage_.find(grads_flat.data_ptr());
+  if (it == stage_.end()) {
+    const auto bytes = grads_flat.options().dtype(at::kByte);
+    it = stage_.emplace(grads_flat.data_ptr(), std::make_pair(at::empty({grads_flat.numel()}, bytes),
+                                                              at::empty({grads_flat.numel() / 32 + 1}, bytes))).first;
+  }
+  uint8_t* sq = it->second.first.data_ptr<uint8_t>();
+  uint8_t* ss = it->second.second.data_ptr<uint8_t>();
+  L.seg[L.count++] = XferQSeg{src + lo * esz_, sq + lo, ss + lo / 32, hi - lo};
+  L.blocks_per_seg = xfer_blocks((hi - lo) * esz_, xfer_cap_);
+  hip_ok(launch_xfer_quant(L, st), "launch_xfer_quant(stage)");
+  for (int k = 0; k < P; ++k) {
+    const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
+    if (a >= b) continue;
+    copy(q_dst(k, a), sq + a, b - a, reinterpret_cast<void*>(stream));
+    copy(sc_dst(k, a), ss + a / 32, (b - a) / 32, reinterpret_cast<void*>(stream));
   }
 }
 
@@ -1045,6 +1141,13 @@ at::Tensor AsyncEngine::inbox_view(int shard, int wi, int slot) const {
   TORCH_CHECK(shard >= 0 && shard < (int)owners_.size() && owners_[shard] == rank_, "psd async: not my shard");
   TORCH_CHECK(wi >= 0 && wi < (int)workers_.size() && slot >= 0 && slot <= S_, "psd async: bad inbox index");
   return shards_[shard].inbox[(size_t)wi * (S_ + 1) + slot];
+}
+
+at::Tensor AsyncEngine::inbox_scales_view(int shard, int wi, int slot) const {
+  TORCH_CHECK(push_mx_, "psd async: inbox scale bytes exist on MX-push engines only");
+  TORCH_CHECK(shard >= 0 && shard < (int)owners_.size() && owners_[shard] == rank_, "psd async: not my shard");
+  TORCH_CHECK(wi >= 0 && wi < (int)workers_.size() && slot >= 0 && slot <= S_, "psd async: bad inbox index");
+  return shards_[shard].inbox_sc[(size_t)wi * (S_ + 1) + slot];
 }
 
 at::Tensor AsyncEngine::scalar_view(int shard, int wi, int slot) const {

@@ -40,6 +40,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -55,7 +56,7 @@ class AsyncEngine {
  public:
   AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers, std::vector<int64_t> shard_off,
               std::vector<int64_t> shard_len, int staleness, int nbuf, std::string shm_name, bool create, int device,
-              double timeout_s, int elem_bytes = 2, bool mx = false, bool clip = false);
+              double timeout_s, int elem_bytes = 2, bool mx = false, bool clip = false, bool push_mx = false);
   ~AsyncEngine();
 
   // -- memory exchange (collective through the caller's store) --
@@ -108,8 +109,11 @@ class AsyncEngine {
   void wait_applied(int64_t nsteps);  // this worker's pushes 0..nsteps-1 applied at every shard
   void wait_all_applied(int64_t nsteps);  // every worker's pushes 0..nsteps-1 applied at every shard
 
-  // this rank's inbox slot of worker index wi at shard (owner side; start-up self-test)
+  // this rank's inbox slot of worker index wi at shard (owner side; start-up self-test): the gradient
+  // elements, or on a push_mx engine the e4m3 payload; inbox_scales_view: its E8M0 bytes (push_mx only)
   at::Tensor inbox_view(int shard, int wi, int slot) const;
+  at::Tensor inbox_scales_view(int shard, int wi, int slot) const;
+  int64_t inbox_slot_bytes(int shard) const;  // bytes of one inbox slot of `shard` (any rank)
   at::Tensor scalar_view(int shard, int wi, int slot) const;  // its scalar block (64 fp32; clip engines)
 
   // -- introspection --
@@ -146,7 +150,8 @@ class AsyncEngine {
     OptimHyper hyper{};
     std::vector<at::Tensor> layers;   // layer table (set_shard_layers); empty: the flat apply
     double trust_coef = 0.001;
-    std::vector<at::Tensor> inbox;    // [workers * (S+1)] bf16 views
+    std::vector<at::Tensor> inbox;    // [workers * (S+1)] bf16 views (push_mx: e4m3 payload views)
+    std::vector<at::Tensor> inbox_sc; // [workers * (S+1)] uint8 views of the slots' E8M0 bytes (push_mx engines)
     std::vector<at::Tensor> scal;     // [workers * (S+1)] fp32 [64] views of the scalar slots (clip engines)
     std::vector<at::Tensor> publish;  // [nbuf] bf16 views
     std::vector<bool> busy;           // publish buffer is the target of an enqueued apply
@@ -168,7 +173,11 @@ class AsyncEngine {
   char* publish_ptr(int shard, int buf) const;
   char* scalar_ptr(int shard, int wi, int slot) const;
   // sc: the sources' scalar blocks (clip engines), empty otherwise
-  void apply_into(ShardState& st, const std::vector<at::Tensor>& g, const std::vector<at::Tensor>& sc, int buf);
+  // mxs: the sources' E8M0 scale bytes (push_mx engines), empty otherwise
+  void apply_into(ShardState& st, const std::vector<at::Tensor>& g, const std::vector<at::Tensor>& sc,
+                  const std::vector<at::Tensor>& mxs, int buf);
+  // push_mx: [lo, hi) of the gradient buffer -> MX e4m3 in this worker's inbox slots
+  void push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream);
   int free_buf(int shard) const;
   bool claim_buf(int shard, int b);
   static bool done(void* event);
@@ -193,6 +202,12 @@ class AsyncEngine {
   int esz_;
   bool mx_ = false;  // MX fp8 publish: each publish slot also holds e4m3 + E8M0 scales of the snapshot
   bool clip_ = false;  // per-push clipping scalars: W * (S + 1) scalar slots after each shard's publish slots
+  // MX fp8 gradient push: an inbox slot is shard_len e4m3 bytes + shard_len / 32 E8M0 bytes, the
+  // workers quantise as they push and the owner's apply dequantises as it sums
+  bool push_mx_ = false;
+  // copy transport of an MX push: per gradient buffer (by address) a worker-side staging pair
+  // (payload [total], scales [total / 32]) the range is quantised into before the copies
+  std::map<const void*, std::pair<at::Tensor, at::Tensor>> stage_;
   std::vector<int> owners_, workers_, my_shards_;
   std::vector<int64_t> shard_off_, shard_len_;
   int my_wi_ = -1;

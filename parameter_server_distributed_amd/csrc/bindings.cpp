@@ -23,12 +23,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("shadow"), py::arg("dyn"), py::arg("kind"), py::arg("momentum") = 0.0, py::arg("dampening") = 0.0,
         py::arg("nesterov") = false, py::arg("weight_decay") = 0.0, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
         py::arg("eps") = 1e-8, py::arg("maximize") = false,
-        py::arg("grid_cap") = 0, py::arg("scales") = ScaleList{});
+        py::arg("grid_cap") = 0, py::arg("scales") = ScaleList{}, py::arg("mx_scales") = MxScaleList{});
   m.def("fused_apply_lw_", &fused_apply_lw_, py::arg("master"), py::arg("grads"), py::arg("state1"),
         py::arg("state2"), py::arg("shadow"), py::arg("dyn"), py::arg("kind"), py::arg("momentum") = 0.0,
         py::arg("dampening") = 0.0, py::arg("nesterov") = false, py::arg("weight_decay") = 0.0, py::arg("beta1") = 0.9,
         py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("maximize") = false, py::arg("trust_coef") = 0.001,
-        py::arg("layers") = std::vector<at::Tensor>{}, py::arg("grid_cap") = 0, py::arg("scales") = ScaleList{});
+        py::arg("layers") = std::vector<at::Tensor>{}, py::arg("grid_cap") = 0, py::arg("scales") = ScaleList{},
+        py::arg("mx_scales") = MxScaleList{});
   m.def(
       "lw_table_build",
       [](const std::vector<int64_t>& offsets, const std::vector<int64_t>& numels, const std::vector<int64_t>& ndims,
@@ -54,7 +55,9 @@ PYBIND11_MODULE(_C, m) {
       py::arg("weight_decay"), "per-push optimizer hyperparameters of an apply-on-arrival PS (async_hyper.h)");
   m.def("optim_advance_", &optim_advance_, py::arg("dyn"), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999);
   m.def("multi_reduce_", &multi_reduce_, py::arg("out"), py::arg("srcs"), py::arg("scale") = 1.0,
-        py::arg("scales") = ScaleList{});
+        py::arg("scales") = ScaleList{}, py::arg("mx_scales") = MxScaleList{});
+  m.def("push_quant_mx_", &push_quant_mx_, py::arg("x"), py::arg("q"), py::arg("scales"),
+        py::arg("blocks_per_seg") = 0);
   m.def("grad_clip_coef_", &grad_clip_coef_, py::arg("flat"), py::arg("clip_norm"), py::arg("out"), py::arg("partials"),
         py::arg("grid_cap") = 0);
   m.def("pack_cast_", &pack_cast_, py::arg("srcs"), py::arg("dsts"));
@@ -323,11 +326,11 @@ PYBIND11_MODULE(_C, m) {
   // ---- asynchronous apply-on-arrival PS over peer memory ----
   py::class_<AsyncEngine>(m, "AsyncEngine")
       .def(py::init<int, int, std::vector<int>, std::vector<int>, std::vector<int64_t>, std::vector<int64_t>, int, int,
-                    std::string, bool, int, double, int, bool, bool>(),
+                    std::string, bool, int, double, int, bool, bool, bool>(),
            py::arg("rank"), py::arg("world"), py::arg("owners"), py::arg("workers"), py::arg("shard_off"),
            py::arg("shard_len"), py::arg("staleness"), py::arg("nbuf"), py::arg("shm_name"), py::arg("create"),
            py::arg("device"), py::arg("timeout_s"), py::arg("elem_bytes") = 2, py::arg("mx") = false,
-           py::arg("clip") = false)
+           py::arg("clip") = false, py::arg("push_mx") = false)
       .def("local_desc", [](const AsyncEngine& e) { return py::bytes(e.local_desc()); })
       .def("attach_peer", [](AsyncEngine& e, int r, py::bytes d) { e.attach_peer(r, std::string(d)); })
       .def("set_shard_state", &AsyncEngine::set_shard_state)
@@ -348,6 +351,8 @@ PYBIND11_MODULE(_C, m) {
       .def("wait_applied", &AsyncEngine::wait_applied, py::call_guard<py::gil_scoped_release>())
       .def("wait_all_applied", &AsyncEngine::wait_all_applied, py::call_guard<py::gil_scoped_release>())
       .def("inbox_view", &AsyncEngine::inbox_view)
+      .def("inbox_scales_view", &AsyncEngine::inbox_scales_view)
+      .def("inbox_slot_bytes", &AsyncEngine::inbox_slot_bytes)
       .def("scalar_view", &AsyncEngine::scalar_view)
       .def("histogram", &AsyncEngine::histogram)
       .def("version", &AsyncEngine::version)

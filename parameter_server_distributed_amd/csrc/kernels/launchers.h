@@ -23,7 +23,12 @@ enum OptimKind : int32_t {
   OPT_LAMB = 5,       // Adam direction u + wd p scaled by ||p|| / ||u|| per tensor (launchers_optim_lw.h)
 };
 
-enum DType : int32_t { DT_F32 = 0, DT_BF16 = 1, DT_F8E4M3 = 2 };
+enum DType : int32_t {
+  DT_F32 = 0,
+  DT_BF16 = 1,
+  DT_F8E4M3 = 2,
+  DT_MX8 = 3,  // gradient sources only: OCP MX e4m3 payload + one E8M0 byte per 32 elements (SourceList::mx_scale)
+};
 
 // Static hyper-parameters: passed by value, frozen into a captured graph (they never change
 // during a run).
@@ -61,12 +66,27 @@ constexpr int kMaxSources = 16;
 // every source or null for every source. With scales the consumers compute
 // grad_scale * sum_k scale_k * src_k (one fma per source element, in source order) in separate
 // kernel instantiations; a scale of exactly 1 reproduces the unscaled bits.
+//
+// DT_MX8 sources (the async plane's fp8 gradient push): ptr[k] is the e4m3 payload, mx_scale[k] its
+// E8M0 bytes (one per 32 elements, blocks numbered from element 0 of the source); the consumers sum
+// dq(q_k) = q_k * 2^(byte - 127) in fp32 with the same forms, in their own instantiations. The
+// source length must be a multiple of 32. mx_scale is null for every other dtype.
 struct SourceList {
   const void* ptr[kMaxSources];
   const float* scale[kMaxSources];
   int32_t count;
   int32_t dtype;  // DType of every source
+  const uint8_t* mx_scale[kMaxSources];
 };
+
+// DT_MX8: every source carries its scale bytes and n is a whole number of 32-element blocks
+inline bool source_mx_ok(const SourceList& s, int64_t n) {
+  if (s.dtype != DT_MX8) return true;
+  if (n % 32 != 0) return false;
+  for (int k = 0; k < s.count; ++k)
+    if (!s.mx_scale[k]) return false;
+  return true;
+}
 
 // 0: no scales, 1: every source has one, -1: a mix (refused by every launcher)
 inline int source_scale_mode(const SourceList& s) {

@@ -47,6 +47,29 @@ struct XferMxList {
 };
 hipError_t launch_xfer_mx(const XferMxList& list, hipStream_t stream);
 
+// Quantising push (fp8 gradient push): per segment, n elements of the worker's bf16 / fp32 gradient
+// -> n e4m3 payload bytes at q_dst and n / 32 E8M0 scale bytes at sc_dst, in one pass, with the
+// segment / workgroup mapping of launch_xfer. Scale and rounding are those of launch_quant_mx
+// (kernels/fp8.hip), except that a NaN or +-inf element becomes the e4m3 NaN byte 0x7F (a block
+// that holds one takes the unit scale 127) instead of being dropped or saturated. n % 32 == 0, blocks
+// numbered from the segment's first element; src and q_dst 16-byte aligned. All stores are
+// non-temporal and released at system scope before the kernel ends (local and peer destinations).
+// blocks_per_seg counts workgroups (the push's CU budget) as in XferList; the launcher picks their
+// width (1024 lanes for grids under 128 workgroups, else 256), which does not change the bytes.
+struct XferQSeg {
+  const void* src;
+  uint8_t* q_dst;
+  uint8_t* sc_dst;
+  int64_t n;
+};
+struct XferQList {
+  XferQSeg seg[kMaxXferSeg];
+  int32_t count;
+  int32_t blocks_per_seg;
+  int32_t src_dtype;  // DT_BF16 or DT_F32 (launchers.h)
+};
+hipError_t launch_xfer_quant(const XferQList& list, hipStream_t stream);
+
 // blocks per segment for `bytes` (the largest segment of a launch): ~128 KiB per workgroup, at
 // most `cap` (a local copy may take more CUs than one peer link can use)
 inline int32_t xfer_blocks(int64_t bytes, int32_t cap) {

@@ -17,6 +17,10 @@
 // instantiation (SCALED) that multiplies each source by its device scalar inside the same pass,
 // acc = fmaf(c_k, g_k, acc); its only LDS is the K staged scalars. The unscaled instantiation is the
 // kernel as it was.
+//
+// MX sources (DT_MX8, the fp8 gradient push): two more instantiations per kind that read 8 e4m3 bytes
+// and the block's E8M0 byte per source and lane-iteration (9/8 B per element and source instead of
+// 2) and sum the dequantised values with the same forms (optim_update.h load8_mx).
 #include "common.h"
 #include "launchers.h"
 #include "optim_update.h"
@@ -65,8 +69,8 @@ __global__ __launch_bounds__(256) void fused_apply_kernel(OptimHyper h, const Op
     if (two_state) store8_f32(s2 + i, b);
     if (shadow) store8_bf16(shadow + i, p);
   }
-  // Tail (n % 8 elements): first block only.
-  if (blockIdx.x == 0) {
+  // Tail (n % 8 elements): first block only. MX sources come in whole 32-element blocks: no tail.
+  if constexpr (SRC_DT != DT_MX8) if (blockIdx.x == 0) {
     for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
       float gr = load_source1<SRC_DT, SCALED>(g, i, gs, sc);
       float p = master[i];
@@ -98,7 +102,10 @@ static void dispatch_src(const OptimHyper& h, const OptimDyn* dyn, float* master
 #define PSD_APPLY(DT, SC)                                                                                          \
   hipLaunchKernelGGL((fused_apply_kernel<KIND, DT, SC>), dim3(grid), dim3(block), 0, st, h, dyn, master, g, s1, s2, \
                      shadow, n)
-  if (g.dtype == DT_BF16) {
+  if (g.dtype == DT_MX8) {
+    if (scaled) PSD_APPLY(DT_MX8, true);
+    else PSD_APPLY(DT_MX8, false);
+  } else if (g.dtype == DT_BF16) {
     if (scaled) PSD_APPLY(DT_BF16, true);
     else PSD_APPLY(DT_BF16, false);
   } else {
@@ -112,6 +119,7 @@ hipError_t launch_fused_apply(const OptimHyper& h, const OptimDyn* dyn, float* m
                               float* s1, float* s2, uint16_t* shadow, int64_t n, hipStream_t st, int grid_cap) {
   if (n <= 0) return hipSuccess;
   if (g.count < 1 || g.count > kMaxSources || source_scale_mode(g) < 0) return hipErrorInvalidValue;
+  if (!source_mx_ok(g, n)) return hipErrorInvalidValue;
   switch (h.kind) {
     case OPT_SGD: dispatch_src<OPT_SGD>(h, dyn, master, g, s1, s2, shadow, n, st, grid_cap); break;
     case OPT_MOMENTUM: dispatch_src<OPT_MOMENTUM>(h, dyn, master, g, s1, s2, shadow, n, st, grid_cap); break;

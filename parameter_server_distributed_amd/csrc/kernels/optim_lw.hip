@@ -195,6 +195,13 @@ inline bool lw_table_ok(const LwTable& t) {
          t.chunk_off && t.partials && t.ratio;
 }
 
+// bf16 / fp32 sources, or MX sources with their scale bytes (a layer table's range is a multiple of 8
+// elements and MX sources are whole 32-element blocks: the host entry point checks the length)
+inline bool lw_src_ok(const SourceList& g) {
+  if (g.dtype == DT_MX8) return source_mx_ok(g, 0);
+  return g.dtype == DT_BF16 || g.dtype == DT_F32;
+}
+
 template <int KIND>
 void lw_apply_src(const OptimHyper& h, const OptimDyn* dyn, float* master, const SourceList& g, float* s1, float* s2,
                   uint16_t* shadow, const LwTable& t, hipStream_t st, int grid) {
@@ -202,7 +209,10 @@ void lw_apply_src(const OptimHyper& h, const OptimDyn* dyn, float* master, const
   const bool scaled = KIND != OPT_LAMB && source_scale_mode(g) == 1;
 #define PSD_LW_APPLY(DT, SC)                                                                                        \
   hipLaunchKernelGGL((lw_apply_kernel<KIND, DT, SC>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, shadow, t)
-  if (g.dtype == DT_BF16) {
+  if (g.dtype == DT_MX8) {
+    if (scaled) PSD_LW_APPLY(DT_MX8, true);
+    else PSD_LW_APPLY(DT_MX8, false);
+  } else if (g.dtype == DT_BF16) {
     if (scaled) PSD_LW_APPLY(DT_BF16, true);
     else PSD_LW_APPLY(DT_BF16, false);
   } else {
@@ -217,11 +227,11 @@ void lw_apply_src(const OptimHyper& h, const OptimDyn* dyn, float* master, const
 hipError_t launch_lw_norms(const OptimHyper& h, const OptimDyn* dyn, const float* master, const SourceList& g,
                            float* s1, float* s2, const LwTable& t, hipStream_t st, int grid_cap) {
   if (!lw_table_ok(t) || g.count < 1 || g.count > kMaxSources) return hipErrorInvalidValue;
-  if (g.dtype != DT_BF16 && g.dtype != DT_F32) return hipErrorInvalidValue;
+  if (!lw_src_ok(g)) return hipErrorInvalidValue;
   const int mode = source_scale_mode(g);
   if (mode < 0) return hipErrorInvalidValue;
   const int grid = lw_grid(t.n_chunks, grid_cap);
-  const bool bf = g.dtype == DT_BF16;
+  const bool bf = g.dtype == DT_BF16, mx = g.dtype == DT_MX8;
 #define PSD_LW_NORM(DT, LAMB)                                                                                          \
   do {                                                                                                                 \
     if (mode == 1)                                                                                                     \
@@ -230,11 +240,13 @@ hipError_t launch_lw_norms(const OptimHyper& h, const OptimDyn* dyn, const float
       hipLaunchKernelGGL((lw_norm_kernel<DT, LAMB, false>), dim3(grid), dim3(256), 0, st, h, dyn, master, g, s1, s2, t); \
   } while (0)
   if (h.kind == OPT_LARS) {
-    if (bf) PSD_LW_NORM(DT_BF16, false);
+    if (mx) PSD_LW_NORM(DT_MX8, false);
+    else if (bf) PSD_LW_NORM(DT_BF16, false);
     else PSD_LW_NORM(DT_F32, false);
   } else if (h.kind == OPT_LAMB) {
     if (!s1 || !s2) return hipErrorInvalidValue;
-    if (bf) PSD_LW_NORM(DT_BF16, true);
+    if (mx) PSD_LW_NORM(DT_MX8, true);
+    else if (bf) PSD_LW_NORM(DT_BF16, true);
     else PSD_LW_NORM(DT_F32, true);
   } else {
     return hipErrorInvalidValue;
@@ -259,7 +271,7 @@ hipError_t launch_lw_apply(const OptimHyper& h, const OptimDyn* dyn, float* mast
                            float* s2, uint16_t* shadow, const LwTable& t, hipStream_t st, int grid_cap) {
   if (!lw_table_ok(t)) return hipErrorInvalidValue;
   if (h.kind != OPT_LAMB && (g.count < 1 || g.count > kMaxSources)) return hipErrorInvalidValue;
-  if (g.dtype != DT_BF16 && g.dtype != DT_F32) return hipErrorInvalidValue;
+  if (!lw_src_ok(g)) return hipErrorInvalidValue;
   if (h.kind != OPT_LAMB && source_scale_mode(g) < 0) return hipErrorInvalidValue;
   const int grid = lw_grid(t.n_chunks, grid_cap);
   switch (h.kind) {

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "launchers.h"
+#include "mx_common.h"
 
 namespace psd {
 
@@ -51,6 +52,20 @@ __device__ __forceinline__ const float* stage_scales(const SourceList& g) {
   }
 }
 
+// 8 elements of an MX source (DT_MX8) at i (a multiple of 8): 8 e4m3 payload bytes and the E8M0 byte
+// of their 32-element block, dequantised as dequant_mx does: q * 2^(byte - 127) in fp32, exact (and
+// exactly representable in bf16) for normal-range values.
+__device__ __forceinline__ void load8_mx(const uint8_t* __restrict__ q, const uint8_t* __restrict__ sc, int64_t i,
+                                         float t[8]) {
+  const uint2 b = *reinterpret_cast<const uint2*>(q + i);
+  const float s = __uint_as_float((uint32_t)sc[i >> 5] << 23);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    t[e] = e4m3_to_f32((uint8_t)(b.x >> (8 * e))) * s;
+    t[e + 4] = e4m3_to_f32((uint8_t)(b.y >> (8 * e))) * s;
+  }
+}
+
 // out = scale * sum_k src_k[i..i+8), or with SCALED scale * sum_k sc[k] * src_k (one fma per source
 // element, in source order; sc[k] == 1 gives the unscaled bits)
 template <int SRC_DT, bool SCALED = false>
@@ -60,7 +75,9 @@ __device__ __forceinline__ void load_sources8(const SourceList& g, int64_t i, fl
   for (int e = 0; e < 8; ++e) out[e] = 0.f;
   for (int k = 0; k < g.count; ++k) {
     float t[8];
-    if (SRC_DT == DT_BF16)
+    if constexpr (SRC_DT == DT_MX8)
+      load8_mx(static_cast<const uint8_t*>(g.ptr[k]), g.mx_scale[k], i, t);
+    else if (SRC_DT == DT_BF16)
       load8_bf16(static_cast<const uint16_t*>(g.ptr[k]) + i, t);
     else
       load8_f32(static_cast<const float*>(g.ptr[k]) + i, t);

@@ -15,7 +15,8 @@
 namespace psd {
 
 // SCALED: out = scale * sum_k sc_k * src_k (SourceList::scale; the async plane's pre-reduce of a
-// clipped round of more than 16 pushes), one fma per source element in source order
+// clipped round of more than 16 pushes), one fma per source element in source order. SRC_DT DT_MX8:
+// the sources are MX e4m3 inbox slots (fp8 gradient push), dequantised in the load.
 template <int SRC_DT, int OUT_DT, bool SCALED = false>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(SourceList s, void* __restrict__ out, float scale,
                                                            int64_t n) {
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(SourceList s, void* _
     else
       store8_f32(static_cast<float*>(out) + i, acc);
   }
-  if (blockIdx.x == 0) {
+  if constexpr (SRC_DT != DT_MX8) if (blockIdx.x == 0) {  // tail; MX sources are whole 32-element blocks
     for (int64_t i = (nvec << 3) + threadIdx.x; i < n; i += blockDim.x) {
       float acc = 0.f;
       for (int k = 0; k < s.count; ++k) {
@@ -54,7 +55,7 @@ hipError_t launch_multi_reduce(const SourceList& s, void* out, int32_t out_dtype
   if (n <= 0) return hipSuccess;
   if (s.count < 1 || s.count > kMaxSources) return hipErrorInvalidValue;
   const int mode = source_scale_mode(s);
-  if (mode < 0) return hipErrorInvalidValue;
+  if (mode < 0 || !source_mx_ok(s, n)) return hipErrorInvalidValue;
   const int block = 256;
   const int grid = stream_grid((n >> 3) > 0 ? (n >> 3) : 1, block);
 #define PSD_RED(SD, OD)                                                                                          \
@@ -68,6 +69,8 @@ hipError_t launch_multi_reduce(const SourceList& s, void* out, int32_t out_dtype
   else if (s.dtype == DT_BF16 && out_dtype == DT_F32) PSD_RED(DT_BF16, DT_F32);
   else if (s.dtype == DT_F32 && out_dtype == DT_BF16) PSD_RED(DT_F32, DT_BF16);
   else if (s.dtype == DT_F32 && out_dtype == DT_F32) PSD_RED(DT_F32, DT_F32);
+  else if (s.dtype == DT_MX8 && out_dtype == DT_BF16) PSD_RED(DT_MX8, DT_BF16);
+  else if (s.dtype == DT_MX8 && out_dtype == DT_F32) PSD_RED(DT_MX8, DT_F32);
   else return hipErrorInvalidValue;
 #undef PSD_RED
   return hipGetLastError();

@@ -18,7 +18,11 @@
 // the block's E8M0 byte, written to the worker's q / scale copies (the fp8 convolutions read them)
 // and, dequantised, to its bf16 working weights -- the separate dequant_mx pass over the pulled
 // copy is gone.
+//
+// The quantising push (xfer_quant_kernel) is the same scatter with the MX quantisation of the
+// gradient fused in: 1 + 1/32 bytes per element cross to the owner's inbox instead of 2 (bf16).
 #include "common.h"
+#include "launchers.h"
 #include "launchers_xfer.h"
 #include "mx_common.h"
 
@@ -111,6 +115,151 @@ __global__ __launch_bounds__(256) void xfer_mx_kernel(XferMxList L) {
       }
     }
   }
+}
+
+namespace {
+
+// 16 consecutive elements (half a 32-element block) of a bf16 / fp32 source: 16-byte vector loads
+template <int SRC_DT>
+__device__ __forceinline__ void load16_src(const void* __restrict__ src, int64_t i, float (&t)[16]) {
+  if constexpr (SRC_DT == DT_BF16) {
+    load8_bf16(static_cast<const uint16_t*>(src) + i * 16, t);
+    load8_bf16(static_cast<const uint16_t*>(src) + i * 16 + 8, t + 8);
+  } else {
+    load8_f32(static_cast<const float*>(src) + i * 16, t);
+    load8_f32(static_cast<const float*>(src) + i * 16 + 8, t + 8);
+  }
+}
+
+// |x| as its bit pattern: for finite values the unsigned order of these is the order of |x|, and
+// anything above kMaxFiniteBits is an inf or a NaN -- one integer max finds a lane's amax AND whether
+// it holds a non-finite element (fmaxf would drop a NaN)
+constexpr uint32_t kMaxFiniteBits = 0x7f7fffffu;
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+
+// 4 e4m3 bytes of (a, b, c, d) * inv, a in the low byte: the clamp and the two packed hardware
+// conversions f32_to_e4m3 does one value at a time (round to nearest even, saturating at 448)
+__device__ __forceinline__ uint32_t q8x4(float a, float b, float c, float d, float inv) {
+  a = __builtin_amdgcn_fmed3f(a * inv, 448.f, -448.f);
+  b = __builtin_amdgcn_fmed3f(b * inv, 448.f, -448.f);
+  c = __builtin_amdgcn_fmed3f(c * inv, 448.f, -448.f);
+  d = __builtin_amdgcn_fmed3f(d * inv, 448.f, -448.f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (uint32_t)w;
+}
+
+}  // namespace
+
+// Quantising push: the gradient slices of one bucket for every owner it overlaps, bf16 / fp32 in,
+// MX e4m3 out (payload + one E8M0 byte per 32 elements), mapping as xfer_kernel. A lane takes 16
+// consecutive elements -- two (bf16) or four (fp32) 16-byte loads, ONE 16-byte non-temporal payload
+// store -- so a block is a lane pair: the pair agrees on amax with one quad-permute DPP, and the scale
+// bytes of 4 consecutive blocks are collected on every 8th lane (two lane exchanges), which stores
+// them as one dword (2-byte or byte stores only where the destination is not 4-byte aligned or the
+// segment ends inside the group). Scale and rounding: mx_exp_byte and the conversion of f32_to_e4m3
+// (four values per pair of packed instructions), as quant_mx_kernel.
+// The loop bounds are workgroup-uniform (a lane past the end idles through the exchanges), so the
+// bytes written do not depend on blocks_per_seg. Vector memory instructions only.
+// BLOCK: lanes per workgroup. A workgroup is the unit of the push's CU budget (blocks_per_seg), and a
+// small grid of 256-lane workgroups leaves one wave per SIMD, where the conversion arithmetic and the
+// memory latency of a pass add up instead of overlapping (the plain copy has no arithmetic to hide):
+// below kQuantWideBelow workgroups the launch takes 1024 lanes (four waves per SIMD; ResNet-50-size
+// gradient at 48 workgroups 93 -> 55 us, profiles/push_fp8.md). A grid that fills the GPU anyway keeps
+// 256 lanes with four items in flight per lane (1024-lane workgroups measured 2.6x slower there).
+constexpr int kQuantWideBelow = 128;
+template <int SRC_DT, int U, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void xfer_quant_kernel(XferQList L) {
+  const int s = (int)(blockIdx.x % (unsigned)L.count);
+  const int j = (int)(blockIdx.x / (unsigned)L.count);
+  const XferQSeg g = L.seg[s];
+  const int64_t n16 = g.n >> 4;  // 16-element items, two per block
+  const int64_t stride = (int64_t)L.blocks_per_seg * BLOCK * U;
+  for (int64_t b0 = (int64_t)j * BLOCK * U; b0 < n16; b0 += stride) {
+    float t[U][16];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = b0 + u * BLOCK + threadIdx.x;
+      if (i < n16) load16_src<SRC_DT>(g.src, i, t[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = b0 + u * BLOCK + threadIdx.x;
+      const bool act = i < n16;  // n16 is even: the two lanes of a block are active together
+      uint32_t mb = 0;  // this lane's amax, as bits
+      if (act) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mb = max(mb, abs_bits(t[u][e]));
+      }
+      const bool finite = mb <= kMaxFiniteBits;
+      // a NaN or an inf anywhere in the block: unit scale for the block (mx_exp_byte)
+      float m = __uint_as_float(finite ? mb : 0x7f800000u);
+      m = fmaxf(m, mx_dpp<0xB1>(m));  // quad_perm [1,0,3,2]: the block's two lanes agree
+      const int eb = mx_exp_byte(m, 448.f);
+      if (act) {
+        const float inv = __uint_as_float((uint32_t)(254 - eb) << 23);  // 2^(127 - eb)
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          w[k] = q8x4(t[u][4 * k], t[u][4 * k + 1], t[u][4 * k + 2], t[u][4 * k + 3], inv);
+        if (!finite) {
+          // a NaN or +-inf element travels as the e4m3 NaN byte 0x7F (e4m3fn has no inf, and the
+          // saturating conversion would turn an inf into 448): a diverged gradient must stay visible
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (abs_bits(t[u][4 * k + e]) > kMaxFiniteBits) w[k] = (w[k] & ~(0xFFu << (8 * e))) | (0x7Fu << (8 * e));
+        }
+        st16<true>(reinterpret_cast<u32x4*>(g.q_dst) + i, u32x4{w[0], w[1], w[2], w[3]});
+      }
+      // scale bytes: lane 4p gets blocks (2p, 2p + 1) of the wave, then lane 8r blocks 4r .. 4r + 3
+      uint32_t sw = (uint32_t)eb | ((uint32_t)__shfl_xor(eb, 2) << 8);
+      sw |= (uint32_t)__shfl_down((int)sw, 4) << 16;
+      if (act && (threadIdx.x & 7) == 0) {
+        const int64_t blk = i >> 1, left = (n16 - i) >> 1;
+        const int nb = left < 4 ? (int)left : 4;
+        uint8_t* p = g.sc_dst + blk;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+        if (nb == 4 && (a & 3) == 0) {
+          __builtin_nontemporal_store(sw, reinterpret_cast<uint32_t*>(p));
+        } else if ((a & 1) == 0 && (nb & 1) == 0) {
+          for (int h = 0; h < nb; h += 2)
+            __builtin_nontemporal_store((uint16_t)(sw >> (8 * h)), reinterpret_cast<uint16_t*>(p + h));
+        } else {
+          for (int h = 0; h < nb; ++h) __builtin_nontemporal_store((uint8_t)(sw >> (8 * h)), p + h);
+        }
+      }
+    }
+  }
+  // as xfer_kernel<.., NTS = true>: system-scope release per wave and a counted wait the compiler
+  // cannot drop, so the commit event behind this launch is never observed ahead of the bytes
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+hipError_t launch_xfer_quant(const XferQList& L, hipStream_t st) {
+  if (L.count <= 0) return hipSuccess;
+  if (L.count > kMaxXferSeg || L.blocks_per_seg < 1) return hipErrorInvalidValue;
+  for (int i = 0; i < L.count; ++i) {
+    const XferQSeg& g = L.seg[i];
+    if (g.n < 0 || g.n % 32 != 0 || !g.sc_dst ||
+        ((reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.q_dst)) & 15))
+      return hipErrorInvalidValue;
+  }
+  const dim3 grid((unsigned)(L.count * L.blocks_per_seg));
+  const bool wide = L.count * L.blocks_per_seg < kQuantWideBelow;
+  if (L.src_dtype != DT_BF16 && L.src_dtype != DT_F32) return hipErrorInvalidValue;
+#define PSD_XQ(DT, U, B) hipLaunchKernelGGL((xfer_quant_kernel<DT, U, B>), grid, dim3(B), 0, st, L)
+  if (L.src_dtype == DT_BF16) {
+    if (wide) PSD_XQ(DT_BF16, 2, 1024);
+    else PSD_XQ(DT_BF16, 4, 256);
+  } else {
+    if (wide) PSD_XQ(DT_F32, 2, 1024);
+    else PSD_XQ(DT_F32, 2, 256);
+  }
+#undef PSD_XQ
+  return hipGetLastError();
 }
 
 hipError_t launch_xfer(const XferList& L, hipStream_t st) {

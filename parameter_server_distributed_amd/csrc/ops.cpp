@@ -11,6 +11,8 @@
 
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <tuple>
 
 #include "glue.h"
 #include "kernels/launchers.h"
@@ -55,6 +57,18 @@ inline uint16_t f2bf(float f) {
   return (uint16_t)(u >> 16);
 }
 
+// OCP e4m3fn byte -> fp32 (kernels/mx_common.h e4m3_to_f32)
+inline float e4m3f(uint8_t b) {
+  const uint32_t sg = b >> 7, e = (b >> 3) & 0xF, m = b & 7;
+  if (e == 0xF && m == 7) return std::numeric_limits<float>::quiet_NaN();
+  const float v = e == 0 ? std::ldexp((float)m, -9) : std::ldexp(1.f + (float)m / 8.f, (int)e - 7);
+  return sg ? -v : v;
+}
+// element i of an MX source: q * 2^(scale byte - 127) in fp32 (ops dequantize_mx_ref)
+inline float mx_elem(const uint8_t* q, const uint8_t* sc, int64_t i) {
+  return e4m3f(q[i]) * std::ldexp(1.f, (int)sc[i >> 5] - 127);
+}
+
 // Scalar optimizer step: identical operation order to the device kernel (optim.hip).
 inline void cpu_update(const OptimHyper& h, float lr, float bc1, float bc2s, bool first, float& p, float g,
                        float& s1, float& s2) {
@@ -91,15 +105,38 @@ OptimDyn* dyn_ptr(const at::Tensor& dyn) {
   return reinterpret_cast<OptimDyn*>(dyn.data_ptr());
 }
 
+inline bool is_mx_payload(const at::Tensor& t) {
+  return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte;
+}
+
 SourceList make_sources(const std::vector<at::Tensor>& srcs, int64_t n, const at::Device& dev,
-                        const ScaleList& scales = {}) {
+                        const ScaleList& scales = {}, const MxScaleList& mx_scales = {}) {
   TORCH_CHECK(!srcs.empty() && (int)srcs.size() <= kMaxSources, "psd: 1..16 gradient sources required");
   SourceList s{};
   s.count = (int32_t)srcs.size();
-  s.dtype = dt_of(srcs[0]);
+  const bool mx = !mx_scales.empty();
+  if (mx) {
+    // MX sources: e4m3 payload + one E8M0 byte per 32 elements, for every source
+    TORCH_CHECK(mx_scales.size() == srcs.size(), "psd: MX scale bytes must be given for every gradient source or for "
+                "none (", mx_scales.size(), " of ", srcs.size(), " set)");
+    TORCH_CHECK(n % 32 == 0, "psd: MX gradient sources come in whole 32-element blocks, got ", n, " elements");
+    s.dtype = DT_MX8;
+  } else {
+    TORCH_CHECK(!is_mx_payload(srcs[0]), "psd: float8_e4m3fn / uint8 gradient sources are MX payloads: pass their "
+                "scale bytes (mx_scales)");
+    s.dtype = dt_of(srcs[0]);
+  }
   for (size_t k = 0; k < srcs.size(); ++k) {
     TORCH_CHECK(srcs[k].device() == dev, "psd: gradient source on wrong device");
-    TORCH_CHECK(dt_of(srcs[k]) == s.dtype, "psd: gradient sources must share a dtype");
+    if (mx) {
+      TORCH_CHECK(is_mx_payload(srcs[k]), "psd: MX gradient sources must be float8_e4m3fn or uint8");
+      const at::Tensor& b = mx_scales[k];
+      TORCH_CHECK(b.scalar_type() == at::kByte && b.is_contiguous() && b.numel() == n / 32 && b.device() == dev,
+                  "psd: an MX source's scales must be uint8 [numel / 32] on the master's device");
+      s.mx_scale[k] = b.data_ptr<uint8_t>();
+    } else {
+      TORCH_CHECK(dt_of(srcs[k]) == s.dtype, "psd: gradient sources must share a dtype");
+    }
     TORCH_CHECK(srcs[k].is_contiguous() && srcs[k].numel() == n, "psd: gradient source shape mismatch");
     s.ptr[k] = srcs[k].data_ptr();
   }
@@ -133,7 +170,7 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
                      const c10::optional<at::Tensor>& state1, const c10::optional<at::Tensor>& state2,
                      const c10::optional<at::Tensor>& shadow, const at::Tensor& dyn, int64_t kind, double momentum,
                      double dampening, bool nesterov, double weight_decay, double beta1, double beta2, double eps,
-                     bool maximize, const ScaleList& scales) {
+                     bool maximize, const ScaleList& scales, const MxScaleList& mx_scales) {
   TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous(), "psd: master must be contiguous fp32");
   ApplyArgs a;
   const int64_t n = a.n = master.numel();
@@ -166,7 +203,7 @@ ApplyArgs apply_args(const at::Tensor& master, const std::vector<at::Tensor>& gr
                 "psd: shadow must be contiguous bf16 like master");
     a.sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
   }
-  a.src = make_sources(grads, n, master.device(), scales);
+  a.src = make_sources(grads, n, master.device(), scales, mx_scales);
   TORCH_CHECK(dyn.device() == master.device(), "psd: dyn must live with master");
   if (master.is_cuda()) {
     check_aligned(master, "master");
@@ -184,8 +221,9 @@ inline float cpu_source(const SourceList& src, int64_t i, float gs) {
   float g = 0.f;
   const bool scaled = src.scale[0] != nullptr;
   for (int k = 0; k < src.count; ++k) {
-    const float x = src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
-                                         : static_cast<const float*>(src.ptr[k])[i];
+    const float x = src.dtype == DT_MX8    ? mx_elem(static_cast<const uint8_t*>(src.ptr[k]), src.mx_scale[k], i)
+                    : src.dtype == DT_BF16 ? bf16f(static_cast<const uint16_t*>(src.ptr[k])[i])
+                                           : static_cast<const float*>(src.ptr[k])[i];
     if (scaled) g = std::fma(*src.scale[k], x, g);
     else g += x;
   }
@@ -203,12 +241,12 @@ inline float cpu_lamb_u(float m, float v, float w, float bc1, float bc2s, float 
 void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
                   c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                   double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
-                  double eps, bool maximize, int64_t grid_cap, const ScaleList& scales) {
+                  double eps, bool maximize, int64_t grid_cap, const ScaleList& scales, const MxScaleList& mx_scales) {
   TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_ADAMW,
               "psd: fused_apply_ takes sgd / momentum / adam / adamw; lars and lamb need a layer table "
               "(fused_apply_lw_)");
   const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
-                                 weight_decay, beta1, beta2, eps, maximize, scales);
+                                 weight_decay, beta1, beta2, eps, maximize, scales, mx_scales);
   const OptimHyper& h = a.h;
   const int64_t n = a.n;
   float *s1 = a.s1, *s2 = a.s2;
@@ -298,10 +336,10 @@ void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c1
                      c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                      double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
                      double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
-                     int64_t grid_cap, const ScaleList& scales) {
+                     int64_t grid_cap, const ScaleList& scales, const MxScaleList& mx_scales) {
   TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_LAMB, "psd: unknown optimizer kind ", kind);
   const ApplyArgs a = apply_args(master, grads, state1, state2, shadow, dyn, kind, momentum, dampening, nesterov,
-                                 weight_decay, beta1, beta2, eps, maximize, scales);
+                                 weight_decay, beta1, beta2, eps, maximize, scales, mx_scales);
   // ---- the layer table (lw_table_build): shapes, dtypes, device, and the range it was built for
   TORCH_CHECK(layers.size() == 9, "psd: layer table must be the 9 tensors of lw_table_build");
   const at::Tensor& meta = layers[0];
@@ -440,10 +478,11 @@ void optim_advance_(at::Tensor dyn, double beta1, double beta2) {
   d->bc2 = 1.f - std::pow((float)beta2, (float)d->step);
 }
 
-void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales) {
+void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales,
+                   const MxScaleList& mx_scales) {
   TORCH_CHECK(out.is_contiguous(), "psd: out must be contiguous");
   const int64_t n = out.numel();
-  SourceList s = make_sources(srcs, n, out.device(), scales);
+  SourceList s = make_sources(srcs, n, out.device(), scales, mx_scales);
   const int32_t od = dt_of(out);
   TORCH_CHECK(od == DT_F32 || od == DT_BF16, "psd: reduce output must be fp32/bf16");
   if (out.is_cuda()) {
@@ -552,6 +591,43 @@ void xfer_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& d
   L.nt_store = nt_store ? 1 : 0;
   const c10::DeviceGuard g(srcs[0].device());
   hip_check(launch_xfer(L, stream_of(srcs[0])), "launch_xfer");
+}
+
+void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg) {
+  const int64_t n = x.numel();
+  TORCH_CHECK(x.is_contiguous() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16) && n % 32 == 0,
+              "psd: push_quant_mx_ takes a contiguous fp32 or bf16 tensor of a multiple of 32 elements");
+  TORCH_CHECK(is_mx_payload(q) && q.is_contiguous() && q.numel() == n && q.device() == x.device(),
+              "psd: push_quant_mx_ q must be float8_e4m3fn or uint8 like x");
+  TORCH_CHECK(scales.scalar_type() == at::kByte && scales.is_contiguous() && scales.numel() == n / 32 &&
+                  scales.device() == x.device(),
+              "psd: push_quant_mx_ scales must be uint8 [numel / 32] on x's device");
+  TORCH_CHECK(blocks_per_seg >= 0 && blocks_per_seg <= 1024, "psd: push_quant_mx_ blocks_per_seg in [0, 1024]");
+  if (n == 0) return;
+  if (x.is_cuda()) {
+    check_aligned(x, "push_quant_mx_ x");
+    check_aligned(q, "push_quant_mx_ q");
+    XferQList L{};
+    L.seg[L.count++] = XferQSeg{x.data_ptr(), static_cast<uint8_t*>(q.data_ptr()), scales.data_ptr<uint8_t>(), n};
+    L.blocks_per_seg = blocks_per_seg > 0 ? (int32_t)blocks_per_seg : xfer_blocks(n, 48);
+    L.src_dtype = dt_of(x);
+    const c10::DeviceGuard g(x.device());
+    hip_check(launch_xfer_quant(L, stream_of(x)), "launch_xfer_quant");
+    return;
+  }
+  // host: the operations of ops.quantize_mx_ref (the smallest 2^e with amax 2^-e <= 448, byte 127 for
+  // an all-zero or non-finite block, round to nearest even), then the non-finite rule
+  const at::Tensor xf = x.to(at::kFloat).view({-1, 32});
+  const at::Tensor amax = xf.abs().amax(1);
+  at::Tensor m, p;
+  std::tie(m, p) = at::frexp(amax / 448.f);
+  at::Tensor e = at::where(m == 0.5f, p - 1, p).clamp(-127, 127);
+  e = at::where((amax > 0) & at::isfinite(amax), e, at::zeros_like(e));
+  const at::Tensor v = (xf * at::exp2(-e.to(at::kFloat)).unsqueeze(1)).clamp(-448.f, 448.f);
+  at::Tensor qb = v.to(at::kFloat8_e4m3fn).view(at::kByte);
+  qb = at::where(at::isfinite(xf), qb, at::full({}, 0x7F, qb.options()));
+  q.view(at::kByte).view({-1, 32}).copy_(qb);
+  scales.copy_((e + 127).to(at::kByte));
 }
 
 void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts) {

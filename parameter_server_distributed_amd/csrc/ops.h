@@ -9,11 +9,17 @@ namespace psd {
 // null, or one fp32 tensor per gradient source on the master's device whose element 0 multiplies
 // that source. A mix of null and set entries is refused.
 using ScaleList = std::vector<c10::optional<at::Tensor>>;
+// MX gradient sources (the async plane's fp8 push; kernels/launchers.h DT_MX8): with `mx_scales` the
+// gradient sources are float8_e4m3fn (or uint8) payload tensors and mx_scales[k] is source k's uint8
+// E8M0 bytes [n / 32]; the consumer sums q * 2^(byte - 127). Empty: plain bf16 / fp32 sources. One
+// entry per source or none.
+using MxScaleList = std::vector<at::Tensor>;
 
 void fused_apply_(at::Tensor master, const std::vector<at::Tensor>& grads, c10::optional<at::Tensor> state1,
                   c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                   double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
-                  double eps, bool maximize, int64_t grid_cap = 0, const ScaleList& scales = {});
+                  double eps, bool maximize, int64_t grid_cap = 0, const ScaleList& scales = {},
+                  const MxScaleList& mx_scales = {});
 // The layer table of one contiguous flat range of `n` elements (kernels/launchers_optim_lw.h): tensors
 // (offset relative to the range, numel, ndim), every start on an `align`-element boundary. With
 // exclude_1d, tensors of ndim <= 1 get wd_mult 0 and adapt 0. Returns {meta (CPU: n, segments,
@@ -28,9 +34,16 @@ void fused_apply_lw_(at::Tensor master, const std::vector<at::Tensor>& grads, c1
                      c10::optional<at::Tensor> state2, c10::optional<at::Tensor> shadow, at::Tensor dyn, int64_t kind,
                      double momentum, double dampening, bool nesterov, double weight_decay, double beta1, double beta2,
                      double eps, bool maximize, double trust_coef, const std::vector<at::Tensor>& layers,
-                     int64_t grid_cap = 0, const ScaleList& scales = {});
+                     int64_t grid_cap = 0, const ScaleList& scales = {}, const MxScaleList& mx_scales = {});
 void optim_advance_(at::Tensor dyn, double beta1, double beta2);
-void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales = {});
+void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double scale, const ScaleList& scales = {},
+                   const MxScaleList& mx_scales = {});
+// The fp8 gradient push's quantiser on one contiguous range (kernels/xfer.hip xfer_quant_kernel; a
+// host implementation for CPU tensors): x (bf16 / fp32, numel % 32 == 0) -> q (float8_e4m3fn or uint8,
+// like x) and scales (uint8 [numel / 32]). Scale and rounding of quant_mx_; a NaN or +-inf element
+// becomes the e4m3 NaN byte 0x7F and its block takes the unit scale. blocks_per_seg: workgroups
+// (0: the transport's default for the size); the bytes do not depend on it.
+void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg = 0);
 // Global-norm clipping scalars of a flat gradient (kernels/launchers_clip.h): out[0] = c =
 // min(1, clip_norm / (n + 1e-6)), out[1] = n = ||flat||_2. `partials`: fp32 scratch, one element per
 // 8192 elements of `flat`. Two launches on the current stream, no allocation.

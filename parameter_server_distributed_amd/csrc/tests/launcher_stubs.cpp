@@ -41,4 +41,5 @@ hipError_t launch_sumsq_partials(const void*, int32_t, int64_t, float*, hipStrea
 hipError_t launch_clip_finalize(const float*, int64_t, float, float*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_xfer(const XferList&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_xfer_mx(const XferMxList&, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_xfer_quant(const XferQList&, hipStream_t) { return hipErrorNotSupported; }
 }  // namespace psd

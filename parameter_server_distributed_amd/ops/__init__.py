@@ -10,7 +10,7 @@ import torch
 
 from .. import native
 from .optim import (LayerTable, OptimConfig, OptimDyn, advance_, apply_no_advance_, fused_apply_,  # noqa: F401
-                    grad_clip_coef_, multi_reduce_)
+                    grad_clip_coef_, multi_reduce_, push_quant_mx_)
 
 FP8_E4M3_MAX = 448.0
 FP8_E5M2_MAX = 57344.0

@@ -151,17 +151,22 @@ class LayerTable:
 
 def fused_apply_(cfg: OptimConfig, dyn: OptimDyn, master: torch.Tensor, grads, state1=None, state2=None,
                  shadow=None, advance: bool = True, layers: LayerTable | None = None, grid_cap: int = 0,
-                 scales=None) -> None:
+                 scales=None, mx_scales=None) -> None:
     """In-place fused update of ``master`` from the sum of ``grads`` (list or tensor). ``layers``:
     the ``LayerTable`` of ``master``'s range -- required for lars / lamb and with ``exclude_1d``,
     rejected otherwise (a table that changes nothing would only hide a configuration mistake).
     ``scales``: one fp32 tensor per gradient source on ``master``'s device (element 0 is used): the
     update then sees ``grad_scale * sum_k scales[k] * grads[k]``, multiplied inside the same kernel
-    pass (the per-push clipping coefficients of the async plane). ``None``: the unscaled kernels."""
+    pass (the per-push clipping coefficients of the async plane). ``None``: the unscaled kernels.
+    ``mx_scales``: the gradient sources are MX e4m3 payloads (``float8_e4m3fn`` or uint8, a multiple
+    of 32 elements) and ``mx_scales[k]`` holds source k's uint8 E8M0 bytes ``[n / 32]``: the update
+    sees the sum of ``q * 2^(byte - 127)``, dequantised inside the same pass (the async plane's fp8
+    gradient push). One entry per source, or ``None`` for plain bf16 / fp32 sources."""
     C = native()
     if isinstance(grads, torch.Tensor):
         grads = [grads]
     scales = _check_scales(scales, len(grads))
+    mx_scales = _check_scales(mx_scales, len(grads), "mx_scales")
     if cfg.needs_layers and layers is None:
         raise ValueError(f"optimizer {cfg.kind!r} (exclude_1d={cfg.exclude_1d}) needs the tensor boundaries: pass "
                          f"layers=LayerTable(...)")
@@ -175,28 +180,42 @@ def fused_apply_(cfg: OptimConfig, dyn: OptimDyn, master: torch.Tensor, grads, s
         C.optim_advance_(dyn.t, cfg.beta1, cfg.beta2)
     if layers is None:
         C.fused_apply_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
-                       cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, grid_cap, scales)
+                       cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, grid_cap, scales,
+                       mx_scales)
     else:
         C.fused_apply_lw_(master, list(grads), state1, state2, shadow, dyn.t, cfg.code, cfg.momentum, cfg.dampening,
                           cfg.nesterov, cfg.weight_decay, cfg.beta1, cfg.beta2, cfg.eps, cfg.maximize, cfg.trust_coef,
-                          layers.t, grid_cap, scales)
+                          layers.t, grid_cap, scales, mx_scales)
 
 
-def _check_scales(scales, k: int) -> list:
+def _check_scales(scales, k: int, what: str = "scales") -> list:
     """``[]`` for no scales, else one tensor per source; a partial list is the caller's mistake."""
     if scales is None:
         return []
     scales = list(scales)
     if len(scales) != k or any(s is None for s in scales):
-        raise ValueError(f"scales must hold one tensor for each of the {k} gradient sources (or be None), got "
+        raise ValueError(f"{what} must hold one tensor for each of the {k} gradient sources (or be None), got "
                          f"{sum(s is not None for s in scales)} of {len(scales)} set")
     return scales
 
 
-def multi_reduce_(out: torch.Tensor, srcs, scale: float = 1.0, scales=None) -> None:
-    """``out = scale * sum_k srcs[k]``, or with ``scales`` ``scale * sum_k scales[k] * srcs[k]``."""
+def multi_reduce_(out: torch.Tensor, srcs, scale: float = 1.0, scales=None, mx_scales=None) -> None:
+    """``out = scale * sum_k srcs[k]``, or with ``scales`` ``scale * sum_k scales[k] * srcs[k]``;
+    with ``mx_scales`` the sources are MX e4m3 payloads and their E8M0 bytes (see ``fused_apply_``)."""
     srcs = list(srcs)
-    native().multi_reduce_(out, srcs, scale, _check_scales(scales, len(srcs)))
+    native().multi_reduce_(out, srcs, scale, _check_scales(scales, len(srcs)),
+                           _check_scales(mx_scales, len(srcs), "mx_scales"))
+
+
+def push_quant_mx_(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, blocks_per_seg: int = 0) -> None:
+    """The fp8 gradient push's quantiser on one contiguous range: ``x`` (bf16 / fp32, a multiple of
+    32 elements) -> ``q`` (``float8_e4m3fn`` or uint8 like ``x``) and ``scales`` (uint8 ``[n / 32]``),
+    OCP MX e4m3 with the scale and rounding of ``quantize_mx_ref``. Unlike ``quant_mx_`` a NaN or
+    +-inf element becomes the e4m3 NaN byte 0x7F (its block takes the unit scale 127), so a diverged
+    gradient reaches the owner as NaN. GPU: the quantising scatter kernel of the async push
+    (``csrc/kernels/xfer.hip``) with ``blocks_per_seg`` workgroups (0: the transport's default; the
+    bytes do not depend on it). CPU tensors take the host implementation."""
+    native().push_quant_mx_(x, q, scales, int(blocks_per_seg))
 
 
 def clip_chunks(n: int) -> int:

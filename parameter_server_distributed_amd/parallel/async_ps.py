@@ -42,6 +42,18 @@ csrc/kernels/clip.hip), sends the resulting 256-byte scalar block after the buck
 each source of a round by its worker's coefficient ``min(1, clip_norm / (||g|| + 1e-6))`` in the
 pass that sums them. ``grad_norm()`` reports the last step's (norm, coefficient).
 
+Gradient push compression (``push_dtype="fp8"``): a push carries the gradient as OCP MX e4m3, one
+E8M0 scale byte per 32 consecutive elements of the flat gradient buffer (blocks numbered from its
+element 0; every shard, bucket and tensor boundary is a multiple of 64 elements, so no block
+straddles one), with the scale and rounding of ``ops.quantize_mx_ref``. An inbox slot is then
+``shard_len`` payload bytes followed by ``shard_len / 32`` scale bytes. The owner's update of a round
+uses ``grad_scale * sum_k c_k * dq(q_k)``, ``dq`` the blockwise ``q * 2^(scale - 127)`` in fp32, in
+the same source order and with the same additions as the bf16 push -- weight decay, momentum, Adam
+moments, LARS / LAMB norms and the clip coefficients all see the dequantised sum. The clip norm is
+that of the gradient BEFORE quantisation (the norm pass runs over the worker's raw buffer). A NaN or
++-inf gradient element arrives as NaN (e4m3 byte 0x7F). The bytes do not depend on the grid, on
+``xfer_blocks`` or on the transport. No error feedback, no e5m2, no stochastic rounding.
+
 Layout: the parameters live in one flat working buffer (``.data`` views, reverse registration
 order, 64-element aligned) split into P contiguous shards (cut at the nearest tensor starts when the
 optimizer needs tensor boundaries: lars, lamb, ``exclude_1d``; each owner then applies with the
@@ -66,6 +78,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import native
+from ..ops import dequantize_mx_ref, quantize_mx_ref
 from ..ops.optim import LAYERWISE, LayerTable, OptimConfig, OptimDyn, clip_chunks, grad_clip_coef_
 from ..utils.config import fault, feature
 from .collective_ps import ALIGN, _flat_view, _round, install_fp8_weights, zero_grads_, zero_plan
@@ -123,7 +136,8 @@ class AsyncPS:
                  bucket_mb: float = 16.0, device: torch.device | None = None, ps_ranks: list[int] | None = None,
                  worker_ranks: list[int] | None = None, param_dtype: torch.dtype = torch.bfloat16, nbuf: int = 4,
                  timeout_s: float | None = None, overlap: bool = True, store=None, log: bool = False,
-                 semantics: str = "round", pull_dtype: str = "bf16", schedule: str = "free", xfer: str = "auto"):
+                 semantics: str = "round", pull_dtype: str = "bf16", schedule: str = "free", xfer: str = "auto",
+                 push_dtype: str = "bf16"):
         """``semantics``: "round" (K-batch async, default) or "push" (apply-on-arrival with the
         per-push hyperparameters of csrc/async_hyper.h); see the module docstring.
         ``schedule`` "fixed" ("round" semantics only): round r holds exactly every worker's step-r
@@ -140,7 +154,17 @@ class AsyncPS:
         gather kernel per bucket push / pull that reads or writes every owner's peer-mapped memory
         at once, one xGMI link per owner (kernels/xfer.hip); "copy": one hipMemcpyAsync per shard
         (one link at a time); "auto" (default): the kernel, falling back to the copies (on every
-        rank together, logged in ``xfer_mode``) if its start-up self-test fails."""
+        rank together, logged in ``xfer_mode``) if its start-up self-test fails.
+        ``push_dtype`` "fp8": a worker's gradient crosses to the owners as OCP MX e4m3 -- one E8M0
+        scale byte per 32 consecutive elements of the flat gradient buffer, 33/32 bytes per element
+        instead of 2 -- quantised inside the push (the scatter kernel, csrc/kernels/xfer.hip; with
+        ``xfer="copy"`` into a staging buffer first; on the host for ``device=cpu``), and the owner's
+        fused apply dequantises the inbox slots as it sums them (module docstring). "bf16" (default):
+        the raw gradient, exactly as before."""
+        if push_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"push_dtype must be bf16 or fp8, got {push_dtype!r}")
+        self.push_dtype = push_dtype
+        self.push_mx = push_dtype == "fp8"
         if xfer not in ("auto", "kernel", "copy"):
             raise ValueError(f"xfer must be auto, kernel or copy, got {xfer!r}")
         if semantics == "push" and optim.kind in LAYERWISE:
@@ -314,7 +338,7 @@ class AsyncPS:
             self.store.wait([f"{key}/ctl"])
         self.engine = C.AsyncEngine(self.rank, self.world, self.owners, self.worker_ranks, self.shard_off,
                                     self.shard_len, self.S, nbuf, shm, self.rank == 0, devidx, timeout_s,
-                                    torch.finfo(param_dtype).bits // 8, self.pull_mx, self.clip)
+                                    torch.finfo(param_dtype).bits // 8, self.pull_mx, self.clip, self.push_mx)
         if self.rank == 0:
             self.store.set(f"{key}/ctl", b"1")
         try:
@@ -389,7 +413,7 @@ class AsyncPS:
             v = self.master[k].to(self.param_dtype).double()
             self.store.set(f"{self._key}/ck/{tag}/{k}", f"{float(v.sum())!r} {float(v.abs().sum())!r}")
         if self.is_worker:
-            pat = (torch.arange(self.total, device=dev) % 251 + (self.rank + 1)).to(self.param_dtype)
+            pat = self._selftest_pattern(0, self.total, self.rank)
             self.engine.push(0, pat, 0, self.total, self._stream_ptr())
             if self.clip:  # the scalar slots travel by the same transport: round-trip a block too
                 blk = torch.arange(64, dtype=torch.float32, device=dev) + 0.5 * (self.rank + 1)
@@ -413,11 +437,19 @@ class AsyncPS:
         for k in self.my_shards:
             for wi, w in enumerate(self.worker_ranks):
                 v = self.engine.inbox_view(k, wi, 0)
-                want = (torch.arange(self.shard_off[k], self.shard_off[k] + self.shard_len[k], device=dev) % 251
-                        + (w + 1)).to(self.param_dtype)
-                if not torch.equal(v, want):
+                want = self._selftest_pattern(self.shard_off[k], self.shard_off[k] + self.shard_len[k], w)
+                if self.push_mx:
+                    # the pattern is exact in MX e4m3: payload and scale bytes must be its quantisation,
+                    # and dequantise back to it
+                    sv = self.engine.inbox_scales_view(k, wi, 0)
+                    wq, ws = quantize_mx_ref(want)
+                    if not (torch.equal(v.view(torch.uint8), wq.view(torch.uint8)) and torch.equal(sv, ws)
+                            and torch.equal(dequantize_mx_ref(v.view(torch.float8_e4m3fn), sv), want.float())):
+                        ok, why = False, f"rank {self.rank}: shard {k} MX inbox of worker {w} holds wrong data"
+                    sv.zero_()
+                elif not torch.equal(v, want):
                     ok, why = False, f"rank {self.rank}: shard {k} inbox of worker {w} holds wrong data"
-                v.zero_()
+                v.view(torch.uint8).zero_() if self.push_mx else v.zero_()
                 if self.clip:
                     sv = self.engine.scalar_view(k, wi, 0)
                     if not torch.equal(sv, torch.arange(64, dtype=torch.float32, device=dev) + 0.5 * (w + 1)):
@@ -427,6 +459,19 @@ class AsyncPS:
             torch.cuda.synchronize(dev)
         self._agree("selftest", "" if ok else why, attempt=tag)
         self.selftest_ok = True
+
+    def _selftest_pattern(self, lo: int, hi: int, rank: int) -> torch.Tensor:
+        """Elements [lo, hi) of the self-test gradient of worker ``rank``: depends on rank, shard
+        (through the position) and position. bf16 push: ``i % 251 + rank + 1``. fp8 push: that pattern
+        is not representable in e4m3, so small integers in [-7, 7] (every block holds all 15 of them:
+        its amax is 7) times a per-block power of two 2^((block + rank) % 9 - 4), which MX e4m3
+        holds exactly."""
+        i = torch.arange(lo, hi, device=self.device)
+        if not self.push_mx:
+            return (i % 251 + (rank + 1)).to(self.param_dtype)
+        v = (i * 7 + 3 * rank) % 15 - 7
+        e = ((i // 32 + rank) % 9 - 4).float()
+        return (v.float() * torch.exp2(e)).to(self.param_dtype)
 
     def _agree(self, tag: str, err: str, attempt: str = ""):
         """Collective status exchange through the store: every rank raises if any rank failed.
@@ -447,6 +492,12 @@ class AsyncPS:
     def params_flat(self) -> torch.Tensor:
         """The working weights of the current step (the buffer the model's parameters view)."""
         return self.pwork
+
+    @property
+    def push_bytes_per_elem(self) -> float:
+        """Bytes one gradient element takes on its way to the owner: the element size, or 33/32
+        (e4m3 payload + its share of the block's scale byte) under ``push_dtype="fp8"``."""
+        return 33.0 / 32.0 if self.push_mx else float(self.grads[0].element_size())
 
     def _barrier(self, tag: str):
         if self.world == 1:
@@ -707,7 +758,7 @@ class AsyncPS:
             if float(t[1]) > 0:
                 raise RuntimeError(f"push-size probe failed on a rank{f': {err}' if err is not None else ''}")
             el = float(t[0])
-            out[mb] = round(self.total * elem * self.P / max(el, 1e-9) / 1e9, 1) if el > 0 else None
+            out[mb] = round(self.total * self.push_bytes_per_elem * self.P / max(el, 1e-9) / 1e9, 1) if el > 0 else None
         return out
 
     def probe_xfer_blocks(self, caps=(8, 16, 24, 32, 48, 64, 96), reps: int = 3, keep: float = 0.9) -> dict:
@@ -755,7 +806,7 @@ class AsyncPS:
                 self.engine.set_xfer_blocks(old)
                 raise RuntimeError(f"xfer workgroup probe failed on a rank{f': {err}' if err is not None else ''}")
             el = float(t[0])
-            res[int(cap)] = round(self.total * g.element_size() / max(el, 1e-9) / 1e9, 1) if el > 0 else None
+            res[int(cap)] = round(self.total * self.push_bytes_per_elem / max(el, 1e-9) / 1e9, 1) if el > 0 else None
         ok = {c: v for c, v in res.items() if v}
         if not ok:  # no worker timed anything (a pure-owner world): keep the default
             self.engine.set_xfer_blocks(old)
@@ -788,7 +839,8 @@ class AsyncPS:
             e.record()
             e.synchronize()
             ms = s.elapsed_time(e) / reps
-            out[f"{name}_GBps"] = round(self.total * g.element_size() / (ms * 1e-3) / 1e9, 1)
+            bpe = self.push_bytes_per_elem if name == "push" else g.element_size()
+            out[f"{name}_GBps"] = round(self.total * bpe / (ms * 1e-3) / 1e9, 1)
         return out
 
     def abort(self):
@@ -886,7 +938,7 @@ class AsyncPS:
     def _layout_meta(self) -> dict:
         return {"world": self.world, "owners": self.owners, "workers": self.worker_ranks, "P": self.P,
                 "shard_off": self.shard_off, "shard_len": self.shard_len, "total": self.total,
-                "staleness": self.S, "semantics": self.semantics, "round": self.round,
+                "staleness": self.S, "semantics": self.semantics, "round": self.round, "push_dtype": self.push_dtype,
                 "optimizer": self.cfg.to_dict(), "params": [(n, list(p.shape), o, k) for (n, p, o, k) in self._layout]}
 
     def save(self, prefix: str, blocking: bool = True):
@@ -958,6 +1010,10 @@ class AsyncPS:
                 raise ValueError(f"checkpoint {prefix}: {key} {m[key]} does not match this run's {mine[key]}")
         if m["optimizer"]["kind"] != self.cfg.kind:
             raise ValueError(f"checkpoint optimizer {m['optimizer']['kind']} != {self.cfg.kind}")
+        # the push dtype is recorded with the optimizer settings (a checkpoint from before it existed
+        # was a bf16 push). A drained checkpoint holds no in-flight gradient, so resuming with the
+        # other push dtype is supported: the masters, state, versions and clocks do not depend on it.
+        self.resumed_push_dtype = m.get("push_dtype", "bf16")
         self.engine.stop()
         i = 0
         for k in self.my_shards:
@@ -1099,4 +1155,5 @@ class AsyncPS:
     def describe(self) -> str:
         return (f"AsyncPS(world={self.world}, shards={self.P} on ranks {self.owners}, workers={self.worker_ranks}, "
                 f"SSP bound={self.S}, buckets={len(self.buckets)}, params={self.num_params() / 1e6:.2f}M, "
-                f"memory={self.engine.memory_kind()}, xfer={self.xfer_mode})")
+                f"memory={self.engine.memory_kind()}, xfer={self.xfer_mode}"
+                f"{', push=fp8' if self.push_mx else ''})")

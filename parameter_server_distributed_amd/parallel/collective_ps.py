@@ -128,7 +128,16 @@ class CollectivePS:
                  overlap: bool = True, grad_dtype: torch.dtype = torch.bfloat16,
                  param_dtype: torch.dtype = torch.bfloat16, device: torch.device | None = None,
                  ps_ranks: list[int] | None = None, worker_ranks: list[int] | None = None,
-                 pull_dtype: str = "bf16", push_mode: str = "auto"):
+                 pull_dtype: str = "bf16", push_mode: str = "auto", push_dtype: str = "bf16"):
+        if push_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"push_dtype must be bf16 or fp8, got {push_dtype!r}")
+        if push_dtype == "fp8":
+            # the reduce-scatter sums the workers' buckets in flight: there is no per-worker inbox
+            # slot whose blocks an owner could dequantise
+            raise ValueError("push_dtype='fp8' is not supported on the collective plane: its reduce-scatter sums "
+                             "the workers' gradients in flight, so no owner ever holds one worker's quantised "
+                             "blocks; use the async plane (parallel.async_ps.AsyncPS), which pushes MX e4m3 into "
+                             "per-worker inbox slots and dequantises inside the owner's fused apply")
         if optim.needs_layers:
             # every bucket is cut into P equal slices, so tensors straddle owners and a tensor's norm
             # would need a cross-rank exchange per step
