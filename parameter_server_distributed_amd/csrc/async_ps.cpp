@@ -108,35 +108,10 @@ void* map_shm(const std::string& name, size_t bytes, bool create) {
 
 }  // namespace
 
-namespace {
-// utils/config.py FEATURES for the native side: PSD_FEATURES="name=0|1,..." (else the default)
-bool psd_feature_on(const char* name, bool dflt) {
-  const char* env = std::getenv("PSD_FEATURES");
-  if (!env) return dflt;
-  const std::string all(env), key(name);
-  size_t pos = 0;
-  while (pos <= all.size()) {
-    const size_t end = std::min(all.find(',', pos), all.size());
-    const std::string item = all.substr(pos, end - pos);
-    const size_t eq = item.find('=');
-    auto trim = [](std::string t) {
-      const size_t a = t.find_first_not_of(" \t"), b = t.find_last_not_of(" \t");
-      return a == std::string::npos ? std::string() : t.substr(a, b - a + 1);
-    };
-    if (trim(item.substr(0, eq)) == key) {
-      const std::string v = eq == std::string::npos ? "1" : trim(item.substr(eq + 1));
-      return !(v == "0" || v == "false" || v == "off" || v == "no");
-    }
-    pos = end + 1;
-  }
-  return dflt;
-}
-}  // namespace
-
 AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers,
                          std::vector<int64_t> shard_off, std::vector<int64_t> shard_len, int staleness, int nbuf,
                          std::string shm_name, bool create, int device, double timeout_s, int elem_bytes, bool mx,
-                         bool clip, bool push_mx)
+                         bool clip, bool push_mx, bool cached_local, bool apply_background)
     : rank_(rank),
       world_(world),
       S_(staleness),
@@ -202,11 +177,12 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
     if (device_ >= 0) {
       const c10::DeviceGuard g(c10::Device(c10::DeviceType::CUDA, (c10::DeviceIndex)device_));
       // uncached fine-grained: peers' DMA writes / reads are coherent without cache maintenance.
-      // A world of one has no peer: plain device memory there (feature async_cached_local) -- the
+      // A world of one has no peer: plain device memory there (`cached_local`: the caller's feature
+      // async_cached_local, utils/config.py) -- the
       // pushes / pulls and the owner's apply then run at cached-HBM speed instead of the ~0.2 TB/s a
       // copy into uncached memory gets (BERT-base: 14 push copies of 16 MB, 74 us each)
       hipError_t e = hipErrorUnknown;
-      if (world_ == 1 && psd_feature_on("async_cached_local", true)) {
+      if (world_ == 1 && cached_local) {
         e = hipMalloc(&local_mem_, (size_t)local_bytes_);
         mem_kind_ = "device";
       }
@@ -260,17 +236,18 @@ AsyncEngine::AsyncEngine(int rank, int world, std::vector<int> owners, std::vect
           st.scal.push_back(at::from_blob(scalar_ptr(k, wi, s), {kScalarBytes / 4}, opt.dtype(at::kFloat)));
     st.busy.assign(nbuf_, false);
   }
+  // With an SSP bound S >= 1 a round's apply has a whole worker step of slack (the pull that needs
+  // it comes one step later), so it runs in the background (`apply_background`: the caller's feature
+  // async_apply_background): a normal-priority stream and at most
+  // 2 workgroups per CU. A high-priority, 2048-workgroup apply took every CU slot for its ~0.85 ms
+  // and held back the compute stream's next kernels (the gradient-zeroing fills waited up to
+  // 215 us for a slot in a BERT-base kernel trace; step time neutral within the box spread in
+  // plain runs, profiles/r6/boundary/README.md). At S = 0 the apply is on the critical path:
+  // high priority, full grid. A CPU engine resolves the same flags (its host apply ignores the cap).
+  apply_bg_ = S_ >= 1 && apply_background;
+  apply_cap_ = apply_bg_ ? 512 : 0;
   if (device_ >= 0) {
-    // With an SSP bound S >= 1 a round's apply has a whole worker step of slack (the pull that needs
-    // it comes one step later), so it runs in the background: a normal-priority stream and at most
-    // 2 workgroups per CU. A high-priority, 2048-workgroup apply took every CU slot for its ~0.85 ms
-    // and held back the compute stream's next kernels (the gradient-zeroing fills waited up to
-    // 215 us for a slot in a BERT-base kernel trace; step time neutral within the box spread in
-    // plain runs, profiles/r6/boundary/README.md). At S = 0 the apply is on the critical path:
-    // high priority, full grid.
-    const bool bg = S_ >= 1 && psd_feature_on("async_apply_background", true);
-    apply_cap_ = bg ? 512 : 0;
-    ps_stream_ = c10::hip::getStreamFromPool(/*isHighPriority=*/!bg, (c10::DeviceIndex)device_).stream();
+    ps_stream_ = c10::hip::getStreamFromPool(/*isHighPriority=*/!apply_bg_, (c10::DeviceIndex)device_).stream();
     xfer_kernel_ = true;
   }
 }
@@ -601,11 +578,9 @@ bool AsyncEngine::poll_once() {
     if (!done(p.event)) break;
     ShardCtl& s = ctl_->shard[p.shard];
     const int64_t v = s.version.load() + 1;
-    s.buf_version[p.buf].store(v);
-    s.latest.store(p.buf);
-    s.version.store(v);
-    for (const RoundItem& it : p.items) s.clock[it.wi].fetch_add(1);
-    shards_[p.shard].busy[p.buf] = false;
+    // histogram and log first: a wait on the clocks (wait_all_applied, drain) that returns must find
+    // every apply it waited for recorded (the clocks used to advance first, and a histogram or log
+    // read right after a drain could miss the last round)
     {
       std::lock_guard<std::mutex> g(hist_mu_);
       for (const RoundItem& it : p.items) {
@@ -613,6 +588,11 @@ bool AsyncEngine::poll_once() {
         if (log_on_) log_.push_back({p.shard, workers_[it.wi], it.step, it.staleness, v});
       }
     }
+    s.buf_version[p.buf].store(v);
+    s.latest.store(p.buf);
+    s.version.store(v);
+    for (const RoundItem& it : p.items) s.clock[it.wi].fetch_add(1);
+    shards_[p.shard].busy[p.buf] = false;
     n_applies_.fetch_add(1);
     if (p.event) (void)hipEventDestroy(static_cast<hipEvent_t>(p.event));
     pending_.pop_front();

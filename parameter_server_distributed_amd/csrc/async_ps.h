@@ -56,7 +56,8 @@ class AsyncEngine {
  public:
   AsyncEngine(int rank, int world, std::vector<int> owners, std::vector<int> workers, std::vector<int64_t> shard_off,
               std::vector<int64_t> shard_len, int staleness, int nbuf, std::string shm_name, bool create, int device,
-              double timeout_s, int elem_bytes = 2, bool mx = false, bool clip = false, bool push_mx = false);
+              double timeout_s, int elem_bytes = 2, bool mx = false, bool clip = false, bool push_mx = false,
+              bool cached_local = true, bool apply_background = true);
   ~AsyncEngine();
 
   // -- memory exchange (collective through the caller's store) --
@@ -122,6 +123,11 @@ class AsyncEngine {
   std::vector<int64_t> clocks(int shard) const;
   std::vector<int> my_shards() const { return my_shards_; }
   std::string memory_kind() const { return mem_kind_; }
+  // the owner's apply as resolved in the constructor (a CPU engine reports the same flags; it has no
+  // stream to put them on): workgroup cap of the apply kernels (0: the launchers' own grid, 512 in
+  // the background) and whether the apply runs in the background (normal priority, capped)
+  int apply_grid_cap() const { return apply_cap_; }
+  bool apply_background() const { return apply_bg_; }
   std::string error() const;
   // fail every rank's waits now (an external failure detector, e.g. the coordinator expired a peer)
   void inject_error(const std::string& msg);
@@ -197,6 +203,7 @@ class AsyncEngine {
   bool xfer_kernel_ = false;  // set in the constructor: true on a GPU engine
   int xfer_cap_ = 48;         // set_xfer_blocks
   int apply_cap_ = 0;         // fused-apply workgroups (0: the launcher's 2048); see the constructor
+  bool apply_bg_ = false;     // S >= 1 and the caller's apply_background: normal-priority stream, capped grid
   double timeout_s_;
   double dead_after_s_ = 10.0;  // a peer's engine silent this long is presumed dead (PSD_ASYNC_DEAD_S)
   int esz_;

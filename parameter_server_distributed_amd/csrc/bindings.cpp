@@ -326,11 +326,12 @@ PYBIND11_MODULE(_C, m) {
   // ---- asynchronous apply-on-arrival PS over peer memory ----
   py::class_<AsyncEngine>(m, "AsyncEngine")
       .def(py::init<int, int, std::vector<int>, std::vector<int>, std::vector<int64_t>, std::vector<int64_t>, int, int,
-                    std::string, bool, int, double, int, bool, bool, bool>(),
+                    std::string, bool, int, double, int, bool, bool, bool, bool, bool>(),
            py::arg("rank"), py::arg("world"), py::arg("owners"), py::arg("workers"), py::arg("shard_off"),
            py::arg("shard_len"), py::arg("staleness"), py::arg("nbuf"), py::arg("shm_name"), py::arg("create"),
            py::arg("device"), py::arg("timeout_s"), py::arg("elem_bytes") = 2, py::arg("mx") = false,
-           py::arg("clip") = false, py::arg("push_mx") = false)
+           py::arg("clip") = false, py::arg("push_mx") = false, py::arg("cached_local") = true,
+           py::arg("apply_background") = true)
       .def("local_desc", [](const AsyncEngine& e) { return py::bytes(e.local_desc()); })
       .def("attach_peer", [](AsyncEngine& e, int r, py::bytes d) { e.attach_peer(r, std::string(d)); })
       .def("set_shard_state", &AsyncEngine::set_shard_state)
@@ -359,6 +360,8 @@ PYBIND11_MODULE(_C, m) {
       .def("clocks", &AsyncEngine::clocks)
       .def("my_shards", &AsyncEngine::my_shards)
       .def("memory_kind", &AsyncEngine::memory_kind)
+      .def("apply_grid_cap", &AsyncEngine::apply_grid_cap)
+      .def("apply_background", &AsyncEngine::apply_background)
       .def("set_xfer", &AsyncEngine::set_xfer)
       .def("xfer_mode", &AsyncEngine::xfer_mode)
       .def("set_xfer_blocks", &AsyncEngine::set_xfer_blocks)

@@ -338,7 +338,9 @@ class AsyncPS:
             self.store.wait([f"{key}/ctl"])
         self.engine = C.AsyncEngine(self.rank, self.world, self.owners, self.worker_ranks, self.shard_off,
                                     self.shard_len, self.S, nbuf, shm, self.rank == 0, devidx, timeout_s,
-                                    torch.finfo(param_dtype).bits // 8, self.pull_mx, self.clip, self.push_mx)
+                                    torch.finfo(param_dtype).bits // 8, self.pull_mx, self.clip, self.push_mx,
+                                    cached_local=feature("async_cached_local"),
+                                    apply_background=feature("async_apply_background"))
         if self.rank == 0:
             self.store.set(f"{key}/ctl", b"1")
         try:

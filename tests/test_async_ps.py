@@ -211,6 +211,35 @@ def test_async_world1_sync_matches_reference():
     ps.close()
 
 
+def test_async_engine_takes_its_features_from_python(monkeypatch):
+    """the engine used to parse PSD_FEATURES itself, so ``set_feature`` never reached it
+    and the bench's features() JSON could name an apply mode the engine did not use. AsyncPS now hands
+    the resolved features over and the engine reports what it runs with (a CPU engine too: it
+    resolves the flags, though it has no stream to apply them to)."""
+    from parameter_server_distributed_amd.utils.config import set_feature
+
+    monkeypatch.delenv("PSD_FEATURES", raising=False)
+
+    def report(stale):
+        torch.manual_seed(0)
+        spec = models.build("mlp", torch.device("cpu"), torch.float32, hidden=64)
+        ps = AsyncPS(spec.model, OptimConfig(**CFG), staleness=stale, bucket_mb=0.0005, param_dtype=torch.float32)
+        try:
+            return ps.engine.apply_background(), ps.engine.apply_grid_cap(), ps.engine.memory_kind()
+        finally:
+            ps.close()
+
+    try:
+        set_feature("async_apply_background", False)
+        off = report(1)
+    finally:
+        set_feature("async_apply_background", None)
+    assert off[0] is False and off[1:] == (0, "host-shm"), off
+    on = report(1)
+    assert on[0] is True and on[1:] == (512, "host-shm"), on
+    assert report(0) == (False, 0, "host-shm")  # S = 0: the apply is on the critical path whatever the feature
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,stale", [(2, 1), (3, 0)])
 def test_async_gpu_ipc_matches_replay(tmp_path, gpu, world, stale):

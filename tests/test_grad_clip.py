@@ -245,8 +245,13 @@ def _ref_step(cfg, lay, w, srcs, scales, s1, s2, step, dt):
             buf = gg.clone() if step == 1 else mom * s1[sl] + (1 - S(cfg.dampening)) * gg
             s1[sl] = buf
             w[sl] = wt - cfg.lr * buf
-        else:  # adamw
-            wt = wt * (1 - S(cfg.lr) * S(wd))
+        elif cfg.kind == "sgd":
+            w[sl] = wt - cfg.lr * (gt + wd * wt)
+        else:  # adam (decay in the gradient) / adamw (decoupled decay)
+            if cfg.kind == "adam":
+                gt = gt + wd * wt
+            else:
+                wt = wt * (1 - S(cfg.lr) * S(wd))
             m = b1 * s1[sl] + (1 - b1) * gt
             v = b2 * s2[sl] + (1 - b2) * gt * gt
             s1[sl], s2[sl] = m, v
