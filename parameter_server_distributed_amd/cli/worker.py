@@ -49,6 +49,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--push-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="elastic, --ps-plane async: fp8 pushes each gradient as OCP MX e4m3 (33/32 bytes per "
                          "element instead of 2), dequantised inside the owner's fused apply")
+    ap.add_argument("--push-error-feedback", action="store_true",
+                    help="elastic, --ps-plane async, --push-dtype fp8: each worker keeps the quantisation error of "
+                         "its pushes in an fp32 residual and adds it to the next gradient before quantising")
     ap.add_argument("--check-every", type=int, default=5, help="elastic: membership check period (steps)")
     ap.add_argument("--min-workers", type=int, default=1, help="elastic: workers to wait for at start")
     ap.add_argument("--elastic-ckpt-dir", default="",
@@ -151,10 +154,12 @@ def elastic_main(a) -> int:
         if a.ps_plane == "async":
             return AsyncPS(model, optim, num_shards=shards, staleness=a.staleness, bucket_mb=a.bucket_mb, device=dev,
                            overlap=not spec.tied_weights, param_dtype=dtype,
-                           pull_dtype=a.pull_dtype if dev.type == "cuda" else "bf16", push_dtype=a.push_dtype)
+                           pull_dtype=a.pull_dtype if dev.type == "cuda" else "bf16", push_dtype=a.push_dtype,
+                           push_error_feedback=a.push_error_feedback)
         return CollectivePS(model, optim, transport, num_shards=shards, staleness=a.staleness,
                             bucket_mb=a.bucket_mb, device=dev, overlap=not spec.tied_weights,
-                            grad_dtype=dtype, param_dtype=dtype, pull_dtype=a.pull_dtype, push_dtype=a.push_dtype)
+                            grad_dtype=dtype, param_dtype=dtype, pull_dtype=a.pull_dtype, push_dtype=a.push_dtype,
+                            push_error_feedback=a.push_error_feedback)
 
     def make_trainer(ps):
         return Trainer(spec.model, spec.loss, ps, batch, use_graph=False)

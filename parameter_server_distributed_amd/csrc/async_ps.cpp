@@ -946,14 +946,24 @@ std::vector<int64_t> AsyncEngine::pull_impl(int64_t step, char* dst, char* dst_s
   return pulled;
 }
 
-void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, int64_t hi, int64_t stream) {
+void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, int64_t hi, int64_t stream,
+                       c10::optional<at::Tensor> residual) {
   TORCH_CHECK(my_wi_ >= 0, "psd async: rank ", rank_, " is not a worker");
   TORCH_CHECK(grads_flat.is_contiguous() && grads_flat.element_size() == esz_, "psd async: gradient buffer dtype");
+  const bool ef = residual.has_value() && residual->defined();
+  TORCH_CHECK(!ef || push_mx_, "psd async: a push residual (error feedback) needs an MX-push engine");
   check_error();
   const char* src = static_cast<const char*>(grads_flat.data_ptr());
   const int slot = (int)(step % (S_ + 1));
   if (push_mx_) {
-    push_mx_range(grads_flat, lo, hi, slot, stream);
+    float* resid = nullptr;
+    if (ef) {
+      TORCH_CHECK(residual->scalar_type() == at::kFloat && residual->is_contiguous() &&
+                      residual->numel() == grads_flat.numel() && residual->device() == grads_flat.device(),
+                  "psd async: the push residual is contiguous fp32, laid out like the gradient buffer on its device");
+      resid = residual->data_ptr<float>();
+    }
+    push_mx_range(grads_flat, lo, hi, slot, stream, resid);
     return;
   }
   bool remote = false, al = true;
@@ -994,8 +1004,11 @@ void AsyncEngine::push(int64_t step, const at::Tensor& grads_flat, int64_t lo, i
 // peer destinations alike (kernels/xfer.hip xfer_quant_kernel). Copy transport: the range is
 // quantised into the gradient buffer's staging pair by the same kernel, then one hipMemcpyAsync
 // each for a slice's payload and scales. Host engine: quantised on the host (ops.cpp
-// push_quant_mx_). The three give the same bytes.
-void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream) {
+// push_quant_mx_). The three give the same bytes. resid (error feedback, null: off): the worker's
+// fp32 residual, laid out like the gradient buffer; the launch (or host pass) that quantises a range
+// adds its slice before and leaves what the quantiser dropped in it.
+void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream,
+                                float* resid) {
   TORCH_CHECK(lo % 32 == 0 && hi % 32 == 0 && lo >= 0 && hi <= grads_flat.numel(),
               "psd async: an MX push covers whole 32-element blocks of the gradient buffer, got [", lo, ", ", hi, ")");
   const char* src = static_cast<const char*>(grads_flat.data_ptr());
@@ -1011,8 +1024,10 @@ void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_
       const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
       if (a >= b) continue;
       const auto bytes = at::TensorOptions().dtype(at::kByte);
+      c10::optional<at::Tensor> r;
+      if (resid) r = at::from_blob(resid + a, {b - a}, at::TensorOptions().dtype(at::kFloat));
       push_quant_mx_(grads_flat.narrow(0, a, b - a), at::from_blob(q_dst(k, a), {b - a}, bytes),
-                     at::from_blob(sc_dst(k, a), {(b - a) / 32}, bytes), 0);
+                     at::from_blob(sc_dst(k, a), {(b - a) / 32}, bytes), 0, r);
     }
     return;
   }
@@ -1025,7 +1040,7 @@ void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_
     for (int k = 0; k < P; ++k) {
       const int64_t a = std::max(lo, shard_off_[k]), b = std::min(hi, shard_off_[k] + shard_len_[k]);
       if (a >= b) continue;
-      L.seg[L.count++] = XferQSeg{src + a * esz_, q_dst(k, a), sc_dst(k, a), b - a};
+      L.seg[L.count++] = XferQSeg{src + a * esz_, q_dst(k, a), sc_dst(k, a), b - a, resid ? resid + a : nullptr};
       mx = std::max(mx, b - a);
     }
     L.blocks_per_seg = xfer_blocks(mx * esz_, xfer_cap_);
@@ -1040,7 +1055,7 @@ void AsyncEngine::push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_
   }
   uint8_t* sq = it->second.first.data_ptr<uint8_t>();
   uint8_t* ss = it->second.second.data_ptr<uint8_t>();
-  L.seg[L.count++] = XferQSeg{src + lo * esz_, sq + lo, ss + lo / 32, hi - lo};
+  L.seg[L.count++] = XferQSeg{src + lo * esz_, sq + lo, ss + lo / 32, hi - lo, resid ? resid + lo : nullptr};
   L.blocks_per_seg = xfer_blocks((hi - lo) * esz_, xfer_cap_);
   hip_ok(launch_xfer_quant(L, st), "launch_xfer_quant(stage)");
   for (int k = 0; k < P; ++k) {

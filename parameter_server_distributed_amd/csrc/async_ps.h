@@ -101,7 +101,11 @@ class AsyncEngine {
   // push may take from the backward pass running beside it (bench.py probes it at N > 1)
   void set_xfer_blocks(int cap);
   int xfer_blocks_cap() const { return xfer_cap_; }
-  void push(int64_t step, const at::Tensor& grads_flat, int64_t lo, int64_t hi, int64_t stream);
+  // residual (MX-push engines; error feedback): the worker's fp32 residual, laid out like the gradient
+  // buffer. The push quantises grads + residual over [lo, hi) and leaves the quantisation error in
+  // residual[lo, hi), in place, on `stream`: pushes of one range must be stream-ordered.
+  void push(int64_t step, const at::Tensor& grads_flat, int64_t lo, int64_t hi, int64_t stream,
+            c10::optional<at::Tensor> residual = c10::nullopt);
   // clip engines: this worker's 256-byte scalar block of `step` (element 0: its clipping coefficient,
   // kernels/launchers_clip.h) into its scalar slot at every shard, by the push transport; on the
   // stream that commits, before commit(), so the scalars land behind the same event as the buckets
@@ -183,7 +187,7 @@ class AsyncEngine {
   void apply_into(ShardState& st, const std::vector<at::Tensor>& g, const std::vector<at::Tensor>& sc,
                   const std::vector<at::Tensor>& mxs, int buf);
   // push_mx: [lo, hi) of the gradient buffer -> MX e4m3 in this worker's inbox slots
-  void push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream);
+  void push_mx_range(const at::Tensor& grads_flat, int64_t lo, int64_t hi, int slot, int64_t stream, float* resid);
   int free_buf(int shard) const;
   bool claim_buf(int shard, int b);
   static bool done(void* event);

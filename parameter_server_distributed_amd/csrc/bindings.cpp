@@ -57,7 +57,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("multi_reduce_", &multi_reduce_, py::arg("out"), py::arg("srcs"), py::arg("scale") = 1.0,
         py::arg("scales") = ScaleList{}, py::arg("mx_scales") = MxScaleList{});
   m.def("push_quant_mx_", &push_quant_mx_, py::arg("x"), py::arg("q"), py::arg("scales"),
-        py::arg("blocks_per_seg") = 0);
+        py::arg("blocks_per_seg") = 0, py::arg("residual") = py::none());
   m.def("grad_clip_coef_", &grad_clip_coef_, py::arg("flat"), py::arg("clip_norm"), py::arg("out"), py::arg("partials"),
         py::arg("grid_cap") = 0);
   m.def("pack_cast_", &pack_cast_, py::arg("srcs"), py::arg("dsts"));
@@ -346,7 +346,8 @@ PYBIND11_MODULE(_C, m) {
       .def("free_local", &AsyncEngine::free_local)
       .def("pull", &AsyncEngine::pull, py::call_guard<py::gil_scoped_release>())
       .def("pull_mx", &AsyncEngine::pull_mx, py::call_guard<py::gil_scoped_release>())
-      .def("push", &AsyncEngine::push, py::call_guard<py::gil_scoped_release>())
+      .def("push", &AsyncEngine::push, py::arg("step"), py::arg("grads_flat"), py::arg("lo"), py::arg("hi"),
+           py::arg("stream"), py::arg("residual") = py::none(), py::call_guard<py::gil_scoped_release>())
       .def("push_scalars", &AsyncEngine::push_scalars, py::call_guard<py::gil_scoped_release>())
       .def("commit", &AsyncEngine::commit, py::call_guard<py::gil_scoped_release>())
       .def("wait_applied", &AsyncEngine::wait_applied, py::call_guard<py::gil_scoped_release>())

@@ -56,11 +56,16 @@ hipError_t launch_xfer_mx(const XferMxList& list, hipStream_t stream);
 // non-temporal and released at system scope before the kernel ends (local and peer destinations).
 // blocks_per_seg counts workgroups (the push's CU budget) as in XferList; the launcher picks their
 // width (1024 lanes for grids under 128 workgroups, else 256), which does not change the bytes.
+// Error feedback: with resid (n fp32, 16-byte aligned, local memory) the quantised value is
+// v = fp32(src) + resid and resid becomes v - dq(q(v)) in place (0 where v is NaN or +-inf); the
+// payload and scale bytes go where they go without it. Null: no feedback. Every segment of a list
+// carries one or none does.
 struct XferQSeg {
   const void* src;
   uint8_t* q_dst;
   uint8_t* sc_dst;
   int64_t n;
+  float* resid;
 };
 struct XferQList {
   XferQSeg seg[kMaxXferSeg];

@@ -20,7 +20,8 @@
 // copy is gone.
 //
 // The quantising push (xfer_quant_kernel) is the same scatter with the MX quantisation of the
-// gradient fused in: 1 + 1/32 bytes per element cross to the owner's inbox instead of 2 (bf16).
+// gradient fused in: 1 + 1/32 bytes per element cross to the owner's inbox instead of 2 (bf16). With
+// error feedback the worker's fp32 residual is added before and rewritten after, in the same pass.
 #include "common.h"
 #include "launchers.h"
 #include "launchers_xfer.h"
@@ -168,7 +169,18 @@ __device__ __forceinline__ uint32_t q8x4(float a, float b, float c, float d, flo
 // gradient at 48 workgroups 93 -> 55 us, profiles/push_fp8.md). A grid that fills the GPU anyway keeps
 // 256 lanes with four items in flight per lane (1024-lane workgroups measured 2.6x slower there).
 constexpr int kQuantWideBelow = 128;
-template <int SRC_DT, int U, int BLOCK>
+// EF (error feedback, XferQSeg::resid): the lane adds its 16 fp32 residuals to the gradient before
+// anything else looks at it -- four more 16-byte loads, issued with the gradient loads -- quantises the
+// sum v as above, then dequantises its own 16 bytes (packed hardware conversion, times the block's
+// power of two: exact), and writes v - dq back over the residual with four 16-byte stores. The
+// compiler may contract that multiply and subtract into one fma; the product is exact, so the bits
+// are the same either way. The residual of a NaN / +-inf element is 0: the NaN has been delivered
+// and must not come back with every later push. The residual accesses are plain, not non-temporal:
+// non-temporal residual LOADS cost 1.5x - 1.8x the whole kernel's time (ResNet-50-size bf16 gradient,
+// 48 workgroups: 259 us against 164 us), non-temporal stores changed nothing. One item in flight per
+// lane at 1024 lanes; at 256 lanes one (bf16) or two (fp32) -- 71 / 107 VGPRs; four items (179 VGPRs,
+// two waves per SIMD) and 1024-lane workgroups on a full grid were slower (profiles/push_fp8_ef.md).
+template <int SRC_DT, int U, int BLOCK, bool EF = false>
 __global__ __launch_bounds__(BLOCK) void xfer_quant_kernel(XferQList L) {
   const int s = (int)(blockIdx.x % (unsigned)L.count);
   const int j = (int)(blockIdx.x / (unsigned)L.count);
@@ -177,15 +189,33 @@ __global__ __launch_bounds__(BLOCK) void xfer_quant_kernel(XferQList L) {
   const int64_t stride = (int64_t)L.blocks_per_seg * BLOCK * U;
   for (int64_t b0 = (int64_t)j * BLOCK * U; b0 < n16; b0 += stride) {
     float t[U][16];
+    [[maybe_unused]] u32x4 r[EF ? U : 1][4];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t i = b0 + u * BLOCK + threadIdx.x;
-      if (i < n16) load16_src<SRC_DT>(g.src, i, t[u]);
+      if (i < n16) {
+        load16_src<SRC_DT>(g.src, i, t[u]);
+        if constexpr (EF) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) r[u][k] = ld16<false>(reinterpret_cast<const u32x4*>(g.resid) + i * 4 + k);
+        }
+      }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t i = b0 + u * BLOCK + threadIdx.x;
       const bool act = i < n16;  // n16 is even: the two lanes of a block are active together
+      if constexpr (EF) {
+        if (act) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            t[u][4 * k] += __uint_as_float(r[u][k].x);
+            t[u][4 * k + 1] += __uint_as_float(r[u][k].y);
+            t[u][4 * k + 2] += __uint_as_float(r[u][k].z);
+            t[u][4 * k + 3] += __uint_as_float(r[u][k].w);
+          }
+        }
+      }
       uint32_t mb = 0;  // this lane's amax, as bits
       if (act) {
 #pragma unroll
@@ -212,6 +242,25 @@ __global__ __launch_bounds__(BLOCK) void xfer_quant_kernel(XferQList L) {
               if (abs_bits(t[u][4 * k + e]) > kMaxFiniteBits) w[k] = (w[k] & ~(0xFFu << (8 * e))) | (0x7Fu << (8 * e));
         }
         st16<true>(reinterpret_cast<u32x4*>(g.q_dst) + i, u32x4{w[0], w[1], w[2], w[3]});
+        if constexpr (EF) {
+          const float sc = __uint_as_float(eb ? (uint32_t)eb << 23 : 0x00400000u);  // 2^(eb - 127)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], false);
+            const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], true);
+            const float d[4] = {lo[0], lo[1], hi[0], hi[1]};
+            float nr[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float v = t[u][4 * k + e];
+              nr[e] = v - d[e] * sc;
+              if (!finite && abs_bits(v) > kMaxFiniteBits) nr[e] = 0.f;
+            }
+            st16<false>(reinterpret_cast<u32x4*>(g.resid) + i * 4 + k,
+                        u32x4{__float_as_uint(nr[0]), __float_as_uint(nr[1]), __float_as_uint(nr[2]),
+                              __float_as_uint(nr[3])});
+          }
+        }
       }
       // scale bytes: lane 4p gets blocks (2p, 2p + 1) of the wave, then lane 8r blocks 4r .. 4r + 3
       uint32_t sw = (uint32_t)eb | ((uint32_t)__shfl_xor(eb, 2) << 8);
@@ -244,14 +293,25 @@ hipError_t launch_xfer_quant(const XferQList& L, hipStream_t st) {
   for (int i = 0; i < L.count; ++i) {
     const XferQSeg& g = L.seg[i];
     if (g.n < 0 || g.n % 32 != 0 || !g.sc_dst ||
-        ((reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.q_dst)) & 15))
+        ((reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.q_dst) |
+          reinterpret_cast<uintptr_t>(g.resid)) & 15) ||
+        (g.resid != nullptr) != (L.seg[0].resid != nullptr))  // all segments carry a residual or none
       return hipErrorInvalidValue;
   }
   const dim3 grid((unsigned)(L.count * L.blocks_per_seg));
   const bool wide = L.count * L.blocks_per_seg < kQuantWideBelow;
   if (L.src_dtype != DT_BF16 && L.src_dtype != DT_F32) return hipErrorInvalidValue;
-#define PSD_XQ(DT, U, B) hipLaunchKernelGGL((xfer_quant_kernel<DT, U, B>), grid, dim3(B), 0, st, L)
-  if (L.src_dtype == DT_BF16) {
+#define PSD_XQ(DT, U, B, ...) \
+  hipLaunchKernelGGL((xfer_quant_kernel<DT, U, B, ##__VA_ARGS__>), grid, dim3(B), 0, st, L)
+  if (L.seg[0].resid) {
+    if (L.src_dtype == DT_BF16) {
+      if (wide) PSD_XQ(DT_BF16, 1, 1024, true);
+      else PSD_XQ(DT_BF16, 1, 256, true);
+    } else {
+      if (wide) PSD_XQ(DT_F32, 1, 1024, true);
+      else PSD_XQ(DT_F32, 2, 256, true);
+    }
+  } else if (L.src_dtype == DT_BF16) {
     if (wide) PSD_XQ(DT_BF16, 2, 1024);
     else PSD_XQ(DT_BF16, 4, 256);
   } else {

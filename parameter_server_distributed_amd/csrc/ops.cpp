@@ -593,7 +593,8 @@ void xfer_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& d
   hip_check(launch_xfer(L, stream_of(srcs[0])), "launch_xfer");
 }
 
-void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg) {
+void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg,
+                    c10::optional<at::Tensor> residual) {
   const int64_t n = x.numel();
   TORCH_CHECK(x.is_contiguous() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16) && n % 32 == 0,
               "psd: push_quant_mx_ takes a contiguous fp32 or bf16 tensor of a multiple of 32 elements");
@@ -603,12 +604,19 @@ void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_
                   scales.device() == x.device(),
               "psd: push_quant_mx_ scales must be uint8 [numel / 32] on x's device");
   TORCH_CHECK(blocks_per_seg >= 0 && blocks_per_seg <= 1024, "psd: push_quant_mx_ blocks_per_seg in [0, 1024]");
+  const bool ef = residual.has_value() && residual->defined();
+  if (ef)
+    TORCH_CHECK(residual->scalar_type() == at::kFloat && residual->is_contiguous() && residual->numel() == n &&
+                    residual->device() == x.device(),
+                "psd: push_quant_mx_ residual must be contiguous fp32 [numel] on x's device");
   if (n == 0) return;
   if (x.is_cuda()) {
     check_aligned(x, "push_quant_mx_ x");
     check_aligned(q, "push_quant_mx_ q");
+    if (ef) check_aligned(*residual, "push_quant_mx_ residual");
     XferQList L{};
-    L.seg[L.count++] = XferQSeg{x.data_ptr(), static_cast<uint8_t*>(q.data_ptr()), scales.data_ptr<uint8_t>(), n};
+    L.seg[L.count++] = XferQSeg{x.data_ptr(), static_cast<uint8_t*>(q.data_ptr()), scales.data_ptr<uint8_t>(), n,
+                                ef ? residual->data_ptr<float>() : nullptr};
     L.blocks_per_seg = blocks_per_seg > 0 ? (int32_t)blocks_per_seg : xfer_blocks(n, 48);
     L.src_dtype = dt_of(x);
     const c10::DeviceGuard g(x.device());
@@ -616,8 +624,11 @@ void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_
     return;
   }
   // host: the operations of ops.quantize_mx_ref (the smallest 2^e with amax 2^-e <= 448, byte 127 for
-  // an all-zero or non-finite block, round to nearest even), then the non-finite rule
-  const at::Tensor xf = x.to(at::kFloat).view({-1, 32});
+  // an all-zero or non-finite block, round to nearest even), then the non-finite rule; with a residual
+  // the operations of ops.push_quant_mx_ef_ref (v = fp32(x) + r before, r = v - dq(q) after, 0 where
+  // v is not finite)
+  at::Tensor xf = x.to(at::kFloat).view({-1, 32});
+  if (ef) xf = xf + residual->view({-1, 32});
   const at::Tensor amax = xf.abs().amax(1);
   at::Tensor m, p;
   std::tie(m, p) = at::frexp(amax / 448.f);
@@ -628,6 +639,10 @@ void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_
   qb = at::where(at::isfinite(xf), qb, at::full({}, 0x7F, qb.options()));
   q.view(at::kByte).view({-1, 32}).copy_(qb);
   scales.copy_((e + 127).to(at::kByte));
+  if (ef) {
+    const at::Tensor dq = qb.view(at::kFloat8_e4m3fn).to(at::kFloat) * at::exp2(e.to(at::kFloat)).unsqueeze(1);
+    residual->view({-1, 32}).copy_(at::where(at::isfinite(xf), xf - dq, at::zeros_like(xf)));
+  }
 }
 
 void pack_cast_(const std::vector<at::Tensor>& srcs, const std::vector<at::Tensor>& dsts) {

@@ -42,8 +42,11 @@ void multi_reduce_(at::Tensor out, const std::vector<at::Tensor>& srcs, double s
 // host implementation for CPU tensors): x (bf16 / fp32, numel % 32 == 0) -> q (float8_e4m3fn or uint8,
 // like x) and scales (uint8 [numel / 32]). Scale and rounding of quant_mx_; a NaN or +-inf element
 // becomes the e4m3 NaN byte 0x7F and its block takes the unit scale. blocks_per_seg: workgroups
-// (0: the transport's default for the size); the bytes do not depend on it.
-void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg = 0);
+// (0: the transport's default for the size); the bytes do not depend on it. residual (error feedback:
+// contiguous fp32 [numel] on x's device, 16-byte aligned on the GPU): the quantised value is
+// v = fp32(x) + residual, and residual becomes v - dq(q, scales) in place, 0 where v is NaN or +-inf.
+void push_quant_mx_(const at::Tensor& x, at::Tensor q, at::Tensor scales, int64_t blocks_per_seg = 0,
+                    c10::optional<at::Tensor> residual = c10::nullopt);
 // Global-norm clipping scalars of a flat gradient (kernels/launchers_clip.h): out[0] = c =
 // min(1, clip_norm / (n + 1e-6)), out[1] = n = ||flat||_2. `partials`: fp32 scratch, one element per
 // 8192 elements of `flat`. Two launches on the current stream, no allocation.

@@ -78,6 +78,20 @@ def quantize_mx_ref(x: torch.Tensor, e5m2: bool = False):
     return q, (e + 127).to(torch.uint8)
 
 
+def push_quant_mx_ef_ref(g: torch.Tensor, r: torch.Tensor):
+    """PyTorch reference of the fp8 gradient push with error feedback (``push_quant_mx_`` with a
+    residual): ``v = fp32(g) + r``; ``(q, scales)`` = MX e4m3 of ``v`` as ``quantize_mx_ref``, except
+    that a NaN or +-inf element of ``v`` becomes the e4m3 NaN byte 0x7F (its block takes the unit
+    scale 127 and its finite elements saturate at +-448); ``r_new = v - dq(q, scales)`` in fp32, 0
+    where ``v`` is not finite. Returns ``(q, scales, r_new)``; ``r`` is left as it was."""
+    v = g.float().reshape(-1) + r.reshape(-1)
+    q, s = quantize_mx_ref(v)
+    fin = torch.isfinite(v)
+    q = torch.where(fin, q.view(torch.uint8), torch.full_like(q.view(torch.uint8), 0x7F)).view(torch.float8_e4m3fn)
+    r_new = torch.where(fin, v - dequantize_mx_ref(q, s), torch.zeros_like(v))
+    return q.reshape(g.shape), s, r_new.reshape(r.shape)
+
+
 def dequantize_mx_ref(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     """fp32 ``q * 2^(scale - 127)`` blockwise (reference / host path of dequant_mx_)."""
     v = q.float().reshape(-1, 32) * torch.exp2(scales.float() - 127.0).unsqueeze(1)

@@ -207,15 +207,20 @@ def multi_reduce_(out: torch.Tensor, srcs, scale: float = 1.0, scales=None, mx_s
                            _check_scales(mx_scales, len(srcs), "mx_scales"))
 
 
-def push_quant_mx_(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, blocks_per_seg: int = 0) -> None:
+def push_quant_mx_(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, blocks_per_seg: int = 0,
+                   residual: torch.Tensor | None = None) -> None:
     """The fp8 gradient push's quantiser on one contiguous range: ``x`` (bf16 / fp32, a multiple of
     32 elements) -> ``q`` (``float8_e4m3fn`` or uint8 like ``x``) and ``scales`` (uint8 ``[n / 32]``),
     OCP MX e4m3 with the scale and rounding of ``quantize_mx_ref``. Unlike ``quant_mx_`` a NaN or
     +-inf element becomes the e4m3 NaN byte 0x7F (its block takes the unit scale 127), so a diverged
     gradient reaches the owner as NaN. GPU: the quantising scatter kernel of the async push
     (``csrc/kernels/xfer.hip``) with ``blocks_per_seg`` workgroups (0: the transport's default; the
-    bytes do not depend on it). CPU tensors take the host implementation."""
-    native().push_quant_mx_(x, q, scales, int(blocks_per_seg))
+    bytes do not depend on it). CPU tensors take the host implementation.
+    ``residual`` (error feedback; contiguous fp32 ``[n]`` on ``x``'s device, 16-byte aligned on the
+    GPU): the quantised value is ``v = fp32(x) + residual`` and ``residual`` becomes
+    ``v - dq(q, scales)`` in place, 0 where ``v`` is NaN or +-inf -- ``ops.push_quant_mx_ef_ref``,
+    bit for bit; on the GPU inside the same kernel pass."""
+    native().push_quant_mx_(x, q, scales, int(blocks_per_seg), residual)
 
 
 def clip_chunks(n: int) -> int:

@@ -52,7 +52,21 @@ the same source order and with the same additions as the bf16 push -- weight dec
 moments, LARS / LAMB norms and the clip coefficients all see the dequantised sum. The clip norm is
 that of the gradient BEFORE quantisation (the norm pass runs over the worker's raw buffer). A NaN or
 +-inf gradient element arrives as NaN (e4m3 byte 0x7F). The bytes do not depend on the grid, on
-``xfer_blocks`` or on the transport. No error feedback, no e5m2, no stochastic rounding.
+``xfer_blocks`` or on the transport. No e5m2, no stochastic rounding.
+
+Error feedback (``push_error_feedback=True``, fp8 push only): each worker keeps ONE fp32 residual
+``r`` of ``total`` elements, laid out like the flat gradient buffer, zero at the start
+(``push_residual``). A push of ``[lo, hi)`` quantises ``v = fp32(g) + r`` instead of ``g`` and leaves
+``r = v - dq(q(v))`` behind, in place, in the kernel pass that quantises (exact in fp32: ``dq``
+scales by a power of two); a NaN / +-inf element of ``v`` travels as NaN and its residual becomes 0.
+Reference: ``ops.push_quant_mx_ef_ref``. The wire format, the slot size and the owner's apply are
+untouched: the owner cannot tell whether feedback is on. A component too small for its block's
+scale is no longer dropped on every step: it accumulates in ``r`` until it crosses half a quantum.
+With clipping the norm is still that of the raw ``g`` (the residual is not in the norm pass): the
+owner computes ``c_k * dq(q(g + r))``, the chosen approximation. Pushes of one range are
+stream-ordered (``_resid_on``). The self-test and the probes push through the feedback path and
+leave the residual zero. Checkpoints carry each worker's residual (``save`` / ``load``); the elastic
+re-shard and crash restore (``canonical_state`` / ``load_canonical_state``) drop it.
 
 Layout: the parameters live in one flat working buffer (``.data`` views, reverse registration
 order, 64-element aligned) split into P contiguous shards (cut at the nearest tensor starts when the
@@ -137,7 +151,7 @@ class AsyncPS:
                  worker_ranks: list[int] | None = None, param_dtype: torch.dtype = torch.bfloat16, nbuf: int = 4,
                  timeout_s: float | None = None, overlap: bool = True, store=None, log: bool = False,
                  semantics: str = "round", pull_dtype: str = "bf16", schedule: str = "free", xfer: str = "auto",
-                 push_dtype: str = "bf16"):
+                 push_dtype: str = "bf16", push_error_feedback: bool = False):
         """``semantics``: "round" (K-batch async, default) or "push" (apply-on-arrival with the
         per-push hyperparameters of csrc/async_hyper.h); see the module docstring.
         ``schedule`` "fixed" ("round" semantics only): round r holds exactly every worker's step-r
@@ -160,11 +174,19 @@ class AsyncPS:
         instead of 2 -- quantised inside the push (the scatter kernel, csrc/kernels/xfer.hip; with
         ``xfer="copy"`` into a staging buffer first; on the host for ``device=cpu``), and the owner's
         fused apply dequantises the inbox slots as it sums them (module docstring). "bf16" (default):
-        the raw gradient, exactly as before."""
+        the raw gradient, exactly as before.
+        ``push_error_feedback`` (``push_dtype="fp8"`` only): each worker keeps what the quantiser
+        dropped in one fp32 residual laid out like the flat gradient buffer (``push_residual``) and
+        adds it to the next gradient before quantising, inside the same push kernel (module
+        docstring). Off (default): every push discards its quantisation error."""
         if push_dtype not in ("bf16", "fp8"):
             raise ValueError(f"push_dtype must be bf16 or fp8, got {push_dtype!r}")
+        if push_error_feedback and push_dtype != "fp8":
+            raise ValueError(f"push_error_feedback=True needs push_dtype='fp8' (a {push_dtype} push drops nothing to "
+                             f"feed back)")
         self.push_dtype = push_dtype
         self.push_mx = push_dtype == "fp8"
+        self.push_error_feedback = bool(push_error_feedback)
         if xfer not in ("auto", "kernel", "copy"):
             raise ValueError(f"xfer must be auto, kernel or copy, got {xfer!r}")
         if semantics == "push" and optim.kind in LAYERWISE:
@@ -252,6 +274,13 @@ class AsyncPS:
             if self.pull_mx else []
         self.grads = [torch.zeros(total, dtype=param_dtype, device=dev) for _ in range(2)]
         self.gb = 0
+        # error feedback of the fp8 push: ONE residual per worker (the gradient buffers alternate, the
+        # residual does not), read and rewritten in place by the launch that quantises a range. Pushes
+        # of one range must therefore be stream-ordered: _resid_stream is the stream of the last launch
+        # that touched the residual, and _resid_on orders a launch on another stream behind it.
+        self.push_residual = torch.zeros(total, dtype=torch.float32, device=dev) \
+            if self.push_error_feedback and self.is_worker else None
+        self._resid_stream = None
         # per-push global-norm clipping (OptimConfig.clip_norm > 0): the push scalars -- 256-byte
         # blocks [c, ||g||, 0...] -- alternate with the gradient buffers (step t-2's push may still be
         # reading the other one); one scratch of per-chunk partial sums. Off: nothing is allocated.
@@ -416,7 +445,10 @@ class AsyncPS:
             self.store.set(f"{self._key}/ck/{tag}/{k}", f"{float(v.sum())!r} {float(v.abs().sum())!r}")
         if self.is_worker:
             pat = self._selftest_pattern(0, self.total, self.rank)
-            self.engine.push(0, pat, 0, self.total, self._stream_ptr())
+            # with error feedback the push goes through the feedback kernel, as training's will: the
+            # pattern is exact in MX e4m3, so a zero residual stays zero (reset below all the same)
+            self.engine.push(0, pat, 0, self.total, self._stream_ptr(), self._resid_on())
+            self.reset_push_residual()
             if self.clip:  # the scalar slots travel by the same transport: round-trip a block too
                 blk = torch.arange(64, dtype=torch.float32, device=dev) + 0.5 * (self.rank + 1)
                 self.engine.push_scalars(0, blk, self._stream_ptr())
@@ -520,6 +552,29 @@ class AsyncPS:
         s = s or torch.cuda.current_stream(self.device)
         return s.cuda_stream
 
+    def _resid_on(self, stream=None):
+        """The residual argument of an ``engine.push`` about to be launched on ``stream`` (None: the
+        current stream): ``None`` with feedback off. If the last launch that touched the residual ran
+        on another stream, ``stream`` first waits for everything issued there (the bucket-to-stream
+        mapping, ``rebucket``, the probes and ``reset_push_residual`` may all change streams)."""
+        if self.push_residual is None:
+            return None
+        if self.is_cuda:
+            s = stream or torch.cuda.current_stream(self.device)
+            last = self._resid_stream
+            if last is not None and last != s:
+                ev = torch.cuda.Event()
+                ev.record(last)
+                s.wait_event(ev)
+            self._resid_stream = s
+        return self.push_residual
+
+    def reset_push_residual(self):
+        """Zero this worker's error-feedback residual (no-op with feedback off), ordered behind every
+        push issued so far; later pushes are ordered behind the reset."""
+        if self._resid_on() is not None:
+            self.push_residual.zero_()
+
     def _set_grad_views(self):
         views = self._gview_cache.get(self.gb)
         if views is None:  # built once per gradient buffer (two alternate)
@@ -547,7 +602,8 @@ class AsyncPS:
         work = eb(self.pwork) if all(self.pwork is not b for b in self.pbufs) else 0
         return {"params": sum(eb(b) for b in self.pbufs) + work, "grads": 2 * eb(self.grads[0]),
                 "master": sum(eb(t) for t in self.master.values()),
-                "state": sum(eb(t) for t in list(self.state1.values()) + list(self.state2.values()))}
+                "state": sum(eb(t) for t in list(self.state1.values()) + list(self.state2.values())),
+                "push_residual": eb(self.push_residual) if self.push_residual is not None else 0}
 
     # ------------------------------------------------------------------ per-step protocol
     def begin_step(self, track: bool = True):
@@ -624,9 +680,9 @@ class AsyncPS:
             ev.record(torch.cuda.current_stream(self.device))
             cs = self.comm_streams[b.index % len(self.comm_streams)]
             cs.wait_event(ev)
-            self.engine.push(self.step_idx, g, b.lo, b.hi, cs.cuda_stream)
+            self.engine.push(self.step_idx, g, b.lo, b.hi, cs.cuda_stream, self._resid_on(cs))
         else:
-            self.engine.push(self.step_idx, g, b.lo, b.hi, 0)
+            self.engine.push(self.step_idx, g, b.lo, b.hi, 0, self._resid_on())
 
     def finish_step(self, track: bool = True):
         if not self.is_worker:
@@ -739,7 +795,7 @@ class AsyncPS:
                     for i, lo in enumerate(range(0, self.total, n)):
                         cs = self.comm_streams[i % len(self.comm_streams)] if self.is_cuda else None
                         self.engine.push(self.step_idx, g, lo, min(lo + n, self.total),
-                                         cs.cuda_stream if cs is not None else 0)
+                                         cs.cuda_stream if cs is not None else 0, self._resid_on(cs))
                     if self.is_cuda:
                         for cs in self.comm_streams:
                             cs.synchronize()
@@ -752,6 +808,8 @@ class AsyncPS:
                     el = (time.perf_counter() - t0) / reps
                 except Exception as e:  # noqa: BLE001
                     err = e
+                finally:  # the pushes ran the feedback path; training starts at 0, also after a failure
+                    self.reset_push_residual()
             t = torch.tensor([el, 1.0 if err is not None else 0.0], dtype=torch.float64)
             if self.world > 1 and dist.is_initialized():
                 if dist.get_backend() == "nccl":
@@ -790,15 +848,17 @@ class AsyncPS:
             if self.is_worker:
                 try:
                     st = self.comm_streams[0]
-                    self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream)
+                    self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream, self._resid_on(st))
                     st.synchronize()
                     t0 = time.perf_counter()
                     for _ in range(reps):
-                        self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream)
+                        self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream, self._resid_on(st))
                     st.synchronize()
                     el = (time.perf_counter() - t0) / reps
                 except Exception as e:  # noqa: BLE001 -- reported collectively below
                     err = e
+                finally:  # the pushes ran the feedback path: leave the residual zero, also after a failure
+                    self.reset_push_residual()
             t = torch.tensor([el, 1.0 if err is not None else 0.0], dtype=torch.float64)
             if self.world > 1 and dist.is_initialized():
                 if dist.get_backend() == "nccl":
@@ -828,21 +888,25 @@ class AsyncPS:
         tmp = torch.empty_like(self.params_flat)
         st = torch.cuda.current_stream(self.device)
         out = {}
-        for name, fn in (("push", lambda: self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream)),
-                         # step_idx: the latest admissible snapshot under both schedules (a fixed
-                         # schedule keeps only the last S + 1 versions; step 0's is long gone)
-                         ("pull", lambda: self.engine.pull(self.step_idx, tmp, st.cuda_stream))):
-            fn()
-            torch.cuda.synchronize(self.device)
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(reps):
+        try:
+            for name, fn in (("push", lambda: self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream,
+                                                                self._resid_on(st))),
+                             # step_idx: the latest admissible snapshot under both schedules (a fixed
+                             # schedule keeps only the last S + 1 versions; step 0's is long gone)
+                             ("pull", lambda: self.engine.pull(self.step_idx, tmp, st.cuda_stream))):
                 fn()
-            e.record()
-            e.synchronize()
-            ms = s.elapsed_time(e) / reps
-            bpe = self.push_bytes_per_elem if name == "push" else g.element_size()
-            out[f"{name}_GBps"] = round(self.total * bpe / (ms * 1e-3) / 1e9, 1)
+                torch.cuda.synchronize(self.device)
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(reps):
+                    fn()
+                e.record()
+                e.synchronize()
+                ms = s.elapsed_time(e) / reps
+                bpe = self.push_bytes_per_elem if name == "push" else g.element_size()
+                out[f"{name}_GBps"] = round(self.total * bpe / (ms * 1e-3) / 1e9, 1)
+        finally:  # the timed pushes ran the feedback path: leave the residual zero, also after a failure
+            self.reset_push_residual()
         return out
 
     def abort(self):
@@ -941,13 +1005,17 @@ class AsyncPS:
         return {"world": self.world, "owners": self.owners, "workers": self.worker_ranks, "P": self.P,
                 "shard_off": self.shard_off, "shard_len": self.shard_len, "total": self.total,
                 "staleness": self.S, "semantics": self.semantics, "round": self.round, "push_dtype": self.push_dtype,
+                "push_error_feedback": self.push_error_feedback,
                 "optimizer": self.cfg.to_dict(), "params": [(n, list(p.shape), o, k) for (n, p, o, k) in self._layout]}
 
     def save(self, prefix: str, blocking: bool = True):
         """Sharded checkpoint (collective: every rank calls at the same step). After a drain, each
         shard owner writes ``{prefix}.rank{r}.psd`` (atomic, CRC-checked: csrc/checkpoint.cpp) with
         its fp32 masters, optimizer state and step scalars, plus the shard versions and every
-        worker's SSP clock; rank 0 writes ``{prefix}.manifest.json``. The device state is
+        worker's SSP clock; rank 0 writes ``{prefix}.manifest.json``. With ``push_error_feedback``
+        each worker's file also carries its residual as one extra tensor after the shard tensors
+        (``"push_residual": true`` in its per-rank JSON; the manifest records
+        ``push_error_feedback``), snapshotted after the drain, when no push is rewriting it. The device state is
         snapshotted (HBM->HBM) before any rank returns, so the engines' next applies cannot race
         the copy; with ``blocking=False`` the device->host copy and the file write run on a host
         thread while training continues. Returns that thread (or None).
@@ -967,6 +1035,11 @@ class AsyncPS:
             snap.extend(t.detach().clone() for t in ts)
             meta["shards"][str(k)] = {"version": int(self.engine.version(k)), "clocks": list(self.engine.clocks(k)),
                                       "n": len(ts)}
+        # error feedback: this worker's residual, one extra tensor after the shard tensors. The drain
+        # above left the comm streams idle, so no push is rewriting it.
+        meta["push_residual"] = self.push_residual is not None
+        if self.push_residual is not None:
+            snap.append(self.push_residual.detach().clone())
         # the workers' step (the owners that are not workers learn it from the store)
         steps = torch.tensor([self.step_idx if self.is_worker else 0], dtype=torch.int64)
         if self.world > 1 and dist.is_initialized():
@@ -985,7 +1058,7 @@ class AsyncPS:
             host = [t.cpu() for t in snap]
             C.save_native_ckpt(path, man_s, host)
             if self.rank == 0:
-                m0 = {k: v for k, v in man.items() if k not in ("shards", "rank")}
+                m0 = {k: v for k, v in man.items() if k not in ("shards", "rank", "push_residual")}
                 with open(f"{prefix}.manifest.json.tmp", "w") as f:
                     f.write(json.dumps(m0))
                 os.replace(f"{prefix}.manifest.json.tmp", f"{prefix}.manifest.json")
@@ -1001,7 +1074,10 @@ class AsyncPS:
         """Resume from ``save(prefix)`` with the same layout (collective, before the first step):
         every owner restores its shards' masters, optimizer state and step scalars and re-publishes
         them as the saved shard versions with the saved SSP clocks; every worker continues at the
-        saved step (its first pull waits on the restored clocks)."""
+        saved step (its first pull waits on the restored clocks). The error-feedback residual: with
+        feedback on and a residual in this rank's file it is restored; with feedback on and none in
+        the file (an older checkpoint, or one saved without feedback) it starts at zero; with
+        feedback off a residual in the file is ignored."""
         import json
 
         man, ts = native().load_native_ckpt(f"{prefix}.rank{self.rank}.psd")
@@ -1029,6 +1105,12 @@ class AsyncPS:
                     j += 1
             i += sh["n"]
             self.engine.publish_initial(k, sh["version"], sh["clocks"])
+        # error feedback: restored when on and the file carries a residual; zero when the file has none
+        # (an older checkpoint, or one saved without feedback); ignored when off
+        if self.push_residual is not None:
+            self.reset_push_residual()
+            if m.get("push_residual", False):
+                self.push_residual.copy_(ts[i])
         self.step_idx = int(m["step_idx"])
         self._prefetched = None
         self.engine.start()
@@ -1134,6 +1216,9 @@ class AsyncPS:
         self._to_work()
         self.step_idx = 0
         self._prefetched = None
+        # the canonical state carries no residual (it belongs to a worker of the old layout): error
+        # feedback restarts at zero, at most one step's quantisation error is lost
+        self.reset_push_residual()
         if self.is_cuda:
             torch.cuda.synchronize(self.device)
         self._barrier(f"canon-load-{self._ckpt_seq}")
@@ -1158,4 +1243,4 @@ class AsyncPS:
         return (f"AsyncPS(world={self.world}, shards={self.P} on ranks {self.owners}, workers={self.worker_ranks}, "
                 f"SSP bound={self.S}, buckets={len(self.buckets)}, params={self.num_params() / 1e6:.2f}M, "
                 f"memory={self.engine.memory_kind()}, xfer={self.xfer_mode}"
-                f"{', push=fp8' if self.push_mx else ''})")
+                f"{', push=fp8' if self.push_mx else ''}{' + error feedback' if self.push_error_feedback else ''})")

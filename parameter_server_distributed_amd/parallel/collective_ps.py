@@ -128,9 +128,14 @@ class CollectivePS:
                  overlap: bool = True, grad_dtype: torch.dtype = torch.bfloat16,
                  param_dtype: torch.dtype = torch.bfloat16, device: torch.device | None = None,
                  ps_ranks: list[int] | None = None, worker_ranks: list[int] | None = None,
-                 pull_dtype: str = "bf16", push_mode: str = "auto", push_dtype: str = "bf16"):
+                 pull_dtype: str = "bf16", push_mode: str = "auto", push_dtype: str = "bf16",
+                 push_error_feedback: bool = False):
         if push_dtype not in ("bf16", "fp8"):
             raise ValueError(f"push_dtype must be bf16 or fp8, got {push_dtype!r}")
+        if push_error_feedback:
+            raise ValueError("push_error_feedback=True is not supported on the collective plane: it has no quantised "
+                             "push whose error a worker could keep; use the async plane "
+                             "(parallel.async_ps.AsyncPS) with push_dtype='fp8'")
         if push_dtype == "fp8":
             # the reduce-scatter sums the workers' buckets in flight: there is no per-worker inbox
             # slot whose blocks an owner could dequantise

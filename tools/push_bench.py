@@ -6,6 +6,9 @@ xfer_quant_kernel and the MX-source instantiations of the fused apply):
     quantising scatter (``push_quant_mx_``: bf16 in, e4m3 payload + E8M0 scale bytes out) for a
     ResNet-50-size and a BERT-base-size gradient into device memory, at the engine's default
     workgroup budget (48 per segment) and at 256;
+  * the quantising scatter with error feedback (``push_quant_mx_`` with a residual: the fp32
+    residual read, added, and rewritten in the same pass) against the plain quantising scatter, for
+    bf16 and fp32 gradients of both sizes at both budgets;
   * the flat fused apply (momentum, adamw) fed K = 1, 4, 8, 16 bf16 sources against K MX sources of
     the ResNet-50 size, alternating the two so that drift hits both alike.
 
@@ -56,6 +59,7 @@ def main():
     C = native()
     dev = torch.device("cuda", 0)
     has_mx = hasattr(C, "push_quant_mx_") and not a.bf16_only
+    has_ef = has_mx and "residual" in (C.push_quant_mx_.__doc__ or "")
     lines = []
 
     def out(s=""):
@@ -88,7 +92,7 @@ def main():
         return f"{m:.1f} ({lo:.1f}-{hi:.1f}) | {nbytes / m / 1e6:.2f}"
 
     res = {"device": torch.cuda.get_device_name(0), "tree": os.path.abspath(a.tree), "has_fp8_push": has_mx,
-           "iters": a.iters, "reps": a.reps, "scatter": [], "apply": []}
+           "has_error_feedback": has_ef, "iters": a.iters, "reps": a.reps, "scatter": [], "feedback": [], "apply": []}
     out(f"device: {res['device']}; fp8 push in this build: {has_mx}; median of {a.reps} windows of {a.iters} calls")
     out()
     out("| gradient | workgroups | bf16 scatter us (min-max) | TB/s read+written | bytes written | "
@@ -116,6 +120,34 @@ def main():
                                    "fp8_us": r.get("fp8"), "bf16_bytes_written": 2 * n,
                                    "fp8_bytes_written": n + n // 32})
         del g, dst, q, sc
+
+    if has_ef:
+        # bytes through local HBM per element: source read (2 / 4) + payload and scales written (33/32),
+        # with feedback 8 more (the fp32 residual read and rewritten)
+        out()
+        out("| gradient | source | workgroups | quantising scatter us (min-max) | TB/s read+written | "
+            "with error feedback us (min-max) | TB/s read+written | time ratio |")
+        out("|---|---|---:|---:|---:|---:|---:|---:|")
+        for name, n in SIZES.items():
+            n = _round(n)
+            q = torch.empty(n, dtype=torch.uint8, device=dev)
+            sc = torch.empty(n // 32, dtype=torch.uint8, device=dev)
+            resid = torch.zeros(n, device=dev)
+            for dt in (torch.bfloat16, torch.float32):
+                g = (torch.randn(n, device=dev) * 0.05).to(dt)
+                esz = g.element_size()
+                for bps in (48, 256):
+                    r = timed({"fp8": lambda: C.push_quant_mx_(g, q, sc, bps),
+                               "ef": lambda: C.push_quant_mx_(g, q, sc, bps, resid)})
+                    plain_b = esz * n + n + n // 32
+                    src = "bf16" if dt == torch.bfloat16 else "fp32"
+                    out(f"| {name} | {src} | {bps} | {cell(r['fp8'], plain_b)} | {cell(r['ef'], plain_b + 8 * n)} | "
+                        f"{r['ef'][0] / r['fp8'][0]:.3f} |")
+                    res["feedback"].append({"gradient": name, "n": n, "source": src, "blocks_per_seg": bps,
+                                            "fp8_us": r["fp8"], "ef_us": r["ef"], "fp8_bytes": plain_b,
+                                            "ef_bytes": plain_b + 8 * n})
+                del g
+            del q, sc, resid
 
     n = _round(SIZES["resnet50"])
     out()
