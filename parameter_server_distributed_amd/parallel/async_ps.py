@@ -95,9 +95,7 @@ from .. import native
 from ..ops import dequantize_mx_ref, quantize_mx_ref
 from ..ops.optim import LAYERWISE, LayerTable, OptimConfig, OptimDyn, clip_chunks, grad_clip_coef_
 from ..utils.config import fault, feature
-from .collective_ps import ALIGN, _flat_view, _round, install_fp8_weights, zero_grads_, zero_plan
-
-
+from .flat import ALIGN, FlatBinding, _round, install_fp8_weights, spread_owners
 
 
 def snap_bounds(total: int, P: int, starts: list[int]) -> list[int]:
@@ -189,6 +187,8 @@ class AsyncPS:
         self.push_error_feedback = bool(push_error_feedback)
         if xfer not in ("auto", "kernel", "copy"):
             raise ValueError(f"xfer must be auto, kernel or copy, got {xfer!r}")
+        if semantics not in ("round", "push"):
+            raise ValueError(f"semantics must be 'round' or 'push', got {semantics!r}")
         if semantics == "push" and optim.kind in LAYERWISE:
             raise ValueError(f"optimizer {optim.kind!r} takes whole rounds (the trust ratio is a property of the "
                              f"round's gradient): semantics='push' is not supported with it, use 'round'")
@@ -201,13 +201,7 @@ class AsyncPS:
         self.worker_ranks = list(worker_ranks) if worker_ranks is not None else list(range(self.world))
         self.is_worker = self.rank in self.worker_ranks
         self.W = len(self.worker_ranks)
-        if ps_ranks is not None:
-            self.owners = list(ps_ranks)
-        else:
-            P = num_shards or self.world
-            if not 1 <= P <= self.world:
-                raise ValueError(f"num_shards must be in [1, world={self.world}], got {P}")
-            self.owners = [k * self.world // P for k in range(P)]
+        self.owners = list(ps_ranks) if ps_ranks is not None else spread_owners(num_shards or self.world, self.world)
         self.P = len(self.owners)
         self.my_shards = [k for k, r in enumerate(self.owners) if r == self.rank]
         self.S = int(staleness)
@@ -248,12 +242,13 @@ class AsyncPS:
             bounds = [_round(total * k // self.P, ALIGN) for k in range(self.P)] + [total]
         self.shard_off = bounds[:-1]
         self.shard_len = [bounds[k + 1] - bounds[k] for k in range(self.P)]
-        self._build_buckets(layout, bucket_mb)
 
         dev = self.device
-        init = torch.zeros(total, dtype=torch.float32, device=dev)
-        for n, p, o, k in layout:
-            _flat_view(init, o, p).copy_(p.detach().float())
+        self._layout = layout
+        self.flat = FlatBinding(model, layout, total)
+        self._zero_plan = self.flat.zero_plan
+        self._build_buckets(bucket_mb)
+        init = self.flat.initial(dev)
         # working weights: with S >= 1 two buffers alternate per step, so the pull of step t+1 (DMA
         # from the owners' publish buffers) runs on a side stream while step t computes
         # (world 1: the pull is one local device copy, so pulling straight into the working weights at
@@ -290,8 +285,6 @@ class AsyncPS:
         self._last_scal = None
         f32 = dict(dtype=torch.float32, device=dev)
         # per-push hyperparameters (module docstring)
-        if semantics not in ("round", "push"):
-            raise ValueError(f"semantics must be 'round' or 'push', got {semantics!r}")
         self.semantics = semantics
         # K = W: every round completes (a cap below W would strand a partial round at W > 16 and
         # hold a worker's clock back forever); the engine pre-reduces above 16 sources
@@ -319,23 +312,9 @@ class AsyncPS:
                 self.layers[k] = LayerTable.for_range(flat, self.shard_off[k], self.shard_off[k] + self.shard_len[k],
                                                       optim.exclude_1d, dev, ALIGN)
 
-        # grad sinks (fused BN / MFMA linear write their parameter gradients straight into the buffer)
-        self._direct = set()
-        for m in model.modules():
-            if hasattr(m, "psd_direct_grad_params"):
-                for dp in m.psd_direct_grad_params():
-                    if dp is not None and dp.requires_grad:
-                        self._direct.add(id(dp))
-                m._psd_grad_sink = self._sink
-        self._layout = layout
-        self._zero_plan = zero_plan([(o, p.numel()) for (_n, p, o, _k) in layout if id(p) not in self._direct], total)
-        self._arrived: set = set()
-        for (n, p, o, k) in layout:
-            p.data = _flat_view(self.pwork, o, p)
-        self._gview_cache = {}
-        self._set_grad_views()
-        self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for _, p, _o, _n in layout]
-        self._next = 0
+        self.flat.bind_params(self.pwork)
+        self.flat.bind_grads(self.grads[self.gb])
+        self.flat.watch(self._push, overlap)
         if self.is_cuda:
             # ONE push stream: HIP maps a process's streams onto GPU_MAX_HW_QUEUES = 4 hardware
             # queues, and compute + engine apply + push + pull already take four -- a fifth stream
@@ -344,7 +323,6 @@ class AsyncPS:
             # profiles/async_push_streams_r4.md). The owners' links overlap inside one launch
             # instead (kernels/xfer.hip).
             self.comm_stream = torch.cuda.Stream(device=dev)
-            self.comm_streams = [self.comm_stream]
             self.pull_stream = torch.cuda.Stream(device=dev)
             self.push_done = [None, None]
             self.step_done = [None, None]  # end of a step's work on the compute stream, per buffer
@@ -538,8 +516,6 @@ class AsyncPS:
             return
         k = f"{self._key}/bar/{tag}"
         self.store.add(k, 1)
-        import time
-
         t0 = time.time()
         while int(self.store.add(k, 0)) < self.world:
             if time.time() - t0 > 600:
@@ -551,6 +527,23 @@ class AsyncPS:
             return 0
         s = s or torch.cuda.current_stream(self.device)
         return s.cuda_stream
+
+    def _mark(self, stream=None, then=None):
+        """An event recorded on ``stream`` (None: the current stream); ``then``, a stream, waits for it."""
+        ev = torch.cuda.Event()
+        ev.record(stream or torch.cuda.current_stream(self.device))
+        if then is not None:
+            then.wait_event(ev)
+        return ev
+
+    def _all_max(self, vals: list, dtype=torch.float64) -> list:
+        """Collective: the element-wise maximum over the ranks of a few host scalars."""
+        t = torch.tensor(vals, dtype=dtype)
+        if self.world > 1 and dist.is_initialized():
+            if dist.get_backend() == "nccl":
+                t = t.to(self.device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return t.tolist()
 
     def _resid_on(self, stream=None):
         """The residual argument of an ``engine.push`` about to be launched on ``stream`` (None: the
@@ -575,27 +568,11 @@ class AsyncPS:
         if self._resid_on() is not None:
             self.push_residual.zero_()
 
-    def _set_grad_views(self):
-        views = self._gview_cache.get(self.gb)
-        if views is None:  # built once per gradient buffer (two alternate)
-            g = self.grads[self.gb]
-            views = {id(p): _flat_view(g, o, p) for (_n, p, o, _k) in self._layout}
-            self._gview_cache[self.gb] = views
-        self._grad_views = views
-        for n, p, o, k in self._layout:
-            p.grad = None if id(p) in self._direct else views[id(p)]
-
     def _to_work(self):
         """The pulled buffer of this step into the working weights (stream-ordered on the current
         stream: after the previous step's kernels, before this step's)."""
         if self.pwork is not self.pbufs[self.cb]:
             self.pwork.copy_(self.pbufs[self.cb])
-
-    def _sink(self, p):
-        if id(p) not in self._direct:
-            return None
-        v = self._grad_views[id(p)]
-        return v.view(v.shape)
 
     def memory_bytes(self) -> dict:
         eb = lambda t: t.numel() * t.element_size()  # noqa: E731
@@ -614,12 +591,8 @@ class AsyncPS:
         if self.is_cuda and self.push_done[self.gb] is not None:
             # the push copies of step t-2 read this gradient buffer
             torch.cuda.current_stream(self.device).wait_event(self.push_done[self.gb])
-        zero_grads_(self.grads[self.gb], self._zero_plan)
-        self._arrived = set()
-        self._set_grad_views()
-        for b in self.buckets:
-            b.pending = len(b.params)
-        self._next = 0
+        self.flat.begin(self.grads[self.gb])
+        self.flat.bind_grads(self.grads[self.gb])  # two buffers alternate: every p.grad is re-pointed
         if self.prefetch:
             self.cb = t % 2
             if self._prefetched is not None and self._prefetched[0] == t:
@@ -648,38 +621,16 @@ class AsyncPS:
             if self.step_done[nb] is not None:
                 self.pull_stream.wait_event(self.step_done[nb])
             pulled = self._pull_into(t, nb, self.pull_stream)
-            ev = torch.cuda.Event()
-            ev.record(self.pull_stream)
-            self.pull_done[nb] = ev
+            self.pull_done[nb] = self._mark(self.pull_stream)
         else:
             pulled = self.engine.pull(t, self.pbufs[nb], 0)
         self._prefetched = (t, list(pulled))
 
-    def _on_grad(self, p):
-        self._arrived.add(id(p))
-        if id(p) in self._direct:
-            v = self._grad_views[id(p)]
-            if p.grad is not None and p.grad.data_ptr() != v.data_ptr():
-                v.copy_(p.grad)
-        b = self._p2b[id(p)]
-        b.pending -= 1
-        if not self.overlap:
-            return
-        while self._next < len(self.buckets) and self.buckets[self._next].pending <= 0:
-            self._push(self.buckets[self._next])
-            self._next += 1
-
     def _push(self, b: _Bucket):
         g = self.grads[self.gb]
-        if b.pending > 0 and self._zero_plan is not None:  # flushed with gradients missing
-            for _n, p, _o, _k in b.params:
-                if id(p) in self._direct and id(p) not in self._arrived:
-                    self._grad_views[id(p)].zero_()
         if self.is_cuda:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            cs = self.comm_streams[b.index % len(self.comm_streams)]
-            cs.wait_event(ev)
+            cs = self.comm_stream
+            self._mark(then=cs)
             self.engine.push(self.step_idx, g, b.lo, b.hi, cs.cuda_stream, self._resid_on(cs))
         else:
             self.engine.push(self.step_idx, g, b.lo, b.hi, 0, self._resid_on())
@@ -687,9 +638,7 @@ class AsyncPS:
     def finish_step(self, track: bool = True):
         if not self.is_worker:
             return
-        while self._next < len(self.buckets):
-            self._push(self.buckets[self._next])
-            self._next += 1
+        self.flat.launch_ready(flush=True)
         if self.clip:
             # the whole gradient is in the buffer now (the buckets above are already on their way):
             # one read-only pass -> this push's scalar, which follows the buckets on the comm stream
@@ -697,23 +646,13 @@ class AsyncPS:
             blk = self.scal[self.gb]
             grad_clip_coef_(self.grads[self.gb], self.cfg.clip_norm, blk, self.clip_partials)
             if self.is_cuda:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(self.device))
-                self.comm_stream.wait_event(ev)
+                self._mark(then=self.comm_stream)
             self.engine.push_scalars(self.step_idx, blk, self.comm_stream.cuda_stream if self.is_cuda else 0)
             self._last_scal = blk
-        if self.is_cuda:
-            for cs in self.comm_streams[1:]:  # the commit posts after every push copy has landed
-                ev = torch.cuda.Event()
-                ev.record(cs)
-                self.comm_stream.wait_event(ev)
+        if self.is_cuda:  # the commit posts behind the push copies, on their stream
             self.engine.commit(self.step_idx, self.pulled, self.comm_stream.cuda_stream)
-            ev = torch.cuda.Event()
-            ev.record(self.comm_stream)
-            self.push_done[self.gb] = ev
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.device))
-            self.step_done[self.cb] = done
+            self.push_done[self.gb] = self._mark(self.comm_stream)
+            self.step_done[self.cb] = self._mark()
         else:
             self.engine.commit(self.step_idx, self.pulled, 0)
         self.step_idx += 1
@@ -737,13 +676,13 @@ class AsyncPS:
     # ------------------------------------------------------------------ end of run / reporting
     def drain(self):
         """Block until every worker's pushes so far are applied everywhere (collective: all ranks)."""
-        steps = torch.tensor([self.step_idx if self.is_worker else 0], dtype=torch.int64)
-        if self.world > 1 and dist.is_initialized():
-            steps = steps.to(self.device) if dist.get_backend() == "nccl" else steps
-            dist.all_reduce(steps, op=dist.ReduceOp.MAX)
-        self.engine.wait_all_applied(int(steps.item()))
+        self.engine.wait_all_applied(self._workers_step())
         if self.is_cuda:
             torch.cuda.synchronize(self.device)
+
+    def _workers_step(self) -> int:
+        """Collective: the workers' step (the owners that are not workers learn it here)."""
+        return self._all_max([self.step_idx if self.is_worker else 0], torch.int64)[0]
 
     def refresh_weights(self):
         """After ``drain``: the working weights (the model's parameter views) = the latest applied
@@ -754,14 +693,14 @@ class AsyncPS:
             if self.is_cuda:
                 torch.cuda.synchronize(self.device)
 
-    def _build_buckets(self, layout, bucket_mb: float):
+    def _build_buckets(self, bucket_mb: float):
         """Push buckets: consecutive parameter ranges of ~``bucket_mb`` (the tail padding travels
         with the last bucket)."""
         elem = torch.finfo(self.param_dtype).bits // 8
         cap = max(ALIGN, int(bucket_mb * (1 << 20)) // elem)
         self.buckets: list[_Bucket] = []
         cur = _Bucket(0, lo=0)
-        for n, p, o, k in layout:
+        for n, p, o, k in self._layout:
             cur.params.append((n, p, o, k))
             cur.hi = o + _round(k, ALIGN)
             if cur.hi - cur.lo >= cap:
@@ -771,55 +710,59 @@ class AsyncPS:
             self.buckets.append(cur)
         self.buckets[-1].hi = self.total
         self.bucket_mb = float(bucket_mb)
-        self._p2b = {id(p): b for b in self.buckets for _n, p, _o, _k in b.params}
+        self.flat.set_buckets(self.buckets)
 
     def rebucket(self, bucket_mb: float):
         """Rebuild the push buckets at another size (between steps; every rank the same size)."""
-        self._build_buckets(self._layout, bucket_mb)
+        self._build_buckets(bucket_mb)
 
     def probe_push_sizes(self, sizes_mb=(1, 2, 4, 8, 16, 32, 64), reps: int = 3) -> dict:
         """The bandwidth of THIS plane's push transport vs bucket size, measured before training
         (collective, every rank): each worker DMA-copies its whole gradient buffer into its inbox
-        slot on every owner in chunks of ``size`` MB -- one engine push per chunk on alternating
-        push streams, exactly what a step's bucket pushes do (no commit: nothing is applied) --
+        slot on every owner in chunks of ``size`` MB -- one engine push per chunk on the push
+        stream, exactly what a step's bucket pushes do (no commit: nothing is applied) --
         and the max over ranks of the time gives {MB: GB/s}. The RCCL send/recv probe
         (parallel/bucketing.py probe_p2p) measures the collective plane's transport, not this one."""
         out = {}
         g = self.grads[0]
-        elem = g.element_size()
+        cs = self.comm_stream if self.is_cuda else None
         for mb in sizes_mb:
-            n = max(ALIGN, int(mb * (1 << 20)) // elem // ALIGN * ALIGN)  # chunk ends stay 16-B aligned
-            el, err = 0.0, None
-            if self.is_worker:
-                def run():
-                    for i, lo in enumerate(range(0, self.total, n)):
-                        cs = self.comm_streams[i % len(self.comm_streams)] if self.is_cuda else None
-                        self.engine.push(self.step_idx, g, lo, min(lo + n, self.total),
-                                         cs.cuda_stream if cs is not None else 0, self._resid_on(cs))
-                    if self.is_cuda:
-                        for cs in self.comm_streams:
-                            cs.synchronize()
+            n = max(ALIGN, int(mb * (1 << 20)) // g.element_size() // ALIGN * ALIGN)  # chunk ends stay 16-B aligned
 
-                try:  # a failure here must reach every rank (below), not strand them in the all_reduce
-                    run()
-                    t0 = time.perf_counter()
-                    for _ in range(reps):
-                        run()
-                    el = (time.perf_counter() - t0) / reps
-                except Exception as e:  # noqa: BLE001
-                    err = e
-                finally:  # the pushes ran the feedback path; training starts at 0, also after a failure
-                    self.reset_push_residual()
-            t = torch.tensor([el, 1.0 if err is not None else 0.0], dtype=torch.float64)
-            if self.world > 1 and dist.is_initialized():
-                if dist.get_backend() == "nccl":
-                    t = t.to(self.device)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            if float(t[1]) > 0:
-                raise RuntimeError(f"push-size probe failed on a rank{f': {err}' if err is not None else ''}")
-            el = float(t[0])
+            def run():
+                for lo in range(0, self.total, n):
+                    self.engine.push(self.step_idx, g, lo, min(lo + n, self.total),
+                                     cs.cuda_stream if cs is not None else 0, self._resid_on(cs))
+                if cs is not None:
+                    cs.synchronize()
+
+            el = self._time_pushes(run, reps, "push-size probe")
             out[mb] = round(self.total * self.push_bytes_per_elem * self.P / max(el, 1e-9) / 1e9, 1) if el > 0 else None
         return out
+
+    def _time_pushes(self, run, reps: int, what: str) -> float:
+        """Collective: the seconds one ``run()`` takes on a worker (once untimed, then ``reps`` timed;
+        the push stream is idle before the clock starts and before it stops), maximum over the ranks.
+        A failure on any rank raises on every rank instead of stranding the others in the all_reduce."""
+        el, err = 0.0, None
+        sync = self.comm_stream.synchronize if self.is_cuda else (lambda: None)
+        if self.is_worker:
+            try:
+                run()
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    run()
+                sync()
+                el = (time.perf_counter() - t0) / reps
+            except Exception as e:  # noqa: BLE001 -- reported collectively below
+                err = e
+            finally:  # the pushes ran the feedback path: leave the residual zero, also after a failure
+                self.reset_push_residual()
+        el, failed = self._all_max([el, 1.0 if err is not None else 0.0])
+        if failed > 0:
+            raise RuntimeError(f"{what} failed on a rank{f': {err}' if err is not None else ''}")
+        return el
 
     def probe_xfer_blocks(self, caps=(8, 16, 24, 32, 48, 64, 96), reps: int = 3, keep: float = 0.9) -> dict:
         """The scatter kernel's workgroup budget (collective, every rank; before training): each
@@ -828,46 +771,20 @@ class AsyncPS:
         within ``keep`` of the best bandwidth -- the fewest CUs the push takes from the backward
         pass running beside it for (nearly) the same link throughput -- and sets it on the engine.
         Only meaningful where the kernel transport runs (a remote owner); otherwise returns {}."""
-        if not (self.is_cuda and self.xfer_mode == "kernel") or all(o == self.rank for o in self.owners):
-            remote = False
-        else:
-            remote = True
-        t = torch.tensor([1.0 if remote else 0.0], dtype=torch.float64)
-        if self.world > 1 and dist.is_initialized():
-            if dist.get_backend() == "nccl":
-                t = t.to(self.device)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        if float(t[0]) == 0.0 or not self.is_cuda:
+        remote = self.is_cuda and self.xfer_mode == "kernel" and any(o != self.rank for o in self.owners)
+        if self._all_max([1.0 if remote else 0.0])[0] == 0.0 or not self.is_cuda:
             return {}
-        g = self.grads[0]
+        g, st = self.grads[0], self.comm_stream
         old = self.engine.xfer_blocks_cap()
         res = {}
         for cap in caps:
             self.engine.set_xfer_blocks(int(cap))
-            el, err = 0.0, None
-            if self.is_worker:
-                try:
-                    st = self.comm_streams[0]
-                    self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream, self._resid_on(st))
-                    st.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(reps):
-                        self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream, self._resid_on(st))
-                    st.synchronize()
-                    el = (time.perf_counter() - t0) / reps
-                except Exception as e:  # noqa: BLE001 -- reported collectively below
-                    err = e
-                finally:  # the pushes ran the feedback path: leave the residual zero, also after a failure
-                    self.reset_push_residual()
-            t = torch.tensor([el, 1.0 if err is not None else 0.0], dtype=torch.float64)
-            if self.world > 1 and dist.is_initialized():
-                if dist.get_backend() == "nccl":
-                    t = t.to(self.device)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            if float(t[1]) > 0:
+            try:
+                el = self._time_pushes(lambda: self.engine.push(self.step_idx, g, 0, self.total, st.cuda_stream,
+                                                                self._resid_on(st)), reps, "xfer workgroup probe")
+            except RuntimeError:
                 self.engine.set_xfer_blocks(old)
-                raise RuntimeError(f"xfer workgroup probe failed on a rank{f': {err}' if err is not None else ''}")
-            el = float(t[0])
+                raise
             res[int(cap)] = round(self.total * self.push_bytes_per_elem / max(el, 1e-9) / 1e9, 1) if el > 0 else None
         ok = {c: v for c, v in res.items() if v}
         if not ok:  # no worker timed anything (a pure-owner world): keep the default
@@ -926,15 +843,8 @@ class AsyncPS:
         self.engine.close_peers()
         self.engine.free_local()
         self.engine = None
-        self._release_model()
+        self.flat.release()
         self.closed = True
-
-    def _release_model(self):
-        for h in self._hooks:
-            h.remove()
-        for m in self.model.modules():
-            if getattr(m, "_psd_grad_sink", None) == self._sink:
-                del m._psd_grad_sink
 
     def close(self):
         """Collective: stop the engine, unmap the peers' memory, free this rank's (all ranks call).
@@ -952,7 +862,7 @@ class AsyncPS:
         self._final = (hist, vers, log)
         self.engine.free_local()
         self.engine = None
-        self._release_model()
+        self.flat.release()
         self.closed = True
 
     def staleness_histogram(self):
@@ -985,7 +895,7 @@ class AsyncPS:
             d.set(lr=lr * self.hyper["lr_factor"])
 
     def num_params(self) -> int:
-        return sum(k for (_, _, _, k) in self._layout)
+        return self.flat.num_params()
 
     def state_dict(self) -> dict:
         """This rank's shard state (call after ``drain``)."""
@@ -996,17 +906,17 @@ class AsyncPS:
                 "step_idx": self.step_idx}
 
     # ------------------------------------------------------------------ checkpoint / resume
-    def _quiesce(self):
-        """Collective: every push so far applied at every shard, so the masters, optimizer state,
-        versions and clocks form one consistent cut."""
-        self.drain()
+    def _shard_tensors(self, k: int) -> list:
+        """Shard k's tensors in the order a checkpoint file holds them: fp32 master, step scalars, the
+        optimizer states that exist."""
+        return [self.master[k], self.dyn[k].t] + [d[k] for d in (self.state1, self.state2) if k in d]
 
     def _layout_meta(self) -> dict:
         return {"world": self.world, "owners": self.owners, "workers": self.worker_ranks, "P": self.P,
                 "shard_off": self.shard_off, "shard_len": self.shard_len, "total": self.total,
                 "staleness": self.S, "semantics": self.semantics, "round": self.round, "push_dtype": self.push_dtype,
                 "push_error_feedback": self.push_error_feedback,
-                "optimizer": self.cfg.to_dict(), "params": [(n, list(p.shape), o, k) for (n, p, o, k) in self._layout]}
+                "optimizer": self.cfg.to_dict(), "params": self.flat.param_meta()}
 
     def save(self, prefix: str, blocking: bool = True):
         """Sharded checkpoint (collective: every rank calls at the same step). After a drain, each
@@ -1026,26 +936,21 @@ class AsyncPS:
         import json
         import threading
 
-        self._quiesce()
+        self.drain()  # masters, optimizer state, versions and clocks now form one consistent cut
         C = native()
         snap = []
         meta = {"step_idx": self.step_idx if self.is_worker else None, "shards": {}}
         for k in self.my_shards:
-            ts = [self.master[k], self.dyn[k].t] + [d[k] for d in (self.state1, self.state2) if k in d]
+            ts = self._shard_tensors(k)
             snap.extend(t.detach().clone() for t in ts)
             meta["shards"][str(k)] = {"version": int(self.engine.version(k)), "clocks": list(self.engine.clocks(k)),
                                       "n": len(ts)}
         # error feedback: this worker's residual, one extra tensor after the shard tensors. The drain
-        # above left the comm streams idle, so no push is rewriting it.
+        # above left the comm stream idle, so no push is rewriting it.
         meta["push_residual"] = self.push_residual is not None
         if self.push_residual is not None:
             snap.append(self.push_residual.detach().clone())
-        # the workers' step (the owners that are not workers learn it from the store)
-        steps = torch.tensor([self.step_idx if self.is_worker else 0], dtype=torch.int64)
-        if self.world > 1 and dist.is_initialized():
-            steps = steps.to(self.device) if dist.get_backend() == "nccl" else steps
-            dist.all_reduce(steps, op=dist.ReduceOp.MAX)
-        meta["step_idx"] = int(steps.item())
+        meta["step_idx"] = self._workers_step()
         if self.is_cuda:
             torch.cuda.synchronize(self.device)
         self._barrier(f"ckpt-snap-{self._ckpt_seq}")  # every owner's snapshot taken before anyone pushes
@@ -1096,13 +1001,8 @@ class AsyncPS:
         i = 0
         for k in self.my_shards:
             sh = m["shards"][str(k)]
-            self.master[k].copy_(ts[i])
-            self.dyn[k].t.copy_(ts[i + 1])
-            j = i + 2
-            for d in (self.state1, self.state2):
-                if k in d:
-                    d[k].copy_(ts[j])
-                    j += 1
+            for dst, src in zip(self._shard_tensors(k), ts[i:]):
+                dst.copy_(src)
             i += sh["n"]
             self.engine.publish_initial(k, sh["version"], sh["clocks"])
         # error feedback: restored when on and the file carries a residual; zero when the file has none
@@ -1125,18 +1025,6 @@ class AsyncPS:
             if self.is_cuda:
                 torch.cuda.synchronize(self.device)
 
-    def _canon_index(self):
-        """(flat offset, canonical offset, numel) per parameter, canonical = model.named_parameters
-        order without padding (the layout CollectivePS.canonical_state uses too)."""
-        where = {id(p): (o, k) for (_n, p, o, k) in self._layout}
-        out, c = [], 0
-        for _, p in self.model.named_parameters():
-            if id(p) in where:
-                o, k = where[id(p)]
-                out.append((o, c, k))
-                c += k
-        return out, c
-
     def canonical_keys(self) -> list:
         return ["master", "state1", "state2"][: 1 + self.cfg.num_states]
 
@@ -1148,22 +1036,16 @@ class AsyncPS:
         """Collective: drain, then gather every shard's fp32 master + optimizer state onto rank
         ``root`` in the layout-independent canonical order (owners hold disjoint ranges: a sum
         reduce is the gather). Returns the tensors on ``root``, None elsewhere."""
-        self._quiesce()
-        idx, n = self._canon_index()
+        self.drain()
         out = {}
-        for key, src in (("master", self.master), ("state1", self.state1), ("state2", self.state2)):
-            if (key == "state1" and self.cfg.num_states < 1) or (key == "state2" and self.cfg.num_states < 2):
-                continue
+        for key in self.canonical_keys():
             full = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-            for k, t in src.items():
+            for k, t in getattr(self, key).items():
                 full.narrow(0, self.shard_off[k], self.shard_len[k]).copy_(t)
             if self.world > 1 and dist.is_initialized():
                 dist.reduce(full, root)
             if self.rank == root:
-                canon = torch.empty(n, dtype=torch.float32, device=self.device)
-                for o, c, k in idx:
-                    canon.narrow(0, c, k).copy_(full.narrow(0, o, k))
-                out[key] = canon
+                out[key] = self.flat.to_canonical(full)
         # step scalars: every shard advanced in lock-step (one apply per round), take shard 0's
         d = self.dyn[0].t.detach().clone() if 0 in self.dyn else torch.zeros(8, dtype=torch.int32, device=self.device)
         if self.world > 1 and dist.is_initialized():
@@ -1181,18 +1063,8 @@ class AsyncPS:
         """Inverse of ``canonical_state`` for this (possibly different) world and shard layout:
         every rank passes the full canonical tensors; owners keep their ranges and re-publish them
         (version 0 of this plane), workers take the weights."""
-        idx, n = self._canon_index()
-        full = {}
-        for key in ("master", "state1", "state2"):
-            if key not in sd:
-                continue
-            canon = sd[key].to(self.device)
-            if canon.numel() != n:
-                raise ValueError(f"canonical {key} has {canon.numel()} elements, model has {n}")
-            f = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-            for o, c, k in idx:
-                f.narrow(0, o, k).copy_(canon.narrow(0, c, k))
-            full[key] = f
+        full = {key: self.flat.from_canonical(sd[key].to(self.device), key)
+                for key in ("master", "state1", "state2") if key in sd}
         self.engine.stop()
         for k in self.my_shards:
             for key, dst in (("master", self.master), ("state1", self.state1), ("state2", self.state2)):
@@ -1231,7 +1103,7 @@ class AsyncPS:
         if self.rank != 0:
             return
         names, shapes, vals = [], [], []
-        idx, _ = self._canon_index()
+        idx, _ = self.flat.canon_index()
         params = [(n, p) for n, p in self.model.named_parameters() if p.requires_grad]
         for (n, p), (_o, c, k) in zip(params, idx):
             names.append(n)

@@ -39,13 +39,9 @@ from .. import native
 from ..ops import multi_reduce_
 from ..ops.optim import OptimConfig, OptimDyn, advance_, apply_no_advance_
 from ..utils.config import feature
+from .flat import ALIGN, FlatBinding, _round, install_fp8_weights, spread_owners
+from .flat import zero_grads_, zero_plan  # noqa: F401 -- importable from here as before (tests/test_collective_ps.py)
 from .transport import LocalTransport, Transport
-
-ALIGN = 64  # elements: every tensor starts 128-B aligned in the bf16 buffers
-
-
-def _round(x: int, a: int) -> int:
-    return (x + a - 1) // a * a
 
 
 @dataclass
@@ -57,69 +53,6 @@ class Bucket:
     slice_numel: int = 0
     local_offset: int = 0  # offset of this rank's owned slice inside the local shard buffers
     pending: int = 0
-    launched: bool = False
-
-
-def zero_plan(spans, total: int, max_ranges: int = 8):
-    """Ranges of a flat gradient buffer to zero before a step: the merged ``(offset, numel)`` spans of
-    the parameters whose gradients are *accumulated* into their views (everything but the grad-sink
-    params, whose kernels overwrite their views). ``None`` (zero the whole buffer in one launch)
-    when that is most of the buffer or would take more than ``max_ranges`` launches. BERT-base:
-    the embeddings only, 24M of 110M elements."""
-    merged = []
-    for off, n in sorted(spans):
-        if merged and off <= merged[-1][0] + merged[-1][1]:
-            merged[-1][1] = max(merged[-1][1], off + n - merged[-1][0])
-        else:
-            merged.append([off, n])
-    if len(merged) > max_ranges or sum(n for _, n in merged) > total // 2:
-        return None
-    return [tuple(r) for r in merged]
-
-
-def zero_grads_(flat: torch.Tensor, plan) -> None:
-    if plan is None:
-        flat.zero_()
-        return
-    for off, n in plan:
-        flat.narrow(0, off, n).zero_()
-
-
-def install_fp8_weights(model: nn.Module, resolve) -> None:
-    """Give every fp8 module (``fp8 = True``) a ``_psd_w8(w2)`` hook that returns the MX e4m3 copy
-    of its weight the data plane pulled with the bf16 working copy -- views (q [Cout, K], E8M0
-    scales [Cout*K/32]) into the flat fp8 buffers -- or None when the weight is not in them.
-    ``resolve()`` -> (q_flat, scale_flat, params_flat) of the current working buffers (AsyncPS
-    alternates two)."""
-    for m in model.modules():
-        w = getattr(m, "weight", None)
-        if not getattr(m, "fp8", False) or not isinstance(w, nn.Parameter):
-            continue
-
-        def pub(w2, m=m):
-            bufs = resolve()
-            if bufs is None:
-                return None
-            qf, sf, pf = bufs
-            wt = m.weight
-            off = (wt.data_ptr() - pf.data_ptr()) // wt.element_size()
-            n = wt.numel()
-            if off < 0 or off + n > pf.numel() or off % 32 or n % 32 or w2.numel() != n:
-                return None
-            return qf.narrow(0, off, n).view(w2.shape), sf.narrow(0, off // 32, n // 32)
-
-        m._psd_w8 = pub
-
-
-def _flat_view(flat: torch.Tensor, off: int, p: torch.Tensor) -> torch.Tensor:
-    """View of ``flat[off:off+numel]`` with the same shape *and strides* as ``p`` (channels_last
-    conv weights stay channels_last)."""
-    n = p.numel()
-    seg = flat.narrow(0, off, n)
-    if p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last) and not p.is_contiguous():
-        o, i, kh, kw = p.shape
-        return seg.view(o, kh, kw, i).permute(0, 3, 1, 2)
-    return seg.view(p.shape)
 
 
 class CollectivePS:
@@ -169,14 +102,8 @@ class CollectivePS:
         # collectives with zero gradients and apply/publish their shards.
         self.worker_ranks = list(worker_ranks) if worker_ranks is not None else list(range(self.world))
         self.is_worker = self.rank in self.worker_ranks
-        if ps_ranks is not None:
-            self.owners = list(ps_ranks)
-            self.P = len(self.owners)
-        else:
-            self.P = num_shards or self.world
-            if not 1 <= self.P <= self.world:
-                raise ValueError(f"num_shards must be in [1, world={self.world}], got {self.P}")
-            self.owners = [k * self.world // self.P for k in range(self.P)]
+        self.owners = list(ps_ranks) if ps_ranks is not None else spread_owners(num_shards or self.world, self.world)
+        self.P = len(self.owners)
         if not self.owners or any(not 0 <= r < self.world for r in self.owners) or len(set(self.owners)) != self.P:
             raise ValueError(f"invalid PS ranks {self.owners} for world {self.world}")
         self.my_shards = [k for k, r in enumerate(self.owners) if r == self.rank]
@@ -233,21 +160,16 @@ class CollectivePS:
         self.local_total = lo
 
         dev = self.device
+        self.flat = FlatBinding(model, [e for b in buckets for e in b.params], self.total)
         # fp32 staging of the initial values (rank-consistent init is the caller's job: same seed)
-        init = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        for b in buckets:
-            for _, p, o, _n in b.params:
-                _flat_view(init, o, p).copy_(p.detach().float())
+        init = self.flat.initial(dev)
         self.params_flat = init.to(param_dtype)
         self.grads_flat = torch.zeros(self.total, dtype=grad_dtype, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         self.master = torch.zeros(max(self.local_total, ALIGN), **f32)
         self.state1 = torch.zeros_like(self.master) if optim.num_states >= 1 else None
         self.state2 = torch.zeros_like(self.master) if optim.num_states >= 2 else None
-        for b in buckets:
-            for j, k in enumerate(self.my_shards):
-                src = init.narrow(0, b.offset + k * b.slice_numel, b.slice_numel)
-                self.master.narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel).copy_(src)
+        self._scatter_owned(init, self.master)
         del init
         # gradient slots for bounded staleness (slot s holds the reduced owned slices of one step)
         # (S = 0 reduces in place inside the gradient buffer and needs none)
@@ -273,42 +195,16 @@ class CollectivePS:
             self.p8_amax = torch.zeros(len(buckets) * self.P, dtype=torch.float32, device=dev)
             self.p8_mx = torch.full((self.total // 32,), 127, dtype=torch.uint8, device=dev) if self.pull_mx else None
 
-        # Modules that can write their parameter gradients straight into our flat buffer (fused BN)
-        # get a grad sink; their params keep .grad = None so autograd adopts the written view
-        # instead of launching an accumulate kernel.
-        self._grad_views = {}
-        self._direct = set()
-        for m in model.modules():
-            if hasattr(m, "psd_direct_grad_params"):
-                for dp in m.psd_direct_grad_params():
-                    if dp is not None and dp.requires_grad:
-                        self._direct.add(id(dp))
-                m._psd_grad_sink = self._sink
         # re-point the model at the flat buffers
-        for b in buckets:
-            for _, p, o, _n in b.params:
-                p.data = _flat_view(self.params_flat, o, p)
-                self._grad_views[id(p)] = _flat_view(self.grads_flat, o, p)
-                p.grad = None if id(p) in self._direct else self._grad_views[id(p)]
-        self._direct_params = [p for b in buckets for (_, p, _o, _n) in b.params if id(p) in self._direct]
-        # grad-sink views are overwritten every step: only the accumulated ones need zeroing (a sink
-        # param that gets no gradient in a step is zeroed when its bucket is flushed)
-        self._zero_plan = zero_plan([(o, p.numel()) for b in buckets for (_, p, o, _n) in b.params
-                                     if id(p) not in self._direct], self.grads_flat.numel())
-        self._arrived: set = set()
-        self._hooks = []
-        self._p2b = {}
-        for b in buckets:
-            for _, p, _o, _n in b.params:
-                self._p2b[id(p)] = b
-        for b in buckets:
-            for _, p, _o, _n in b.params:
-                self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
+        self.flat.bind_params(self.params_flat)
+        self.flat.bind_grads(self.grads_flat)
+        self._zero_plan = self.flat.zero_plan
+        self.flat.set_buckets(buckets)
+        self.flat.watch(self._launch, overlap)
         if self.is_cuda:
             self.comm_stream = torch.cuda.Stream(device=dev)
             self.ready_events = [torch.cuda.Event() for _ in buckets]
         self._advanced = False
-        self._next = 0
         self.tracer = None  # utils.trace.StepTracer (set by the Trainer)
         self._sync_init()
         if self.pull_mx:
@@ -320,7 +216,7 @@ class CollectivePS:
         if self.pull_fp8:
             for b in self.buckets:
                 for j, k in enumerate(self.my_shards):
-                    self._quant_slice(b, k, self.master.narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel))
+                    self._quant_slice(b, k, self.master.narrow(0, *self._local(b, j)))
             for b in self.buckets:
                 self._pull(b)
             return
@@ -331,13 +227,27 @@ class CollectivePS:
         if self.is_cuda:
             torch.cuda.synchronize(self.device)
 
-    def _sink(self, p):
-        """Flat-gradient view a fused op may write ``p``'s gradient into (or None)."""
-        if id(p) not in self._direct:
-            return None
-        v = self._grad_views[id(p)]
-        # a fresh view (refcount 1) so autograd's AccumulateGrad adopts it instead of cloning
-        return v.view(v.shape)
+    def _local(self, b: Bucket, j: int):
+        """(offset, numel) of my j-th owned slice of bucket b in the local shard buffers."""
+        return b.local_offset + j * b.slice_numel, b.slice_numel
+
+    def _flat(self, b: Bucket, k: int):
+        """(offset, numel) of shard k's slice of bucket b in the flat buffers."""
+        return b.offset + k * b.slice_numel, b.slice_numel
+
+    def _gather_owned(self, src: torch.Tensor) -> torch.Tensor:
+        """A full flat fp32 buffer holding my owned slices of local buffer ``src``, zero elsewhere."""
+        full = torch.zeros(self.total, dtype=torch.float32, device=self.device)
+        for b in self.buckets:
+            for j, k in enumerate(self.my_shards):
+                full.narrow(0, *self._flat(b, k)).copy_(src.narrow(0, *self._local(b, j)))
+        return full
+
+    def _scatter_owned(self, full: torch.Tensor, dst: torch.Tensor):
+        """Inverse of ``_gather_owned``: my owned slices of ``full`` into local buffer ``dst``."""
+        for b in self.buckets:
+            for j, k in enumerate(self.my_shards):
+                dst.narrow(0, *self._local(b, j)).copy_(full.narrow(0, *self._flat(b, k)))
 
     def memory_bytes(self) -> dict:
         eb = lambda t: 0 if t is None else t.numel() * t.element_size()  # noqa: E731
@@ -349,14 +259,9 @@ class CollectivePS:
         """Call before forward: zero the gradient buffer and reset bucket bookkeeping."""
         if track:
             self.account_begin()
-        zero_grads_(self.grads_flat, self._zero_plan)
-        self._arrived = set()
-        for p in self._direct_params:
+        self.flat.begin(self.grads_flat)
+        for p in self.flat.direct_params:
             p.grad = None
-        for b in self.buckets:
-            b.pending = len(b.params)
-            b.launched = False
-        self._next = 0
         self._advanced = False
 
     def account_begin(self):
@@ -377,38 +282,15 @@ class CollectivePS:
         self.begin_step()
         self.finish_step()
 
-    def _on_grad(self, p):
-        self._arrived.add(id(p))
-        if id(p) in self._direct:
-            v = self._grad_views[id(p)]
-            if p.grad is not None and p.grad.data_ptr() != v.data_ptr():
-                v.copy_(p.grad)  # producer did not use the sink (reference / CPU path)
-        b = self._p2b[id(p)]
-        b.pending -= 1
-        if not self.overlap:
-            return
-        # Launch strictly in bucket order so every rank enqueues the same collective sequence
-        # (an out-of-order ready bucket waits for its predecessors).
-        while self._next < len(self.buckets) and self.buckets[self._next].pending <= 0:
-            self._launch(self.buckets[self._next])
-            self._next += 1
-
     def finish_step(self, track: bool = True):
         """Call after backward: flush buckets whose hooks did not fire and join the comm stream."""
-        while self._next < len(self.buckets):
-            self._launch(self.buckets[self._next])
-            self._next += 1
+        self.flat.launch_ready(flush=True)
         if self.is_cuda:
             torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
         if track:
             self.account_finish()
 
     def _launch(self, b: Bucket):
-        b.launched = True
-        if b.pending > 0 and self._zero_plan is not None:  # flushed with gradients missing
-            for _, p, _o, _n in b.params:
-                if id(p) in self._direct and id(p) not in self._arrived:
-                    self._grad_views[id(p)].zero_()
         if self.is_cuda:
             ev = self.ready_events[b.index]
             ev.record(torch.cuda.current_stream(self.device))
@@ -431,9 +313,9 @@ class CollectivePS:
         out = []
         for j, k in enumerate(self.my_shards):
             if slot is None:  # in-place in the gradient buffer
-                out.append(self.grads_flat.narrow(0, b.offset + k * b.slice_numel, b.slice_numel))
+                out.append(self.grads_flat.narrow(0, *self._flat(b, k)))
             else:
-                out.append(self.slots[slot].narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel))
+                out.append(self.slots[slot].narrow(0, *self._local(b, j)))
         return out
 
     def _inbox_views(self, b: Bucket, j: int):
@@ -460,7 +342,7 @@ class CollectivePS:
             if slot is None:
                 self._p2p_sources[j] = srcs  # S = 0: summed inside the fused apply
             else:
-                multi_reduce_(self.slots[slot].narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel), srcs)
+                multi_reduce_(self.slots[slot].narrow(0, *self._local(b, j)), srcs)
 
     def _push(self, b: Bucket, slot: int | None):
         g = self.grads_flat.narrow(0, b.offset, b.numel)
@@ -489,11 +371,11 @@ class CollectivePS:
         for j, (k, gv) in enumerate(zip(self.my_shards, self._owned_grad_views(b, slot))):
             if self.push_p2p and slot is None:
                 gv = self._p2p_sources[j]
-            lo = b.local_offset + j * b.slice_numel
-            m = self.master.narrow(0, lo, b.slice_numel)
-            s1 = None if self.state1 is None else self.state1.narrow(0, lo, b.slice_numel)
-            s2 = None if self.state2 is None else self.state2.narrow(0, lo, b.slice_numel)
-            shadow = self.params_flat.narrow(0, b.offset + k * b.slice_numel, b.slice_numel)
+            lo = self._local(b, j)
+            m = self.master.narrow(0, *lo)
+            s1 = None if self.state1 is None else self.state1.narrow(0, *lo)
+            s2 = None if self.state2 is None else self.state2.narrow(0, *lo)
+            shadow = self.params_flat.narrow(0, *self._flat(b, k))
             if self.pull_fp8:
                 apply_no_advance_(self.cfg, self.dyn, m, gv, s1, s2, None)
                 self._quant_slice(b, k, m)
@@ -506,15 +388,14 @@ class CollectivePS:
     def _quant_slice(self, b: Bucket, k: int, src: torch.Tensor):
         C = native()
         if self.pull_mx:
-            lo = b.offset + k * b.slice_numel
-            C.quant_mx_(src, self.p8.narrow(0, lo, b.slice_numel), self.p8_mx.narrow(0, lo // 32, b.slice_numel // 32))
+            lo, n = self._flat(b, k)
+            C.quant_mx_(src, self.p8.narrow(0, lo, n), self.p8_mx.narrow(0, lo // 32, n // 32))
             return
         i = b.index * self.P + k
         amax = self.p8_amax.narrow(0, i, 1)
         amax.zero_()
         C.amax_(src, amax)
-        C.quant_fp8_(src, amax, 448.0, self.p8.narrow(0, b.offset + k * b.slice_numel, b.slice_numel),
-                     self.p8_scale.narrow(0, i, 1))
+        C.quant_fp8_(src, amax, 448.0, self.p8.narrow(0, *self._flat(b, k)), self.p8_scale.narrow(0, i, 1))
 
     def _pull_fp8(self, b: Bucket):
         C = native()
@@ -544,9 +425,8 @@ class CollectivePS:
                     self.t.broadcast(q.narrow(0, k * b.slice_numel, b.slice_numel), owner)
                     self.t.broadcast(sc.narrow(0, k, 1), owner)
         for k in range(self.P):
-            lo = b.offset + k * b.slice_numel
-            C.dequant_fp8_(self.p8.narrow(0, lo, b.slice_numel), sc.narrow(0, k, 1),
-                           self.params_flat.narrow(0, lo, b.slice_numel))
+            sl = self._flat(b, k)
+            C.dequant_fp8_(self.p8.narrow(0, *sl), sc.narrow(0, k, 1), self.params_flat.narrow(0, *sl))
 
     def _pull(self, b: Bucket):
         if self.pull_fp8:
@@ -613,12 +493,11 @@ class CollectivePS:
         # the published fp8 buffers still hold the pre-load weights)
         for b in self.buckets:
             for j, k in enumerate(self.my_shards):
-                lo = b.local_offset + j * b.slice_numel
-                m = self.master.narrow(0, lo, b.slice_numel)
+                m = self.master.narrow(0, *self._local(b, j))
                 if self.pull_fp8:
                     self._quant_slice(b, k, m)
                 else:
-                    self.params_flat.narrow(0, b.offset + k * b.slice_numel, b.slice_numel).copy_(m)
+                    self.params_flat.narrow(0, *self._flat(b, k)).copy_(m)
         for b in self.buckets:
             self._pull(b)
 
@@ -628,8 +507,7 @@ class CollectivePS:
                 "worker_ranks": self.worker_ranks, "staleness": self.S, "step_idx": self.step_idx,
                 "optimizer": self.cfg.to_dict(), "total": self.total,
                 "buckets": [{"offset": b.offset, "numel": b.numel, "slice": b.slice_numel,
-                             "params": [(n, list(p.shape), o, k) for (n, p, o, k) in b.params]}
-                            for b in self.buckets]}
+                             "params": self.flat.param_meta(b.params)} for b in self.buckets]}
 
     def save(self, prefix: str, blocking: bool = True):
         """Write this rank's PS shards (fp32 masters, optimizer state, step scalars) to
@@ -715,15 +593,11 @@ class CollectivePS:
     def export_reference(self, path: str, epoch: int, iteration: int = 0):
         """Gather the fp32 masters and write the reference's binary checkpoint layout on rank 0
         (collective: every rank must call)."""
-        full = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-        for b in self.buckets:
-            for j, k in enumerate(self.my_shards):
-                full.narrow(0, b.offset + k * b.slice_numel, b.slice_numel).copy_(
-                    self.master.narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel))
+        full = self._gather_owned(self.master)
         if self.world > 1:
             for b in self.buckets:
                 for k, owner in enumerate(self.owners):
-                    self.t.broadcast(full.narrow(0, b.offset + k * b.slice_numel, b.slice_numel), owner)
+                    self.t.broadcast(full.narrow(0, *self._flat(b, k)), owner)
         if self.rank != 0:
             return
         names, shapes, tensors = [], [], []
@@ -738,15 +612,7 @@ class CollectivePS:
     def close(self):
         """Detach from the model (grad hooks, grad sinks) so a new CollectivePS over a different
         world can take it over; the model keeps its current parameter values."""
-        for h in self._hooks:
-            h.remove()
-        self._hooks = []
-        for m in self.model.modules():
-            if getattr(m, "_psd_grad_sink", None) == self._sink:
-                del m._psd_grad_sink
-        for p in self.model.parameters():
-            p.grad = None
-            p.data = p.data.clone()
+        self.flat.release(detach=True)
 
     def drain(self):
         """Apply the up-to-S reduced gradients still in flight (steps t-S .. t-1) and publish the
@@ -770,38 +636,23 @@ class CollectivePS:
         if stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(stream)
 
-    def _canon_index(self):
-        """(flat offset, canonical offset, numel) per parameter, canonical = model.named_parameters
-        order without padding -- a layout independent of world size, shard count and buckets."""
-        where = {id(p): (o, n) for b in self.buckets for (_, p, o, n) in b.params}
-        out, c = [], 0
-        for _, p in self.model.named_parameters():
-            if id(p) in where:
-                o, n = where[id(p)]
-                out.append((o, c, n))
-                c += n
-        return out, c
+    def canonical_keys(self) -> list:
+        return ["master", "state1", "state2"][: 1 + self.cfg.num_states]
+
+    def dyn_template(self) -> torch.Tensor:
+        """A tensor shaped like the step-scalar block (the receive buffer of a broadcast)."""
+        return self.dyn.t
 
     def canonical_state(self, root: int) -> dict:
         """Gather the fp32 masters + optimizer state of every shard onto rank ``root`` in the
         canonical layout (collective). Returns the tensors on ``root``, None elsewhere."""
-        idx, n = self._canon_index()
         out = {}
-        for key, src in (("master", self.master), ("state1", self.state1), ("state2", self.state2)):
-            if src is None:
-                continue
-            full = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-            for b in self.buckets:
-                for j, k in enumerate(self.my_shards):
-                    full.narrow(0, b.offset + k * b.slice_numel, b.slice_numel).copy_(
-                        src.narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel))
+        for key in self.canonical_keys():
+            full = self._gather_owned(getattr(self, key))
             if self.world > 1:
                 self.t.reduce(full, root)  # owners hold disjoint slices: the sum is the gather
             if self.rank == root:
-                canon = torch.empty(n, dtype=torch.float32, device=self.device)
-                for o, c, k in idx:
-                    canon.narrow(0, c, k).copy_(full.narrow(0, o, k))
-                out[key] = canon
+                out[key] = self.flat.to_canonical(full)
         if self.rank != root:
             return None
         out["dyn"] = self.dyn.t.detach().clone()
@@ -810,26 +661,16 @@ class CollectivePS:
     def load_canonical_state(self, sd: dict):
         """Inverse of ``canonical_state`` for this (possibly different) world: every rank passes the
         full canonical tensors; owners keep their slices and every rank publishes the weights."""
-        idx, n = self._canon_index()
-        for key, dst in (("master", self.master), ("state1", self.state1), ("state2", self.state2)):
-            if dst is None or key not in sd:
+        for key in self.canonical_keys():
+            if key not in sd:
                 continue
-            canon = sd[key].to(self.device)
-            if canon.numel() != n:
-                raise ValueError(f"canonical {key} has {canon.numel()} elements, model has {n}")
-            full = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-            for o, c, k in idx:
-                full.narrow(0, o, k).copy_(canon.narrow(0, c, k))
-            for b in self.buckets:
-                for j, k in enumerate(self.my_shards):
-                    dst.narrow(0, b.local_offset + j * b.slice_numel, b.slice_numel).copy_(
-                        full.narrow(0, b.offset + k * b.slice_numel, b.slice_numel))
+            full = self.flat.from_canonical(sd[key].to(self.device), key)
+            self._scatter_owned(full, getattr(self, key))
             if key == "master":
                 if self.pull_fp8:
                     for b in self.buckets:
                         for j, k in enumerate(self.my_shards):
-                            self._quant_slice(b, k, self.master.narrow(0, b.local_offset + j * b.slice_numel,
-                                                                       b.slice_numel))
+                            self._quant_slice(b, k, self.master.narrow(0, *self._local(b, j)))
                         self._pull(b)
                 else:
                     self.params_flat.copy_(full)
@@ -846,7 +687,7 @@ class CollectivePS:
         return {n: p.detach().float().clone() for n, p in self.model.named_parameters()}
 
     def num_params(self) -> int:
-        return sum(n for b in self.buckets for (_, _, _, n) in b.params)
+        return self.flat.num_params()
 
     def describe(self) -> str:
         return (f"CollectivePS(world={self.world}, shards={self.P} on ranks {self.owners}, staleness={self.S}, "

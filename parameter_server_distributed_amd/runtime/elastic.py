@@ -430,18 +430,14 @@ class ElasticTrainer:
 
     def _broadcast_state(self, ps, state):
         """New rank 0 holds the canonical state; give every rank a copy."""
-        idx, n = ps._canon_index()
-        if hasattr(ps, "canonical_keys"):  # AsyncPS: optimizer states from its config
-            keys = ps.canonical_keys()
-        else:
-            keys = ["master"] + [k for k, t in (("state1", ps.state1), ("state2", ps.state2)) if t is not None]
+        n = ps.num_params()
         out = {}
-        for k in keys:
+        for k in ps.canonical_keys():
             t = state[k].to(self.device) if dist.get_rank() == 0 else torch.empty(n, dtype=torch.float32,
                                                                                   device=self.device)
             dist.broadcast(t, 0)
             out[k] = t
-        dyn = ps.dyn_template() if hasattr(ps, "dyn_template") else ps.dyn.t
+        dyn = ps.dyn_template()
         d = state["dyn"].to(dyn.device) if dist.get_rank() == 0 else torch.empty_like(dyn)
         dist.broadcast(d, 0)
         out["dyn"] = d
