@@ -22,6 +22,8 @@ import torch.nn.functional as F
 
 from ..utils.config import feature as _feat
 from .. import native
+from .handover import (BnFwd, FoldPending, Q8Pending, StridedDr, bn_momentum, dual_from_fold, pop_dr,  # noqa: F401
+                       route_res_grad, sinks, take, take_dr)
 
 
 def _kernel_ok(x: torch.Tensor) -> bool:
@@ -47,14 +49,8 @@ def _q8_args(mod, x: torch.Tensor) -> dict:
 def _stats_args(mod, x: torch.Tensor) -> dict:
     """The batch-statistics partials the producing convolution reduced in its epilogue for exactly
     this tensor (ops/conv.py, kernels/convn.hip), as bn_fwd arguments; consumed once."""
-    pend = getattr(mod, "_psd_stats_pending", None)
-    if pend is None:
-        return {}
-    mod._psd_stats_pending = None
-    y, part, rows = pend
-    if y.data_ptr() != x.data_ptr() or y.shape != x.shape or y.stride() != x.stride():
-        return {}
-    return {"part_in": part, "part_rows": rows}
+    pend = take(mod, "_psd_stats_pending", x, strides=True)
+    return {} if pend is None else {"part_in": pend.part, "part_rows": pend.rows}
 
 
 def _dq8_args(mod, x: torch.Tensor) -> dict:
@@ -72,34 +68,12 @@ def _dq8_args(mod, x: torch.Tensor) -> dict:
 
 def _dq8_hand_over(mod, dx: torch.Tensor, kw: dict) -> None:
     if kw:
-        mod._psd_dq8_producer._psd_dq8_pending = (dx, kw["dq"], kw["dqmx"])
+        mod._psd_dq8_producer._psd_dq8_pending = Q8Pending(dx, kw["dq"], kw["dqmx"])
 
 
 def _q8_hand_over(mod, y: torch.Tensor, kw: dict) -> None:
     if kw:  # (y, e4m3 copy, its MX scales uint8 [numel / 32])
-        mod._psd_q8_consumer._psd_q8_pending = (y, kw["q8_out"], kw["q8_mx"])
-
-
-class StridedDr:
-    """A residual-branch gradient handed to a BN (``_psd_pending_dr``) by a stride-2 1x1 (downsample)
-    convolution, kept on its quarter grid: ``t4`` = dY . W of the strided positions, [N, C, H/2, W/2]
-    channels_last. The full-size gradient is zero except at even (h, w); the consumer convolution's
-    bwd-data epilogue adds it there (kernels/convn.hip bwd mode 5) and only other consumers build the
-    full tensor (``full``)."""
-
-    def __init__(self, t4: torch.Tensor, H: int, W: int):
-        self.t4, self.H, self.W = t4, H, W
-
-    def full(self) -> torch.Tensor:
-        n, c = self.t4.shape[:2]
-        out = torch.zeros(n, self.H, self.W, c, device=self.t4.device, dtype=self.t4.dtype).permute(0, 3, 1, 2)
-        out[:, :, ::2, ::2] = self.t4
-        return out
-
-
-def take_dr(t):
-    """A pending residual gradient as a full-size tensor (StridedDr materialised)."""
-    return t.full() if isinstance(t, StridedDr) else t
+        mod._psd_q8_consumer._psd_q8_pending = Q8Pending(y, kw["q8_out"], kw["q8_mx"])
 
 
 def _fold_target(mod, x: torch.Tensor):
@@ -121,7 +95,7 @@ def _hand_fold(conv, g, coef, x, P=None):
     fold wgrad products [g | x | 1]^T x_in already taken])."""
     conv._psd_fold_out = None
     conv._psd_fold_x = None
-    conv._psd_fold_pending = (g, coef, x) if P is None else (g, coef, x, P)
+    conv._psd_fold_pending = FoldPending(g, coef, x, P)
 
 
 def _fold_pair_ok(bn3, x, bnd, r):
@@ -149,12 +123,12 @@ class _FusedBNFn(torch.autograd.Function):
         has_res = residual is not None
         q8 = _q8_args(mod, x)
         y, mean, invstd, ss, mbits = C.bn_fwd(x, weight, bias, mod.running_mean, mod.running_var, residual, mod.relu,
-                                              True, mod.momentum if mod.momentum is not None else 0.1, mod.eps,
+                                              True, bn_momentum(mod), mod.eps,
                                               mod.num_batches_tracked, None, mask_out=mod.relu and has_res, **q8,
                                               **_stats_args(mod, x))
         _q8_hand_over(mod, y, q8)
         # for the consumer convolution's bwd-data epilogue (ops/conv.py _bn_bwd_fusion): ReLU BNs
-        mod._psd_fwd = (y, x, mean, ss, mbits if has_res else None, None, None) if mod.relu else None
+        mod._psd_fwd = BnFwd(y, x, mean, ss, mbits if has_res else None) if mod.relu else None
         ctx.relu = mod.relu
         ctx.has_res = residual is not None
         ctx.mod = mod
@@ -171,14 +145,8 @@ class _FusedBNFn(torch.autograd.Function):
         x, mbits, w, mean, invstd, ss = ctx.saved_tensors
         mod = ctx.mod
         mod._psd_fwd = None
-        sink = getattr(mod, "_psd_grad_sink", None)
-        dgo = dbo = None
-        if sink is not None and w is not None:
-            dgo, dbo = sink(mod.weight), sink(mod.bias)
-        pre = getattr(mod, "_psd_bwd_pre", None)
-        mod._psd_bwd_pre = None
-        if pre is not None and not (pre[0].data_ptr() == dy.data_ptr() and pre[0].shape == dy.shape):
-            pre = None
+        dgo, dbo = sinks(mod) if w is not None else (None, None)
+        pre = take(mod, "_psd_bwd_pre", dy, strides=False)
         # a residual BN (bn3) folds into its producing 1x1 convolution (its stored mask or the partials
         # the consumer's bwd-data epilogue pre-reduced). (bn1 folded into conv1 measured slower -- 70.9
         # vs 68.0 ms/step, profiles/r5/ab_bn1_fold.md -- and was removed in round 6.)
@@ -188,48 +156,31 @@ class _FusedBNFn(torch.autograd.Function):
             # BN-backward fold: reduction + finalize only; the producing 1x1 convolution's dgrad / wgrad
             # take g and the coefficients (no elementwise pass, no input-gradient tensor)
             if pre is not None:
-                g, coef, dg, db = native().bn_bwd_coef(pre[0], x, w, mean, invstd, part=pre[1], rows=pre[2],
+                g, coef, dg, db = native().bn_bwd_coef(pre.g, x, w, mean, invstd, part=pre.part, rows=pre.rows,
                                                        dgamma_out=dgo, dbeta_out=dbo)
             else:
-                dy2 = take_dr(mod._psd_pending_dr.pop()) if getattr(mod, "_psd_pending_dr", None) else None
-                g, coef, dg, db = native().bn_bwd_coef(dy, x, w, mean, invstd, mbits=mbits, dy2=dy2, dgamma_out=dgo,
-                                                       dbeta_out=dbo)
+                g, coef, dg, db = native().bn_bwd_coef(dy, x, w, mean, invstd, mbits=mbits, dy2=pop_dr(mod),
+                                                       dgamma_out=dgo, dbeta_out=dbo)
             _hand_fold(conv, g, coef, x)
-            res_grad = None
-            if ctx.has_res:
-                if ctx.resid_to is not None:
-                    ctx.resid_to._psd_pending_dr.append(g)
-                else:
-                    res_grad = g
-            return g, dg, db, res_grad, None, None
+            return g, dg, db, route_res_grad(ctx.resid_to, g), None, None  # (foldable: a residual BN)
         if pre is not None:
             # the consumer convolution's bwd-data epilogue reduced this BN's backward and wrote the
             # masked gradient g (= the residual-branch gradient for a residual BN): finalize + one
             # elementwise pass here
-            g, part, rows = pre
+            g = pre.g
             dq8 = _dq8_args(mod, x)
-            dx, dg, db = native().bn_bwd_pre(g, x, w, mean, invstd, part, rows, dgo, dbo, **dq8)
+            dx, dg, db = native().bn_bwd_pre(g, x, w, mean, invstd, pre.part, pre.rows, dgo, dbo, **dq8)
             _dq8_hand_over(mod, dx, dq8)
-            res_grad = None
-            if ctx.has_res:
-                if ctx.resid_to is not None:
-                    ctx.resid_to._psd_pending_dr.append(g)
-                else:
-                    res_grad = g
+            res_grad = route_res_grad(ctx.resid_to, g) if ctx.has_res else None
             return dx, (dg if w is not None else None), (db if w is not None else None), res_grad, None, None
         # residual-branch fusion: the identity-path gradient of this BN's output was stashed by the
         # next block's bn3 backward; fold it in here instead of an autograd add kernel
-        dy2 = take_dr(mod._psd_pending_dr.pop()) if getattr(mod, "_psd_pending_dr", None) else None
+        dy2 = pop_dr(mod)
         dq8 = _dq8_args(mod, x)
         dx, dr, dg, db = native().bn_bwd(dy, x, None, w, mean, invstd, ctx.relu, ctx.has_res, dgo, dbo, dy2, ss,
                                          mbits, **dq8)
         _dq8_hand_over(mod, dx, dq8)
-        res_grad = None
-        if ctx.has_res:
-            if ctx.resid_to is not None:
-                ctx.resid_to._psd_pending_dr.append(dr)
-            else:
-                res_grad = dr
+        res_grad = route_res_grad(ctx.resid_to, dr) if ctx.has_res else None
         return dx, (dg if w is not None else None), (db if w is not None else None), res_grad, None, None
 
 
@@ -243,14 +194,13 @@ class _BNAddBNReluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w3, b3, r, wd, bd, bn3, bnd):
         C = native()
-        mom = lambda m: m.momentum if m.momentum is not None else 0.1  # noqa: E731
         _, mean_d, invstd_d, ss_d, _ = C.bn_fwd(r, wd, bd, bnd.running_mean, bnd.running_var, None, False, True,
-                                                mom(bnd), bnd.eps, bnd.num_batches_tracked, None, stats_only=True,
-                                                **_stats_args(bnd, r))
+                                                bn_momentum(bnd), bnd.eps, bnd.num_batches_tracked, None,
+                                                stats_only=True, **_stats_args(bnd, r))
         q8 = _q8_args(bn3, x)
-        y, mean, invstd, _, mbits = C.bn_fwd(x, w3, b3, bn3.running_mean, bn3.running_var, r, True, True, mom(bn3),
-                                             bn3.eps, bn3.num_batches_tracked, None, mask_out=True, residual_ss=ss_d,
-                                             **q8, **_stats_args(bn3, x))
+        y, mean, invstd, _, mbits = C.bn_fwd(x, w3, b3, bn3.running_mean, bn3.running_var, r, True, True,
+                                             bn_momentum(bn3), bn3.eps, bn3.num_batches_tracked, None, mask_out=True,
+                                             residual_ss=ss_d, **q8, **_stats_args(bn3, x))
         _q8_hand_over(bn3, y, q8)
         # for the consumer convolution's bwd-data epilogue (ops/conv.py _bn_bwd_fusion, mode 3): both
         # BNs' backward reductions ride on it. With both BNs folded (layer 1) the epilogue reduces
@@ -258,7 +208,7 @@ class _BNAddBNReluFn(torch.autograd.Function):
         # the fold products: y3 and yd are not read there
         pair = _fold_pair_ok(bn3, x, bnd, r)
         ctx.pair = None if pair is None else (pair[0], pair[1], pair[0]._psd_fold_x, pair[1]._psd_fold_x)
-        bn3._psd_fwd = (y, x, mean, None, mbits, r, mean_d) if pair is None else (y, None, mean, None, mbits, None, None)
+        bn3._psd_fwd = BnFwd(y, x, mean, None, mbits, r, mean_d) if pair is None else BnFwd(y, None, mean, None, mbits)
         ctx.bn3, ctx.bnd = bn3, bnd
         ctx.save_for_backward(x, mbits, w3, mean, invstd, r, wd, mean_d, invstd_d)
         return y
@@ -268,45 +218,24 @@ class _BNAddBNReluFn(torch.autograd.Function):
         x, mbits, w3, mean, invstd, r, wd, mean_d, invstd_d = ctx.saved_tensors
         bn3, bnd = ctx.bn3, ctx.bnd
         C = native()
-
-        def sinks(m):
-            sink = getattr(m, "_psd_grad_sink", None)
-            return (sink(m.weight), sink(m.bias)) if sink is not None else (None, None)
-
-        dg3o, db3o = sinks(bn3)
-        dgdo, dbdo = sinks(bnd)
+        (dg3o, db3o), (dgdo, dbdo) = sinks(bn3), sinks(bnd)
         bn3._psd_fwd = None
         conv = _fold_target(bn3, x)
-        pre = getattr(bn3, "_psd_bwd_pre", None)
-        bn3._psd_bwd_pre = None
+        pre = take(bn3, "_psd_bwd_pre", dy, strides=False)
         pair = ctx.pair
         ctx.pair = None
-        if pair is not None and pre is not None and len(pre) == 3 and pre[0].data_ptr() == dy.data_ptr() \
-                and pre[0].shape == dy.shape and conv is pair[0] and _fold_target(bnd, r) is pair[1]:
-            # the consumer reduced (sum g, -mean3 sum g); sum g y3 = sum_i W3 (g^T a2), sum g yd =
-            # sum_i Wd (g^T x_in) from the fold wgrads taken now (and handed on, not retaken)
-            g, part, rows = pre
-            if part.shape[0] <= rows:
-                raise RuntimeError("psd dual tail: the partials buffer has no row for sum g y")
+        if pair is not None and pre is not None and pre.part_d is None and conv is pair[0] \
+                and _fold_target(bnd, r) is pair[1]:
+            # the consumer reduced (sum g, -mean3 sum g); the rest comes from the fold products
             (c3, cd, a2, xin) = pair
-            Ps = []
-            for conv_, xin_ in ((c3, a2), (cd, xin)):
-                P = torch.empty(C.convw_fold_rows(conv_.weight.shape[0], conv_.weight.shape[1]), xin_.shape[1],
-                                device=g.device, dtype=torch.float32)
-                if not C.convw_(g, xin_, P, 1, 1, 1, 0, variant=int(_feat("convw_fold2")), fold=True):
-                    raise RuntimeError("psd dual tail: convw_ declined the fold wgrad")
-                Ps.append(P)
-            # the downsample BN's sums derive from bn3's sum g (same masked g) and its own sum g yd
-            part_d = torch.empty(2, part.shape[-1], device=part.device, dtype=torch.float32)
-            C.bnfold_rowdot(Ps[0], c3.weight, part[rows])
-            C.bnfold_rowdot(Ps[1], cd.weight, part_d)
-            _, _, dg3, db3, dgd, dbd, coef, coef_d = C.bn_bwd_dual_pre(
-                g, x, w3, mean, invstd, part, part_d, rows + 1, r, wd, mean_d, invstd_d, dg3o, db3o, dgdo, dbdo,
-                fold=True, fold_d=True, derive_d=True)
+            g = pre.g
+            Ps, dg3, db3, dgd, dbd, coef, coef_d = dual_from_fold(
+                pre, c3.weight, a2, cd.weight, xin, x, w3, mean, invstd, r, wd, mean_d, invstd_d, (dg3o, db3o),
+                (dgdo, dbdo))
             _hand_fold(c3, g, coef, x, Ps[0])
             _hand_fold(cd, g, coef_d, r, Ps[1])
             return g, dg3, db3, g, dgd, dbd, None, None
-        if pre is not None and len(pre) == 4 and pre[0].data_ptr() == dy.data_ptr() and pre[0].shape == dy.shape:
+        if pre is not None and pre.part_d is not None:
             # both reductions ran in the consumer convolution's bwd-data epilogue (convn mode 3): g is
             # the masked gradient incl. the residual branch; finalize both + one elementwise pass
             g, part, rows, part_d = pre
@@ -323,7 +252,7 @@ class _BNAddBNReluFn(torch.autograd.Function):
                     return g, dg3, db3, g, dgd, dbd, None, None
                 return g, dg3, db3, drr, dgd, dbd, None, None
             return dx, dg3, db3, drr, dgd, dbd, None, None
-        dy2 = take_dr(bn3._psd_pending_dr.pop()) if getattr(bn3, "_psd_pending_dr", None) else None
+        dy2 = pop_dr(bn3)
         if conv is not None:  # bn3's input gradient folded into conv3's backward (see _FusedBNFn)
             _, drr, dg3, db3, dgd, dbd, coef, g = C.bn_bwd_dual(dy, x, w3, mean, invstd, mbits, dy2, r, wd, mean_d,
                                                                 invstd_d, dg3o, db3o, dgdo, dbdo, fold=True)
@@ -353,7 +282,7 @@ class _BNReluPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, mod, pool):
         y, arg, mean, invstd, ss = native().bn_pool_fwd(x, weight, bias, mod.running_mean, mod.running_var,
-                                                        mod.momentum if mod.momentum is not None else 0.1, mod.eps,
+                                                        bn_momentum(mod), mod.eps,
                                                         mod.num_batches_tracked)
         ctx.mod, ctx.pool = mod, pool
         ctx.save_for_backward(x, arg, weight, mean, invstd, ss)
@@ -362,13 +291,8 @@ class _BNReluPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, arg, w, mean, invstd, ss = ctx.saved_tensors
-        sink = getattr(ctx.mod, "_psd_grad_sink", None)
-        dgo = dbo = None
-        if sink is not None:
-            dgo, dbo = sink(ctx.mod.weight), sink(ctx.mod.bias)
-        pend = getattr(ctx.pool, "_psd_pending_dr", None)
-        gy2 = pend.pop() if pend else None  # the first bottleneck's downsample-branch gradient
-        dx, dg, db = native().bn_pool_bwd(gy, gy2, arg, x, w, mean, invstd, ss, dgo, dbo)
+        gy2 = pop_dr(ctx.pool)  # the first bottleneck's downsample-branch gradient
+        dx, dg, db = native().bn_pool_bwd(gy, gy2, arg, x, w, mean, invstd, ss, *sinks(ctx.mod))
         return dx, dg, db, None, None
 
 
@@ -424,7 +348,7 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
         y = F.batch_norm(x.float(), self.running_mean, self.running_var,
                          None if self.weight is None else self.weight.float(),
                          None if self.bias is None else self.bias.float(),
-                         self.training, self.momentum if self.momentum is not None else 0.1, self.eps)
+                         self.training, bn_momentum(self), self.eps)
         if residual is not None:
             y = y + residual.float()
         if self.relu:

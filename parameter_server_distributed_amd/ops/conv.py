@@ -33,6 +33,8 @@ src/worker.cpp:316-329). This is worker-side compute for the BASELINE.json ResNe
 from __future__ import annotations
 
 
+import functools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -40,7 +42,8 @@ import torch.nn.functional as F
 from ..utils.config import feature as _feat
 from . import wprep as _wprep
 from . import autotune as _at
-from .bn import StridedDr, take_dr
+from .handover import (BwdPre, StatsPending, StridedDr, bn_momentum, fold_v as _fold_v, pop_dr, same, sinks, take,
+                       take_dr)
 
 
 def _enabled() -> bool:
@@ -136,28 +139,14 @@ def _q_weight(mod, w2: torch.Tensor):
 
 def _take_dq8(mod, dy: torch.Tensor):
     """The MX e5m2 copy of ``dy`` the consumer BN's backward pass wrote for this module (ops/bn.py
-    _dq8_args): (q [N, C, H, W] channels_last, uint8 scales), or None. Consumed once."""
-    pend = getattr(mod, "_psd_dq8_pending", None) if mod is not None else None
-    if pend is None:
-        return None
-    mod._psd_dq8_pending = None
-    d, q, sc = pend
-    if d.data_ptr() != dy.data_ptr() or d.shape != dy.shape or d.stride() != dy.stride():
-        return None
-    return q, sc
+    _dq8_args): a Q8Pending (q [N, C, H, W] channels_last, uint8 scales), or None. Consumed once."""
+    return take(mod, "_psd_dq8_pending", dy, strides=True)
 
 
 def _take_q8(mod, x: torch.Tensor):
-    """The MX e4m3 copy of ``x`` that the producing BN's apply pass wrote for this module (ops/bn.py),
-    as (q [N, C, H, W] channels_last, E8M0 scales uint8 [numel / 32]), or None. Consumed once."""
-    pend = getattr(mod, "_psd_q8_pending", None) if mod is not None else None
-    if pend is None:
-        return None
-    mod._psd_q8_pending = None
-    y, q, sinv = pend
-    if y.data_ptr() != x.data_ptr() or y.shape != x.shape or y.stride() != x.stride():
-        return None
-    return q, sinv
+    """The MX e4m3 copy of ``x`` that the producing BN's apply pass wrote for this module (ops/bn.py):
+    a Q8Pending (q [N, C, H, W] channels_last, E8M0 scales uint8 [numel / 32]), or None. Consumed once."""
+    return take(mod, "_psd_q8_pending", x, strides=True)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -218,6 +207,10 @@ def _get(w):
     return w() if isinstance(w, _Lazy) else w
 
 
+def _out_hw(h: int, w: int, k: int, stride: int, pad: int) -> tuple:
+    return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+
 def _convn_variants(x, w2, k: int, stride: int, pad: int, bn=None) -> dict:
     """{"psdn<v>": fn} over the kernel's tile variants; fn() -> the channels_last conv output. With a
     consumer ``bn`` every "psdn" call also reduces the BN's statistics partials in its epilogue and
@@ -226,7 +219,7 @@ def _convn_variants(x, w2, k: int, stride: int, pad: int, bn=None) -> dict:
     C = _native()
     n, _, h, w = x.shape
     cout = w2.shape[0]
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ho, wo = _out_hw(h, w, k, stride, pad)
     M = n * ho * wo
 
     def make(v, stats):
@@ -241,7 +234,7 @@ def _convn_variants(x, w2, k: int, stride: int, pad: int, bn=None) -> dict:
                 raise RuntimeError("convn_ declined a shape _psdn_ok accepted")
             y = _from_2d(out, n, ho, wo)
             if stats:
-                bn._psd_stats_pending = (y, part, rows)
+                bn._psd_stats_pending = StatsPending(y, part, rows)
             return y
         return fn
 
@@ -300,7 +293,7 @@ def _bn_bwd_fusion(bn, x: torch.Tensor):
     if st is None or not _feat("convn_bwd"):
         return None
     y, bx, mean, ss, mbits, xd, mean_d = st
-    if y.data_ptr() != x.data_ptr() or y.shape != x.shape or y.stride() != x.stride():
+    if not same(y, x, strides=True):
         return None
     if mbits is not None:
         if not bn._psd_pending_dr:
@@ -317,30 +310,43 @@ def _bn_bwd_fusion(bn, x: torch.Tensor):
     return dict(mode=1, bn=bn, bx=bx, mean=mean, ss=ss)
 
 
-def _convn_bwd_variants(dy, w2, k: int, pad: int, fu: dict, dr) -> dict:
+def _take_dr_for(fu) -> None:
+    """Take the residual gradient a residual BN's fusion (modes >= 2) folds in off the BN's queue, as
+    ``fu["dr"]`` (a non-fused choice puts it back: _dgrad_route)."""
+    if fu is not None:
+        fu["dr"] = fu["bn"]._psd_pending_dr.pop() if fu["mode"] >= 2 else None
+
+
+def _convn_bwd_launch(dy, w2, cout: int, k: int, pad: int, v: int, fu: dict, prows: int, declined: str,
+                      x2=None, bias=None) -> torch.Tensor:
+    """One stride-1 bwd-data launch on the narrow kernel (variant ``v``, ``prows`` partial rows) whose epilogue
+    runs the producing BN's backward reduction (``fu``); -> g, the masked gradient the BN's elementwise pass
+    takes, its partials handed to the BN (``_psd_bwd_pre``). ``x2`` / ``bias``: the folded form's operands."""
+    n, _, h, w = dy.shape
+    out = torch.empty(n * h * w, cout, device=dy.device, dtype=dy.dtype)
+    part = torch.empty(prows, 2, cout, device=dy.device, dtype=torch.float32)
+    part_d = torch.empty_like(part) if fu["mode"] == 3 else None
+    rows = _native().convn_bwd_(dy, w2, out, k, k, 1, pad, part, v, fu["mode"], fu["bx"], fu["mean"],
+                                bss=fu.get("ss"), bdr=_dr_arg(fu.get("dr")), bmbits=fu.get("mbits"), x2=x2,
+                                bias=bias, bxd=fu.get("bxd"), bmean_d=fu.get("mean_d"), part_d=part_d)
+    if rows == 0:
+        raise RuntimeError(declined)
+    g = _from_2d(out, n, h, w)
+    fu["bn"]._psd_bwd_pre = BwdPre(g, part, rows, part_d)
+    return g
+
+
+def _convn_bwd_variants(dy, w2, k: int, pad: int, fu: dict) -> dict:
     """{"psdnb<v>": fn}: stride-1 bwd-data on the narrow kernel whose epilogue runs the producing
-    BN's backward reduction; fn() -> g (the masked gradient the BN's elementwise pass takes), with
-    the partials handed to the BN (``_psd_bwd_pre``)."""
+    BN's backward reduction (_convn_bwd_launch)."""
     C = _native()
     n, _, h, w = dy.shape
     cout = w2.shape[0]
-    M = n * h * w
 
     def make(v):
-        def fn():
-            out = torch.empty(M, cout, device=dy.device, dtype=dy.dtype)
-            # (+ 1 row: a BN whose input was never stored completes its partials there, ops/tail.py)
-            part = torch.empty(_part_rows(M, cout, v, h, w, k) + 1, 2, cout, device=dy.device, dtype=torch.float32)
-            part_d = torch.empty_like(part) if fu["mode"] == 3 else None
-            rows = C.convn_bwd_(dy, _get(w2), out, k, k, 1, pad, part, v, fu["mode"], fu["bx"], fu["mean"],
-                                bss=fu.get("ss"), bdr=_dr_arg(dr), bmbits=fu.get("mbits"), bxd=fu.get("bxd"),
-                                bmean_d=fu.get("mean_d"), part_d=part_d)
-            if rows == 0:
-                raise RuntimeError("convn_bwd_ declined a shape _psdn_ok accepted")
-            g = _from_2d(out, n, h, w)
-            fu["bn"]._psd_bwd_pre = (g, part, rows) if part_d is None else (g, part, rows, part_d)
-            return g
-        return fn
+        # (+ 1 row: a BN whose input was never stored completes its partials there, ops/tail.py)
+        return lambda: _convn_bwd_launch(dy, _get(w2), cout, k, pad, v, fu, _part_rows(n * h * w, cout, v, h, w, k) + 1,
+                                         "convn_bwd_ declined a shape _psdn_ok accepted")
 
     return {f"psdnb{v}": make(v) for v in range(C.convn_variants(cout))
             if _variant_ok(cout, v, k, 1, pad, w, dy.shape[1], h)}
@@ -391,7 +397,7 @@ def _dgrad_s2_phases(dy, weight, x, fu, mod=None) -> dict:
                 raise RuntimeError("convn_dgrad_s2_ declined a shape it was offered for")
             g = _from_2d(out, n, h, w)
             if fused:
-                fu["bn"]._psd_bwd_pre = (g, part, rows)
+                fu["bn"]._psd_bwd_pre = BwdPre(g, part, rows)
             return g
         return fn
 
@@ -405,26 +411,30 @@ def _dgrad_s2_phases(dy, weight, x, fu, mod=None) -> dict:
     return cands
 
 
-def _dgrad_route(key: tuple, cands: dict, default: str, fu, dy_like) -> torch.Tensor:
+def _dgrad_route(key: tuple, cands: dict, default: str, fu, dy_like, timed=None, defer=None):
     """bwd-data: the fastest candidate; with a BN backward fusion available the library and
     unfused candidates are timed with the reduction pass they leave to the BN. A non-fused choice
-    returns the handed-over residual gradient to the BN's queue."""
+    returns the handed-over residual gradient to the BN's queue. ``timed``: what the autotuner times in
+    place of each candidate (the fold's dgrad + wgrad pairs); ``defer``: a candidate that is not run
+    here when it wins -- None comes back and the caller runs that path (the fold's "unfold")."""
+    timed = cands if timed is None else timed
     if fu is None:
-        return cands[_at.choose(key, cands, default)]()
+        how = _at.choose(key, timed, default)
+        return cands[how]() if how != defer else None
     if fu.get("bx") is None:
         # the BN's input was never stored (ops/tail.py): only the fused epilogue can reduce its backward
         cands = {name: fn for name, fn in cands.items() if name.startswith("psdnb")}
         if not cands:
             raise RuntimeError("psd: a BN without its stored input needs the fused bwd-data epilogue")
         key, default = key + ("nobx",), next(iter(cands))
-    timed = {name: (fn if name.startswith("psdnb") else _with_bn_bwd_reduce(fn, fu)) for name, fn in cands.items()}
+    timed = {n: (timed[n] if n.startswith("psdnb") else _with_bn_bwd_reduce(timed[n], fu)) for n in cands}
     # (the fused candidates return the BN-masked gradient g, the others dX: validated per family)
     how = _at.choose(key + ("bnbwd",), timed, default, group=lambda n: n.startswith("psdnb"))
-    out = cands[how]()
+    out = cands[how]() if how != defer else None
     if not how.startswith("psdnb"):
-        fu["bn"]._psd_bwd_pre = None
+        fu["bn"]._psd_bwd_pre = None  # (a timed fused candidate's hand-over)
         if fu.get("dr") is not None:
-            fu["bn"]._psd_pending_dr.append(fu["dr"])
+            fu["bn"]._psd_pending_dr.append(fu["dr"])  # the BN's own backward (or the caller's path) pops it again
     return out
 
 
@@ -462,7 +472,7 @@ def _stats_part(bn, M: int, cout: int, device):
 def _hand_stats(bn, y, part, rows: int):
     """Queue the partials a GEMM epilogue reduced for ``y`` on its consumer BN (skips its reduce)."""
     if part is not None and rows > 0:
-        bn._psd_stats_pending = (y, part, rows)
+        bn._psd_stats_pending = StatsPending(y, part, rows)
 
 
 def _dr_arg(dr):
@@ -546,9 +556,17 @@ def _sink_view(mod, weight):
     return sink(weight) if sink is not None else None
 
 
-def _fold_v() -> int:
-    """convw variant of the fold / Gram launches: 1 = the two-stage ring at two workgroups per CU."""
-    return 1 if _feat("convw_fold2") else 0
+def _write_dw(sv, fn, layout):
+    """The chosen weight-gradient candidate ``fn(into=None)`` into the PS sink view ``sv``: the kernel writes
+    the sink itself where it is contiguous in the kernel's ``layout`` ("ohwi": [Cout, k k Cin] rows of a
+    channels_last weight; "oi": [Cout, Cin] rows of a 1x1; None: never in place), else a fresh tensor copied
+    into it. Returns the sink (without one, the fresh tensor); None when the candidate returned None."""
+    if sv is not None and layout is not None:
+        t = sv.permute(0, 2, 3, 1) if layout == "ohwi" else sv
+        if t.is_contiguous():
+            return sv if fn(t.view(t.shape[0], -1)) is not None else None
+    dw = fn()
+    return sv.copy_(dw) if dw is not None and sv is not None else dw
 
 
 def fold_ok(cin: int, cout: int) -> bool:
@@ -559,19 +577,19 @@ def fold_ok(cin: int, cout: int) -> bool:
             and C.convw_fold_rows(cout, cin) > 0)
 
 
-def _fold_backward(ctx, fold, x, weight, need_x: bool, need_w: bool, P=None):
+def _fold_backward(ctx, fold, x, weight, need_x: bool, need_w: bool):
     """conv3's backward with its consumer BN's input gradient folded in (kernels/bnfold.hip): the BN
-    handed over g (the masked upstream gradient) and the coefficients of dy = A g + B y + C, where
-    y = conv(x) is the BN input. dgrad runs on the narrow kernel with the K-concatenated operand
-    [g | x] (and the producing BN's backward reduction in its epilogue where that wins); wgrad on
-    the narrow wgrad kernel's fold mode (g^T x, x^T x, 1^T x in one pass) + the combination. The
-    unfolded path -- the BN elementwise pass, then the ordinary dgrad -- is one of the timed
-    candidates (and the correctness reference); when it wins, (None, None, dy) is returned and the
+    handed over ``fold`` (a FoldPending): g (the masked upstream gradient) and the coefficients of
+    dy = A g + B y + C, where y = conv(x) is the BN input. dgrad runs on the narrow kernel with the
+    K-concatenated operand [g | x] (and the producing BN's backward reduction in its epilogue where
+    that wins); wgrad on the narrow wgrad kernel's fold mode (g^T x, x^T x, 1^T x in one pass) + the
+    combination. The unfolded path -- the BN elementwise pass, then the ordinary dgrad -- is one of the
+    timed candidates (and the correctness reference); when it wins, (None, None, dy) is returned and the
     caller runs the ordinary backward on dy. Returns (dx, dw, None) when folded.
 
-    y None (ops/tail.py: the BN input was never stored): only the folded candidates; ``P`` the fold
+    y None (ops/tail.py: the BN input was never stored): only the folded candidates; ``fold.P`` the fold
     wgrad products the caller already ran (its BN statistics needed g^T x), combined here."""
-    g, coef, y = fold
+    g, coef, y, P = fold
     C = _native()
     n, cin, h, w = x.shape
     cout = weight.shape[0]
@@ -584,117 +602,88 @@ def _fold_backward(ctx, fold, x, weight, need_x: bool, need_w: bool, P=None):
         return keep["dy"]
 
     dx = dw = None
-    how = "unfold"
     frows = C.convw_fold_rows(cout, cin)
     foldable = fold_ok(cin, cout) and x.is_contiguous(memory_format=torch.channels_last)
     if y is None and not foldable:
         raise RuntimeError("psd BN-backward fold without the BN input needs a foldable shape")
-    conv_bwd = torch.ops.aten.convolution_backward
-    wargs = (None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
 
-    def fold_wgrad(into):
+    def fold_wgrad(into=None):
+        o = into if into is not None else torch.empty(cout, cin, device=g.device, dtype=g.dtype)
         Pw = P
         if Pw is None:
             Pw = torch.empty(frows, cin, device=g.device, dtype=torch.float32)
             if not C.convw_(g, x, Pw, 1, 1, 1, 0, variant=_fold_v(), fold=True):
                 raise RuntimeError("convw_ declined a fold shape convw_fold_rows accepted")
-        C.bnfold_combine(Pw, weight, coef, into)
+        C.bnfold_combine(Pw, weight, coef, o)
+        return o.view(cout, cin, 1, 1)
 
     if need_x and foldable:
         w2, bvec = C.bnfold_dgrad_weights(weight, coef)
         wt = _wt(weight.reshape(cout, cin), ctx.mod, weight)
         fu = _bn_bwd_fusion(ctx.bn_in, x)
-        if fu is not None:
-            fu["dr"] = fu["bn"]._psd_pending_dr.pop() if fu["mode"] >= 2 else None
+        _take_dr_for(fu)
 
         # timed as dgrad + wgrad pairs: the unfolded path pays the BN elementwise pass and the plain
         # wgrad on it, the folded one the K-concatenated dgrad and the fold wgrad + combination
-        timing = {"on": True}
-
-        def unfold():
+        def unfold():  # (only ever timed: when it wins, the caller runs the ordinary backward)
             out = torch.empty(M, cin, device=g.device, dtype=g.dtype)
             keep.pop("dy", None)
             if not C.convn_(unfolded_dy(), wt(), out, 1, 1, 1, 0, variant=0):
                 raise RuntimeError("convn_ declined the unfolded dgrad")
-            if timing["on"] and need_w:
-                conv_bwd(keep["dy"], x, weight, *wargs, [False, True, False])
+            if need_w:
+                torch.ops.aten.convolution_backward(keep["dy"], x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0],
+                                                    1, [False, True, False])
             return _from_2d(out, n, h, w)
 
-        def make(v, fused):
-            def fn():
-                o = dgrad(v, fused)
-                if timing["on"] and need_w:
-                    fold_wgrad(torch.empty(cout, cin, device=g.device, dtype=g.dtype))
-                return o
-            return fn
-
         def dgrad(v, fused):
+            declined = "convn_ declined the folded dgrad"
+            if fused:
+                return _convn_bwd_launch(g, w2, cin, 1, 0, v, fu, C.convn_stats_rows(M), declined, x2=x, bias=bvec)
             out = torch.empty(M, cin, device=g.device, dtype=g.dtype)
-            part_d = None
-            if fused:
-                part = torch.empty(C.convn_stats_rows(M), 2, cin, device=g.device, dtype=torch.float32)
-                part_d = torch.empty_like(part) if fu["mode"] == 3 else None
-                rows = C.convn_bwd_(g, w2, out, 1, 1, 1, 0, part, v, fu["mode"], fu["bx"], fu["mean"],
-                                    bss=fu.get("ss"), bdr=_dr_arg(fu.get("dr")), bmbits=fu.get("mbits"), x2=x, bias=bvec,
-                                    bxd=fu.get("bxd"), bmean_d=fu.get("mean_d"), part_d=part_d)
-            else:
-                rows = C.convn_(g, w2, out, 1, 1, 1, 0, variant=v, x2=x, bias=bvec)
-            if rows == 0:
-                raise RuntimeError("convn_ declined the folded dgrad")
-            o = _from_2d(out, n, h, w)
-            if fused:
-                fu["bn"]._psd_bwd_pre = (o, part, rows) if part_d is None else (o, part, rows, part_d)
-            return o
+            if C.convn_(g, w2, out, 1, 1, 1, 0, variant=v, x2=x, bias=bvec) == 0:
+                raise RuntimeError(declined)
+            return _from_2d(out, n, h, w)
+
+        def with_wgrad(fn):
+            def pair():
+                o = fn()
+                if need_w:
+                    fold_wgrad()
+                return o
+            return pair
 
         cands = {"unfold": unfold} if y is not None else {}
         for v in range(C.convn_variants(cin)):
             if not C.convn_variant_ok(cin, v, 1, 1, 1, 0, w, True):
                 continue
-            cands[f"psdnf{v}"] = make(v, False)
+            cands[f"psdnf{v}"] = functools.partial(dgrad, v, False)
             if fu is not None:
-                cands[f"psdnb{v}"] = make(v, True)
+                cands[f"psdnb{v}"] = functools.partial(dgrad, v, True)
+        timed = {nm: (fn if nm == "unfold" else with_wgrad(fn)) for nm, fn in cands.items()}
         key = ("conv1x1", "dgrad_fold", M, cin, cout) + (() if y is not None else ("noy",))
-        if fu is not None and fu.get("bx") is None:
-            # the producing BN's input was never stored (a recomputing tail, ops/tail.py): only the
-            # fused epilogue can reduce its backward (as in _dgrad_route)
-            cands = {nm: fn for nm, fn in cands.items() if nm.startswith("psdnb")}
-            if not cands:
-                raise RuntimeError("psd: a BN without its stored input needs the fused folded bwd-data epilogue")
-            key = key + ("nobx",)
         default = "unfold" if "unfold" in cands else next(iter(cands))
-        if fu is None:
-            how = _at.choose(key, cands, default)
-        else:
-            timed = {nm: (fn if nm.startswith("psdnb") else _with_bn_bwd_reduce(fn, fu)) for nm, fn in cands.items()}
-            # (fused epilogues return the BN-masked gradient, the others dX: validated per family)
-            how = _at.choose(key + ("bnbwd",), timed, default, group=lambda nm: nm.startswith("psdnb"))
-        timing["on"] = False
-        if how != "unfold":
-            dx = cands[how]()
-            if not how.startswith("psdnb") and fu is not None:
-                fu["bn"]._psd_bwd_pre = None
-                if fu.get("dr") is not None:
-                    fu["bn"]._psd_pending_dr.append(fu["dr"])
-        elif fu is not None:
-            fu["bn"]._psd_bwd_pre = None  # (a timed fused candidate's hand-over)
-            if fu.get("dr") is not None:
-                fu["bn"]._psd_pending_dr.append(fu["dr"])  # the ordinary path pops it again
-    elif not need_x:
-        how = "fold" if foldable else "unfold"
-    if how == "unfold":
+        dx = _dgrad_route(key, cands, default, fu, x, timed=timed, defer="unfold")
+    if dx is None and (need_x or not foldable):
         return None, None, unfolded_dy()
     if need_w:
-        sv = _sink_view(ctx.mod, weight)
-        if sv is not None and sv.is_contiguous():
-            fold_wgrad(sv.view(cout, cin))
-            dw = sv
-        else:
-            o = torch.empty(cout, cin, device=g.device, dtype=g.dtype)
-            fold_wgrad(o)
-            dw = o.view(cout, cin, 1, 1)
-            if sv is not None:
-                dw = sv.copy_(dw)
+        dw = _write_dw(_sink_view(ctx.mod, weight), fold_wgrad, "oi")
     return dx, dw, None
+
+
+def _gemm1x1_cands(a2, w2, trans_b: bool, n: int, h: int, w: int, k: int, ncols: int, miopen=None) -> dict:
+    """A 1x1 convolution as the GEMM a2 [n h w, k] . w2 (transposed with ``trans_b``) -> channels_last
+    [n, ncols, h, w]: {"gemm": hipBLASLt[, "miopen": the caller's][, "psd": the persistent 8-phase MFMA
+    GEMM, kernels/gemm.hip, where it takes the shape]}."""
+    def gemm():
+        return _from_2d(torch.mm(a2, w2.t() if trans_b else w2), n, h, w)
+
+    def psd():
+        out = torch.empty(n * h * w, ncols, device=a2.device, dtype=a2.dtype)
+        _native().gemm_(a2, w2, True, trans_b, out)
+        return _from_2d(out, n, h, w)
+
+    cands = {"gemm": gemm, "miopen": miopen, "psd": psd if _psd_ok(k, ncols) else None}
+    return {name: fn for name, fn in cands.items() if fn is not None}
 
 
 class _Conv1x1Fn(torch.autograd.Function):
@@ -718,7 +707,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             # epilogue; the weight gradient runs on the saved bf16 x and W
             got = _take_q8(mod, x)
             if got is not None:  # quantised by the producing BN's apply pass
-                xq, sx = got[0].permute(0, 2, 3, 1).reshape(n * h * w, cin), got[1]
+                xq, sx = got.q.permute(0, 2, 3, 1).reshape(n * h * w, cin), got.scales
             else:
                 xq, sx = _q_act(x2, scaler=f8[0])
             wq, sw = _q_weight(mod, w2)
@@ -736,18 +725,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             return y
         key = ("fwd", n * h * w, cin, cout)
 
-        def gemm():
-            return _from_2d(torch.mm(x2, w2.t()), n, h, w)
-
-        def miopen():
-            return F.conv2d(x, weight)
-
-        def psd():  # the persistent 8-phase MFMA GEMM (kernels/gemm.hip)
-            out = torch.empty(n * h * w, cout, device=x.device, dtype=x.dtype)
-            _native().gemm_(x2, w2, True, True, out)
-            return _from_2d(out, n, h, w)
-
-        def psds():  # the same with the consumer BN's statistics in its epilogue
+        def psds():  # the MFMA GEMM with the consumer BN's statistics in its epilogue
             out = torch.empty(n * h * w, cout, device=x.device, dtype=x.dtype)
             part = _stats_part(bn, n * h * w, cout, x.device)
             rows = _native().gemm_(x2, w2, True, True, out, part=part, shift=bn.running_mean)
@@ -757,10 +735,9 @@ class _Conv1x1Fn(torch.autograd.Function):
             _hand_stats(bn, y, part, rows)
             return y
 
-        cands = {"gemm": gemm, "miopen": miopen}
+        cands = _gemm1x1_cands(x2, w2, True, n, h, w, cin, cout, miopen=lambda: F.conv2d(x, weight))
         bn = _bn_consumer(mod)
-        if _psd_ok(cin, cout):
-            cands["psd"] = psd
+        if "psd" in cands:
             if bn is not None and _feat("gemm_stats") and n * h * w >= 128 and cout >= 256 and cin >= 256 \
                     and cin % 64 == 0:
                 cands["psds"] = psds
@@ -779,13 +756,11 @@ class _Conv1x1Fn(torch.autograd.Function):
         cout = weight.shape[0]
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
-        fold = getattr(ctx.mod, "_psd_fold_pending", None) if ctx.mod is not None else None
+        fold = take(ctx.mod, "_psd_fold_pending", dy, strides=False,
+                    mismatch="psd BN-backward fold: the gradient reaching the convolution is not the one its BN "
+                             "handed over (its input gradient was never formed)")
         if fold is not None:
-            ctx.mod._psd_fold_pending = None
-            if fold[0].data_ptr() != dy.data_ptr() or fold[0].shape != dy.shape:
-                raise RuntimeError("psd BN-backward fold: the gradient reaching the convolution is not the one its BN "
-                                   "handed over (its input gradient was never formed)")
-            dx, dw, dy = _fold_backward(ctx, fold[:3], x, weight, need_x, need_w, P=fold[3] if len(fold) > 3 else None)
+            dx, dw, dy = _fold_backward(ctx, fold, x, weight, need_x, need_w)
             if dy is None:
                 return dx, dw, None, None
             need_x = need_x and dx is None  # unfolded: dy now holds the BN input gradient
@@ -798,7 +773,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             # fp8 bwd-data: e5m2 dY (K-major [M, cout]) x e4m3 W^T ([cin, cout], K-major)
             got = _take_dq8(ctx.mod, dy) if _mx_on() else None
             if got is not None:  # written by the consumer BN's backward pass
-                dyq, sdy = got[0].permute(0, 2, 3, 1).reshape(n * h * w, cout), got[1]
+                dyq, sdy = got.q.permute(0, 2, 3, 1).reshape(n * h * w, cout), got.scales
             else:
                 dyq, sdy = _q_act(_as_2d(dy), e5m2=True, scaler=ctx.f8[1])
             wtq, swt = _q_act(_wt(weight.reshape(cout, cin), ctx.mod, weight)())
@@ -812,28 +787,18 @@ class _Conv1x1Fn(torch.autograd.Function):
             dy2 = _as_2d(dy)
             key = ("dgrad", n * h * w, cin, cout)
 
-            def gemm():
-                return _from_2d(torch.mm(dy2, w2), n, h, w)
-
             def miopen():
                 return conv_bwd(dy, x, weight, *args, [True, False, False])[0]
 
-            def psd():
-                out = torch.empty(n * h * w, cin, device=dy.device, dtype=dy.dtype)
-                _native().gemm_(dy2, w2, True, False, out)
-                return _from_2d(out, n, h, w)
-
-            cands = {"gemm": gemm, "miopen": miopen}
-            if _psd_ok(cout, cin):
-                cands["psd"] = psd
+            cands = _gemm1x1_cands(dy2, w2, False, n, h, w, cout, cin, miopen)
             fu = None
             if _psdn_ok(cout, cin):  # dX = dY . W as a 1x1 convolution of dY with W^T [cin, cout]
                 wt = _wt(w2, ctx.mod, weight)
                 cands.update(_convn_variants(dy, wt, 1, 1, 0))
                 fu = _bn_bwd_fusion(ctx.bn_in, x)
                 if fu is not None:
-                    fu["dr"] = fu["bn"]._psd_pending_dr.pop() if fu["mode"] >= 2 else None
-                    cands.update(_convn_bwd_variants(dy, wt, 1, 0, fu, fu["dr"]))
+                    _take_dr_for(fu)
+                    cands.update(_convn_bwd_variants(dy, wt, 1, 0, fu))
             dx = _dgrad_route(("conv1x1",) + key, cands, "miopen", fu, x)
         if need_w:
             def miopen_w():
@@ -856,14 +821,7 @@ class _Conv1x1Fn(torch.autograd.Function):
                 _native().gemm_splitk_(_as_2d(dy), _as_2d(x), False, False, sv.view(cout, cin))
                 dw = sv
             elif how in wcands:  # narrow wgrad kernel: its slab reduce writes the PS buffer / dW directly
-                if sv is not None and sv.is_contiguous():
-                    dw = wcands[how](sv.view(cout, cin))
-                    if dw is not None:
-                        dw = sv
-                else:
-                    dw = wcands[how]()
-                    if dw is not None and sv is not None:
-                        dw = sv.copy_(dw)
+                dw = _write_dw(sv, wcands[how], "oi")
             if dw is None:
                 dw = cands[how]() if how not in wcands else miopen_w()
                 if sv is not None:
@@ -931,7 +889,7 @@ def _igemm(x: torch.Tensor, w2: torch.Tensor, k: int, stride: int, pad: int, bn=
     from .. import native
 
     n, _, h, w = x.shape
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ho, wo = _out_hw(h, w, k, stride, pad)
     out = torch.empty(n * ho * wo, w2.shape[0], device=x.device, dtype=x.dtype)
     part = _stats_part(bn, n * ho * wo, w2.shape[0], x.device)
     rows = native().conv_fwd_(x, w2, out, k, k, stride, pad, part=part,
@@ -951,9 +909,9 @@ def _igemm_fp8(x: torch.Tensor, w2: torch.Tensor, k: int, stride: int, pad: int,
     from .. import native
 
     n, c, h, w = x.shape
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-    if pre is not None:  # (q channels_last [N, C, H, W], scale_inv) from the producing BN
-        xq, sx = pre[0].permute(0, 2, 3, 1), pre[1]
+    ho, wo = _out_hw(h, w, k, stride, pad)
+    if pre is not None:  # a Q8Pending (q channels_last [N, C, H, W], its scales) from the producing BN
+        xq, sx = pre.q.permute(0, 2, 3, 1), pre.scales
     else:
         xq, sx = _q_act(x.permute(0, 2, 3, 1), e5m2=e5m2, scaler=scaler)  # the NHWC storage, in place order
     wq, sw = _q_weight(mod, w2) if mod is not None else _q_act(w2)
@@ -979,17 +937,7 @@ def _strided_dgrad(mod, dy, weight, to, H: int, W: int):
     w2 = weight.reshape(cout, cin)
     dy2 = _as_2d(dy)
 
-    def gemm():
-        return _from_2d(torch.mm(dy2, w2), n, ho, wo)
-
-    def psd():  # the persistent 8-phase MFMA GEMM (kernels/gemm.hip)
-        out = torch.empty(M4, cin, device=dy.device, dtype=dy.dtype)
-        _native().gemm_(dy2, w2, True, False, out)
-        return _from_2d(out, n, ho, wo)
-
-    cands = {"gemm": gemm}
-    if _psd_ok(cout, cin):
-        cands["psd"] = psd
+    cands = _gemm1x1_cands(dy2, w2, False, n, ho, wo, cout, cin)
     if _psdn_ok(cout, cin):
         cands.update(_convn_variants(dy, _wt(w2, mod, weight), 1, 1, 0))
     t4 = cands[_choose(("dgrad_s2", M4, cin, cout), cands)]()
@@ -1024,7 +972,7 @@ class _ConvFn(torch.autograd.Function):
         def miopen():
             return F.conv2d(x, weight, stride=stride, padding=pad)
 
-        ho_, wo_ = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        ho_, wo_ = _out_hw(h, w, k, stride, pad)
         if fp8 and cin % 128 == 0 and _fp8_ok(k * k * cin, cout) and n * ho_ * wo_ >= 128:  # (kernel contract)
             w2 = weight.permute(0, 2, 3, 1).reshape(cout, k * k * cin)
             y = _igemm_fp8(x, w2 if w2.is_contiguous() else w2.contiguous(), k, stride, pad, scaler=f8[0],
@@ -1114,8 +1062,8 @@ class _ConvFn(torch.autograd.Function):
                     cands.update(_convn_variants(dy, wf, k, 1, pad))
                     fu = _bn_bwd_fusion(ctx.bn_in, x)
                     if fu is not None:
-                        fu["dr"] = fu["bn"]._psd_pending_dr.pop() if fu["mode"] >= 2 else None
-                        cands.update(_convn_bwd_variants(dy, wf, k, pad, fu, fu["dr"]))
+                        _take_dr_for(fu)
+                        cands.update(_convn_bwd_variants(dy, wf, k, pad, fu))
                 key = ("dgrad", n, cin, h, w, cout, k, stride)
                 dx = _dgrad_route(("conv",) + key, cands, "miopen", fu, x)
             elif stride == 2 and k == 3 and pad == 1 and h == 2 * dy.shape[2] and w == 2 * dy.shape[3] \
@@ -1168,21 +1116,11 @@ class _ConvFn(torch.autograd.Function):
                 if dw is None:
                     raise RuntimeError(f"conv_wgrad_ declined {key} after it was chosen")
             elif how in wcands:
-                ohwi = sv.permute(0, 2, 3, 1) if sv is not None else None
-                if ohwi is not None and ohwi.is_contiguous():  # the sink itself, in the kernel's layout
-                    dw = wcands[how](ohwi.view(cout, -1))
-                    if dw is not None:
-                        dw = sv
-                else:
-                    dw = wcands[how]()
-                    if dw is not None and sv is not None:
-                        dw = sv.copy_(dw)
+                dw = _write_dw(sv, wcands[how], "ohwi")
                 if dw is None:
                     raise RuntimeError(f"convw_ {how} declined {key} after it was chosen")
             else:
-                dw = miopen_w()
-                if sv is not None:
-                    dw = sv.copy_(dw)
+                dw = _write_dw(sv, miopen_w, None)
         return dx, dw, None, None, None, None
 
 
@@ -1236,8 +1174,7 @@ class _StemFn(torch.autograd.Function):
         from .. import native
 
         y, arg, mean, invstd, ss, conv_out = native().stem_fwd(
-            x, w, bn_w, bn_b, bn.running_mean, bn.running_var, bn.momentum if bn.momentum is not None else 0.1, bn.eps,
-            bn.num_batches_tracked)
+            x, w, bn_w, bn_b, bn.running_mean, bn.running_var, bn_momentum(bn), bn.eps, bn.num_batches_tracked)
         ctx.bn, ctx.pool = bn, pool
         ctx.save_for_backward(x, w, conv_out, arg, bn_w, mean, invstd, ss)
         return y
@@ -1247,13 +1184,8 @@ class _StemFn(torch.autograd.Function):
         from .. import native
 
         x, w, conv_out, arg, bn_w, mean, invstd, ss = ctx.saved_tensors
-        sink = getattr(ctx.bn, "_psd_grad_sink", None)
-        dgo = dbo = None
-        if sink is not None:
-            dgo, dbo = sink(ctx.bn.weight), sink(ctx.bn.bias)
-        pend = getattr(ctx.pool, "_psd_pending_dr", None)
-        gy2 = pend.pop() if pend else None
-        dconv, dg, db = native().bn_pool_bwd(gy, gy2, arg, conv_out, bn_w, mean, invstd, ss, dgo, dbo)
+        dconv, dg, db = native().bn_pool_bwd(gy, pop_dr(ctx.pool), arg, conv_out, bn_w, mean, invstd, ss,
+                                             *sinks(ctx.bn))
         dw = native().stem_wgrad(x, dconv) if ctx.needs_input_grad[1] else None
         return None, dw, dg, db, None, None
 

@@ -8,6 +8,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import native
+from .handover import pop_dr
 
 
 class _MaxPoolFn(torch.autograd.Function):
@@ -24,9 +25,7 @@ class _MaxPoolFn(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         # second consumer's gradient of the pool output (handed over by the first bottleneck's
         # _Fork): summed inside the gather kernel instead of by an autograd add over the output
-        pend = getattr(ctx.mod, "_psd_pending_dr", None)
-        dy2 = pend.pop() if pend else None
-        return native().maxpool3s2_bwd(dy, arg, ctx.hw[0], ctx.hw[1], dy2), None
+        return native().maxpool3s2_bwd(dy, arg, ctx.hw[0], ctx.hw[1], pop_dr(ctx.mod)), None
 
 
 def _pool_kernel_ok(x: torch.Tensor) -> bool:

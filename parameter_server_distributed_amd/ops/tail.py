@@ -40,8 +40,10 @@ import torch
 from ..utils.config import feature as _feat
 from . import autotune as _at
 from .conv import (Conv1x1, ConvNHWC, _fold_backward, _fold_v, _from_2d, _fwd_records, _native, _part_rows, _sink_view,
-                   fold_ok)
-from .bn import FusedBatchNorm2d, StridedDr, take_dr
+                   _write_dw, fold_ok)
+from .bn import FusedBatchNorm2d
+from .handover import (BnFwd, FoldPending, StridedDr, bn_momentum, dual_from_fold, pop_dr, route_res_grad, sinks,
+                       take)
 
 __all__ = ["tail_ok", "conv_bn_tail", "dual_tail_ok", "conv_bn_dual_tail", "TAIL_CALLS"]
 
@@ -141,6 +143,12 @@ def _stats_route(a2, w2, M: int, cin: int, cout: int, v: int, h: int, w: int, sh
     return _at.choose(("tail", "stats", M, cin, cout), {"gram": gram, "pass": pas}, "pass")
 
 
+def _conv1x1_bwd(dy, x, weight, need_x: bool, need_w: bool):
+    """The library backward of a stride-1 1x1 convolution: (dx, dw, None)."""
+    return torch.ops.aten.convolution_backward(dy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                               [need_x, need_w, False])
+
+
 class _TailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a2, weight, gamma, beta, idt, conv, bn, resid_to):
@@ -167,8 +175,7 @@ class _TailFn(torch.autograd.Function):
             if rows == 0:
                 raise RuntimeError("psd tail: convn declined the statistics-only pass")
         mean, invstd, ss = C.bn_finalize(part, rows, M, gamma, beta, bn.running_mean, bn.running_var,
-                                         bn.momentum if bn.momentum is not None else 0.1, bn.eps,
-                                         bn.num_batches_tracked)
+                                         bn_momentum(bn), bn.eps, bn.num_batches_tracked)
         out = torch.empty(M, cout, device=a2.device, dtype=torch.bfloat16)
         mbits = torch.empty(M * cout // 8, device=a2.device, dtype=torch.uint8)
         if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=v, apply_ss=ss, apply_res=idt, apply_mask=mbits) == 0:
@@ -176,7 +183,7 @@ class _TailFn(torch.autograd.Function):
         y = _from_2d(out, n, h, w)
         # the consumer convolution's bwd-data epilogue runs this BN's backward reduction without its
         # input (bx None: ops/conv.py _bn_bwd_fusion / _dgrad_route)
-        bn._psd_fwd = (y, None, mean, ss, mbits, None, None)
+        bn._psd_fwd = BnFwd(y, None, mean, ss, mbits)
         ctx.mod = conv
         _fwd_records(ctx, conv)
         ctx.bn, ctx.resid_to, ctx.v = bn, resid_to, v
@@ -193,18 +200,12 @@ class _TailFn(torch.autograd.Function):
         n, cin, h, w = a2.shape
         cout = weight.shape[0]
         M = n * h * w
-        sink = getattr(bn, "_psd_grad_sink", None)
-        dgo = dbo = None
-        if sink is not None:
-            dgo, dbo = sink(bn.weight), sink(bn.bias)
-        pre = getattr(bn, "_psd_bwd_pre", None)
-        bn._psd_bwd_pre = None
-        if pre is not None and not (len(pre) == 3 and pre[0].data_ptr() == dy.data_ptr() and pre[0].shape == dy.shape):
-            pre = None
+        dgo, dbo = sinks(bn)
+        pre = take(bn, "_psd_bwd_pre", dy, strides=False)
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if pre is not None:
+        if pre is not None and pre.part_d is None:
             # g = mask (dX + dr) and its partials (sum g, -mean sum g) from the consumer's epilogue
-            g, part, rows = pre
+            g, part, rows = pre[:3]
             if part.shape[0] <= rows:
                 raise RuntimeError("psd tail: the partials buffer has no row for sum g y")
             P = torch.empty(C.convw_fold_rows(cout, cin), cin, device=dy.device, dtype=torch.float32)
@@ -223,23 +224,14 @@ class _TailFn(torch.autograd.Function):
             if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=ctx.v) == 0:
                 raise RuntimeError("psd tail: convn declined the recompute")
             y = _from_2d(out, n, h, w)
-            dy2 = take_dr(bn._psd_pending_dr.pop()) if getattr(bn, "_psd_pending_dr", None) else None
-            g, coef, dg, db = C.bn_bwd_coef(dy, y, gamma, mean, invstd, mbits=mbits, dy2=dy2, dgamma_out=dgo,
+            g, coef, dg, db = C.bn_bwd_coef(dy, y, gamma, mean, invstd, mbits=mbits, dy2=pop_dr(bn), dgamma_out=dgo,
                                             dbeta_out=dbo)
             TAIL_CALLS["bwd_recompute"] += 1
-        res_grad = None
-        if ctx.resid_to is not None:
-            ctx.resid_to._psd_pending_dr.append(g)
-        else:
-            res_grad = g
-        dx, dw, dyu = _fold_backward(ctx, (g, coef, y), a2, weight, need_x, need_w, P=P)
+        res_grad = route_res_grad(ctx.resid_to, g)
+        dx, dw, dyu = _fold_backward(ctx, FoldPending(g, coef, y, P), a2, weight, need_x, need_w)
         if dyu is not None:  # (y present and the unfolded path won): the ordinary conv backward on dy
-            conv_bwd = torch.ops.aten.convolution_backward
-            args = (None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
-            dx, dw, _ = conv_bwd(dyu, a2, weight, *args, [need_x, need_w, False])
-            sv = _sink_view(ctx.mod, weight)
-            if dw is not None and sv is not None:
-                dw = sv.copy_(dw)
+            dx, dw, _ = _conv1x1_bwd(dyu, a2, weight, need_x, need_w)
+            dw = _write_dw(_sink_view(ctx.mod, weight), lambda: dw, None)
         return dx, dw, dg, db, res_grad, None, None, None
 
 
@@ -336,8 +328,8 @@ def _gram_moments(x, w2, shift, M: int) -> torch.Tensor:
 
 
 def _finalize(bn, part, M: int):
-    return _native().bn_finalize(part, 1, M, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                 bn.momentum if bn.momentum is not None else 0.1, bn.eps, bn.num_batches_tracked)
+    return _native().bn_finalize(part, 1, M, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn_momentum(bn),
+                                 bn.eps, bn.num_batches_tracked)
 
 
 def dual_weights_reference(w3_2, wd_2, ss3, ss_d):
@@ -394,7 +386,7 @@ class _DualTailFn(torch.autograd.Function):
         y = _from_2d(out, n, h, w)
         # the consumer convolution's bwd-data epilogue reduces bn3's backward without its input
         # (mode 2, bx None: sum g and -mean3 sum g); backward completes both BNs from the fold products
-        bn3._psd_fwd = (y, None, mean3, None, mbits, None, None)
+        bn3._psd_fwd = BnFwd(y, None, mean3, None, mbits)
         ctx.r3, ctx.rd = types.SimpleNamespace(mod=conv3), types.SimpleNamespace(mod=convd)
         _fwd_records(ctx.r3, conv3)
         _fwd_records(ctx.rd, convd)
@@ -409,40 +401,18 @@ class _DualTailFn(torch.autograd.Function):
         C = _native()
         bn3, bnd = ctx.bn3, ctx.bnd
         bn3._psd_fwd = None
-
-        def sinks(m):
-            sink = getattr(m, "_psd_grad_sink", None)
-            return (sink(m.weight), sink(m.bias)) if sink is not None else (None, None)
-
-        dg3o, db3o = sinks(bn3)
-        dgdo, dbdo = sinks(bnd)
+        (dg3o, db3o), (dgdo, dbdo) = sinks(bn3), sinks(bnd)
         n, c3, h, w = a2.shape
         cd, cout = xin.shape[1], w3.shape[0]
         M = n * h * w
-        pre = getattr(bn3, "_psd_bwd_pre", None)
-        bn3._psd_bwd_pre = None
-        if pre is not None and not (len(pre) == 3 and pre[0].data_ptr() == dy.data_ptr() and pre[0].shape == dy.shape):
-            pre = None
+        pre = take(bn3, "_psd_bwd_pre", dy, strides=False)
         need = ctx.needs_input_grad
-        if pre is not None:
-            g, part, rows = pre
-            if part.shape[0] <= rows:
-                raise RuntimeError("psd dual tail: the partials buffer has no row for sum g y")
-            Ps = []
-            for inp, cin in ((a2, c3), (xin, cd)):
-                P = torch.empty(C.convw_fold_rows(cout, cin), cin, device=g.device, dtype=torch.float32)
-                if not C.convw_(g, inp, P, 1, 1, 1, 0, variant=_fold_v(), fold=True):
-                    raise RuntimeError("psd dual tail: convw_ declined the fold wgrad")
-                Ps.append(P)
-            # the downsample BN's sums derive from bn3's sum g (same masked g) and its own sum g yd
-            part_d = torch.empty(2, part.shape[-1], device=part.device, dtype=torch.float32)
-            C.bnfold_rowdot(Ps[0], w3, part[rows])
-            C.bnfold_rowdot(Ps[1], wd, part_d)
-            _, _, dg3, db3, dgd, dbd, coef, coef_d = C.bn_bwd_dual_pre(
-                g, g, g3, mean3, invstd3, part, part_d, rows + 1, g, gd, mean_d, invstd_d, dg3o, db3o, dgdo, dbdo,
-                fold=True, fold_d=True, derive_d=True)
-            dxa, dw3, _ = _fold_backward(ctx.r3, (g, coef, None), a2, w3, need[0], need[1], P=Ps[0])
-            dxi, dwd, _ = _fold_backward(ctx.rd, (g, coef_d, None), xin, wd, need[4], need[5], P=Ps[1])
+        if pre is not None and pre.part_d is None:
+            g = pre.g  # (neither BN input was stored: g stands in for both)
+            Ps, dg3, db3, dgd, dbd, coef, coef_d = dual_from_fold(
+                pre, w3, a2, wd, xin, g, g3, mean3, invstd3, g, gd, mean_d, invstd_d, (dg3o, db3o), (dgdo, dbdo))
+            dxa, dw3, _ = _fold_backward(ctx.r3, FoldPending(g, coef, None, Ps[0]), a2, w3, need[0], need[1])
+            dxi, dwd, _ = _fold_backward(ctx.rd, FoldPending(g, coef_d, None, Ps[1]), xin, wd, need[4], need[5])
             TAIL_CALLS["dual_bwd_fused"] += 1
             return dxa, dw3, dg3, db3, _DualTailFn._input_grad(ctx, dxi), dwd, dgd, dbd, None, None, None, None
         # no fused consumer: recompute y3 and yd once, the ordinary dual BN backward (one reduce and
@@ -453,18 +423,12 @@ class _DualTailFn(torch.autograd.Function):
             if C.convn_(inp, wt.reshape(cout, cin).contiguous(), o, 1, 1, 1, 0, variant=0) == 0:
                 raise RuntimeError("psd dual tail: convn declined the recompute")
             ys.append(_from_2d(o, n, h, w))
-        dy2 = take_dr(bn3._psd_pending_dr.pop()) if getattr(bn3, "_psd_pending_dr", None) else None
-        dx3, dxd, dg3, db3, dgd, dbd = C.bn_bwd_dual(dy, ys[0], g3, mean3, invstd3, mbits, dy2, ys[1], gd, mean_d,
-                                                     invstd_d, dg3o, db3o, dgdo, dbdo)
-        conv_bwd = torch.ops.aten.convolution_backward
-        args = (None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
-        dxa, dw3, _ = conv_bwd(dx3, a2, w3, *args, [need[0], need[1], False])
-        dxi, dwd, _ = conv_bwd(dxd, xin, wd, *args, [need[4], need[5], False])
-        sv3, svd = _sink_view(ctx.r3.mod, w3), _sink_view(ctx.rd.mod, wd)
-        if dw3 is not None and sv3 is not None:
-            dw3 = sv3.copy_(dw3)
-        if dwd is not None and svd is not None:
-            dwd = svd.copy_(dwd)
+        dx3, dxd, dg3, db3, dgd, dbd = C.bn_bwd_dual(dy, ys[0], g3, mean3, invstd3, mbits, pop_dr(bn3), ys[1], gd,
+                                                     mean_d, invstd_d, dg3o, db3o, dgdo, dbdo)
+        dxa, dw3, _ = _conv1x1_bwd(dx3, a2, w3, need[0], need[1])
+        dxi, dwd, _ = _conv1x1_bwd(dxd, xin, wd, need[4], need[5])
+        dw3 = _write_dw(_sink_view(ctx.r3.mod, w3), lambda: dw3, None)
+        dwd = _write_dw(_sink_view(ctx.rd.mod, wd), lambda: dwd, None)
         TAIL_CALLS["dual_bwd_recompute"] += 1
         return dxa, dw3, dg3, db3, _DualTailFn._input_grad(ctx, dxi), dwd, dgd, dbd, None, None, None, None
 
