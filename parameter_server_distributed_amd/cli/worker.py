@@ -63,8 +63,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="elastic: lock-step RCCL plane, or the asynchronous peer-memory plane (K-batch rounds, SSP "
                          "bound --staleness; one node)")
     ap.add_argument("--fp8-compute", action="store_true",
-                    help="fp8 (e4m3 MFMA) forward / e5m2 bwd-data of the ResNet bottleneck convolutions "
-                         "(BASELINE config 5: Wide-ResNet-101-2 fp8)")
+                    help="fp8 (MX e4m3 MFMA) forward / e5m2 bwd-data of the ResNet bottleneck convolutions "
+                         "(BASELINE config 5: Wide-ResNet-101-2 fp8) and of the encoder / decoder Linear layers "
+                         "(qkv, proj, ffn1, ffn2) of bert_base and gpt_small; weight gradients stay bf16")
     ap.add_argument("--image-size", type=int, default=224, help="ResNet models: synthetic image size")
     return ap
 
@@ -118,12 +119,15 @@ def main(argv=None):
 
 
 def build_model(a, dev, dtype):
-    """The worker's model from the CLI flags (``--fp8-compute``: fp8 bottleneck convolutions)."""
+    """The worker's model from the CLI flags (``--fp8-compute``: fp8 bottleneck convolutions / fp8
+    transformer Linear layers)."""
     from .. import models
 
     kw = {}
     if a.model.lower().replace("-", "_") in ("resnet50", "resnet101", "wide_resnet101_2", "wrn101"):
         kw = dict(fp8=bool(a.fp8_compute), image_size=a.image_size)
+    elif a.model.lower().replace("-", "_") in ("bert_base", "bert", "gpt_small", "gpt"):
+        kw = dict(fp8=bool(a.fp8_compute))
     return models.build(a.model, dev, dtype, **kw)
 
 

@@ -67,6 +67,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("dequant_fp8_", &dequant_fp8_);
   m.def("quant_mx_", &quant_mx_, py::arg("x"), py::arg("out"), py::arg("scales"));
   m.def("dequant_mx_", &dequant_mx_, py::arg("q"), py::arg("scales"), py::arg("out"));
+  m.def("quant_mx_t_", &quant_mx_t_, py::arg("x"), py::arg("out"), py::arg("scales"));
   m.def("quant_fp8_jit_", &quant_fp8_jit_, py::arg("x"), py::arg("out"), py::arg("scale_inv"));
   m.def("quant_fp8_delayed_", &quant_fp8_delayed_, py::arg("x"), py::arg("out"), py::arg("scale_inv"),
         py::arg("hist"), py::arg("margin") = 1.0);
@@ -177,7 +178,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
         py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false);
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
-        py::arg("seed"), py::arg("step") = py::none());
+        py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
+        py::arg("sc8_out") = py::none());
   m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("s"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("dgamma_out") = py::none(),
         py::arg("dbeta_out") = py::none(), py::arg("dhsum_out") = py::none());

@@ -436,8 +436,10 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
     }
     if (a.bpart) {  // the item's column sums in a fixed order over the blocks -> bpart[b][t * HD + h * 64 + d]
       __syncthreads();
-      if ((int)threadIdx.x < 3 * 64) {
-        const int t = threadIdx.x >> 6, d = threadIdx.x & 63;
+      // 3 * 64 sums; at S = 32 the workgroup has 128 threads, which take a second one each (the V sums
+      // were left unwritten there before: an uninitialised third of the QKV bias gradient)
+      for (int c = threadIdx.x; c < 3 * 64; c += NT) {
+        const int t = c >> 6, d = c & 63;
         float acc = 0.f;
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) acc += cs_s[(ww * 3 + t) * 64 + d];

@@ -139,5 +139,9 @@ hipError_t launch_quant_mx(const void* x, int32_t dtype, int64_t n, int e5m2, ui
                            hipStream_t stream);
 hipError_t launch_dequant_mx(const uint8_t* q, const uint8_t* scales, int64_t n, void* out, int32_t out_dtype,
                              hipStream_t stream);
+// the MX copy of x^T from x [R, C] bf16 in one pass (kernels/fp8_t.hip): q [C, R], scales [C, R/32],
+// blocks along R (R % 32 == 0, C % 8 == 0); bitwise launch_quant_mx of the transposed copy
+hipError_t launch_quant_mx_t(const void* x, int64_t R, int64_t C, int e5m2, uint8_t* q, uint8_t* scales,
+                             hipStream_t stream);
 
 }  // namespace psd

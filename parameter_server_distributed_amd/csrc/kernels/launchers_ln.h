@@ -11,6 +11,8 @@ struct LnArgs {
   const uint16_t* beta;   // [H] bf16
   uint16_t* y;            // fwd out [rows, H]
   uint16_t* s;            // fwd out / bwd in: x + dropout(h), the LN input, bf16
+  uint8_t* q8;            // fwd out or null: MX e4m3 copy of y [rows, H] (both or neither of q8 / sc8)
+  uint8_t* sc8;           // fwd out or null: its E8M0 scales [rows, H/32]
   float* mean;            // [rows]
   float* rstd;            // [rows]
   const uint16_t* dy;     // bwd in

@@ -18,6 +18,7 @@
 // [blk][2][H] -> deterministic finalize (fixed order).
 #include "common.h"
 #include "launchers_ln.h"
+#include "mx_common.h"
 
 namespace psd {
 
@@ -68,14 +69,19 @@ __device__ __forceinline__ uint32_t dropout_key(uint32_t seed, const int64_t* st
 
 }  // namespace
 
-template <int E>
+// MX: also the MX e4m3 copy of y for the consumer Linear's fp8 GEMM (ops/linear.py fp8="mx"): payload
+// q8 [rows, H] and one E8M0 byte per 32 columns sc8 [rows, H/32], quantised from the bf16-rounded values
+// y stores -- bitwise quant_mx_kernel (fp8.hip) of y. A lane's E columns are E/4 chunks of 4 that each
+// lie in one 32-column block; GL lanes cover NB whole blocks (E = 12: 8 lanes, 3 blocks; E = 16:
+// 2 lanes, 1 block), so a block's amax is log2(GL) xor-exchanges of NB per-lane partial maxima.
+template <int E, bool MX>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ h,
                                                      const uint16_t* __restrict__ gamma,
                                                      const uint16_t* __restrict__ beta, uint16_t* __restrict__ y,
                                                      uint16_t* __restrict__ s_out, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, int64_t rows, float eps,
                                                      uint32_t seed, const int64_t* __restrict__ step, uint32_t thresh,
-                                                     float scale) {
+                                                     float scale, uint8_t* __restrict__ q8, uint8_t* __restrict__ sc8) {
   constexpr int H = 64 * E;
   const int lane = threadIdx.x & 63;
   const int c0 = lane * E;
@@ -126,6 +132,47 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const uint16_t* __restrict_
 #pragma unroll
     for (int i = 0; i < E; ++i) hv[i] = fmaf((xv[i] - mean) * rstd, g[i], b[i]);
     store_e<E>(y + off, hv);
+    if constexpr (MX) {
+      static_assert(E == 12 || E == 16, "MX block map written for H = 768 / 1024");
+      constexpr int NC = E / 4, GL = (E == 12) ? 8 : 2, NB = (E == 12) ? 3 : 1;
+      const int g0 = (lane & (GL - 1)) * E;  // first column of this lane inside its lane group's NB blocks
+      float bm[NB];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) bm[k] = 0.f;
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        float cm = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          hv[4 * j + e] = bf16_to_f32(f32_to_bf16(hv[4 * j + e]));  // as stored
+          cm = fmaxf(cm, fabsf(hv[4 * j + e]));
+        }
+        const int kb = (g0 + 4 * j) >> 5;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) bm[k] = (kb == k) ? fmaxf(bm[k], cm) : bm[k];
+      }
+#pragma unroll
+      for (int o = 1; o < GL; o <<= 1)
+#pragma unroll
+        for (int k = 0; k < NB; ++k) bm[k] = fmaxf(bm[k], __shfl_xor(bm[k], o));
+      uint8_t* qrow = q8 + off;                          // 4-byte aligned: c0 = lane * E, E % 4 == 0
+      uint8_t* srow = sc8 + r * (H / 32) + (c0 >> 5);
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const int kb = (g0 + 4 * j) >> 5;
+        float am = bm[0];
+#pragma unroll
+        for (int k = 1; k < NB; ++k) am = (kb == k) ? bm[k] : am;
+        const int eb = mx_exp_byte(am, 448.f);
+        const float inv = __uint_as_float((uint32_t)(254 - eb) << 23);  // 2^(127 - eb), as mx_quant8
+        uint32_t w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w |= (uint32_t)f32_to_e4m3(hv[4 * j + e] * inv) << (8 * e);
+        *reinterpret_cast<uint32_t*>(qrow + 4 * j) = w;
+        // the lane holding a block's first chunk writes its scale byte
+        if (((c0 + 4 * j) & 31) == 0) srow[((c0 & 31) + 4 * j) >> 5] = (uint8_t)eb;
+      }
+    }
     if (lane == 0) {
       mean_out[r] = mean;
       rstd_out[r] = rstd;
@@ -466,11 +513,17 @@ hipError_t launch_ln_fwd(const LnArgs& a, hipStream_t st) {
   const int blocks = (int)(blocks64 > 2048 ? 2048 : (blocks64 < 1 ? 1 : blocks64));
   const uint32_t th = keep_thresh(a.p);
   const float sc = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
-#define PSD_LNF(E)                                                                                                  \
-  hipLaunchKernelGGL(ln_fwd_kernel<E>, dim3(blocks), dim3(256), 0, st, a.x, a.h, a.gamma, a.beta, a.y, a.s, a.mean, \
-                     a.rstd, a.rows, a.eps, a.seed, a.step, th, sc)
-  if (a.H == 768) PSD_LNF(12);
-  else PSD_LNF(16);
+  if ((a.q8 == nullptr) != (a.sc8 == nullptr)) return hipErrorInvalidValue;
+#define PSD_LNF(E, MX)                                                                                              \
+  hipLaunchKernelGGL((ln_fwd_kernel<E, MX>), dim3(blocks), dim3(256), 0, st, a.x, a.h, a.gamma, a.beta, a.y, a.s, \
+                     a.mean, a.rstd, a.rows, a.eps, a.seed, a.step, th, sc, a.q8, a.sc8)
+  if (a.q8 != nullptr) {
+    if (a.H == 768) PSD_LNF(12, true);
+    else PSD_LNF(16, true);
+  } else {
+    if (a.H == 768) PSD_LNF(12, false);
+    else PSD_LNF(16, false);
+  }
 #undef PSD_LNF
   return hipGetLastError();
 }

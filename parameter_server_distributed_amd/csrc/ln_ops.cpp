@@ -19,7 +19,8 @@ void check_bf16(const at::Tensor& t, const char* what) {
 }  // namespace
 
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
-                               double eps, double p, int64_t seed, c10::optional<at::Tensor> step) {
+                               double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
+                               c10::optional<at::Tensor> q8_out, c10::optional<at::Tensor> sc8_out) {
   check_bf16(x, "x");
   check_bf16(h, "h");
   check_bf16(gamma, "gamma");
@@ -29,6 +30,17 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
               "psd ln fwd: shapes (H must be 768 or 1024)");
   const c10::DeviceGuard g(x.device());
   const int64_t rows = x.numel() / H;
+  // the MX e4m3 copy of y for the consumer Linear (both outputs or neither)
+  const bool mx = given(q8_out);
+  TORCH_CHECK(mx == given(sc8_out), "psd ln fwd: the MX payload and scales come together");
+  if (mx) {
+    TORCH_CHECK(q8_out->scalar_type() == at::kFloat8_e4m3fn && q8_out->is_contiguous() && q8_out->numel() == x.numel() &&
+                    q8_out->device() == x.device() && (reinterpret_cast<uintptr_t>(q8_out->data_ptr()) & 3u) == 0,
+                "psd ln fwd: q8 must be a contiguous float8_e4m3fn tensor like x");
+    TORCH_CHECK(sc8_out->scalar_type() == at::kByte && sc8_out->is_contiguous() && sc8_out->numel() == x.numel() / 32 &&
+                    sc8_out->device() == x.device(),
+                "psd ln fwd: sc8 must be uint8 [rows, H / 32]");
+  }
   at::Tensor y = at::empty_like(x), s = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   at::Tensor mean = at::empty({rows}, f32), rstd = at::empty({rows}, f32);
@@ -39,6 +51,8 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
   a.beta = cu16(beta);
   a.y = u16(y);
   a.s = u16(s);
+  a.q8 = mx ? reinterpret_cast<uint8_t*>(q8_out->data_ptr()) : nullptr;
+  a.sc8 = mx ? sc8_out->data_ptr<uint8_t>() : nullptr;
   a.mean = mean.data_ptr<float>();
   a.rstd = rstd.data_ptr<float>();
   a.step = given(step) ? step->data_ptr<int64_t>() : nullptr;

@@ -812,6 +812,28 @@ void quant_mx_(const at::Tensor& x, at::Tensor out, at::Tensor scales) {
             "quant_mx");
 }
 
+// MX fp8 of x^T in one pass: x [R, C] bf16 -> out [C, R], scales [C, R/32] (blocks along R)
+void quant_mx_t_(const at::Tensor& x, at::Tensor out, at::Tensor scales) {
+  const bool e5 = out.scalar_type() == at::kFloat8_e5m2;
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() && x.scalar_type() == at::kBFloat16 &&
+                  x.size(0) % 32 == 0 && x.size(1) % 8 == 0,
+              "psd: quant_mx_t input must be a contiguous bf16 [R, C] device tensor with R % 32 == 0 and C % 8 == 0");
+  const int64_t R = x.size(0), C = x.size(1);
+  TORCH_CHECK((out.scalar_type() == at::kFloat8_e4m3fn || e5) && out.dim() == 2 && out.size(0) == C &&
+                  out.size(1) == R && out.is_contiguous() && out.device() == x.device(),
+              "psd: quant_mx_t out must be a contiguous float8_e4m3fn or float8_e5m2 [C, R] tensor on x's device");
+  TORCH_CHECK(scales.scalar_type() == at::kByte && scales.is_contiguous() && scales.numel() == x.numel() / 32 &&
+                  scales.device() == x.device(),
+              "psd: quant_mx_t scales must be uint8 [C, R / 32] on x's device");
+  const c10::DeviceGuard g(x.device());
+  if (x.numel() == 0) return;
+  check_aligned(x, "x");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 15u) == 0, "psd: fp8 out must be 16-byte aligned");
+  hip_check(launch_quant_mx_t(x.data_ptr(), R, C, e5 ? 1 : 0, reinterpret_cast<uint8_t*>(out.data_ptr()),
+                              scales.data_ptr<uint8_t>(), stream_of(x)),
+            "quant_mx_t");
+}
+
 void dequant_mx_(const at::Tensor& q, const at::Tensor& scales, at::Tensor out) {
   TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.is_contiguous() && q.is_cuda() && out.numel() == q.numel() &&
                   out.is_contiguous() && q.numel() % 32 == 0,

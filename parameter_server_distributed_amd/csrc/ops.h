@@ -64,6 +64,9 @@ void quant_fp8_delayed_(const at::Tensor& x, at::Tensor out, at::Tensor scale_in
 void dequant_fp8_(const at::Tensor& x, const at::Tensor& scale_inv, at::Tensor out);
 void quant_mx_(const at::Tensor& x, at::Tensor out, at::Tensor scales);
 void dequant_mx_(const at::Tensor& q, const at::Tensor& scales, at::Tensor out);
+// x [R, C] bf16 -> the MX copy of x^T: out [C, R] (e4m3fn / e5m2), scales [C, R/32]; bitwise
+// quant_mx_ of x.t().contiguous(), one launch and one read of x (kernels/fp8_t.hip)
+void quant_mx_t_(const at::Tensor& x, at::Tensor out, at::Tensor scales);
 
 std::vector<at::Tensor> bn_fwd(const at::Tensor& x, c10::optional<at::Tensor> gamma, c10::optional<at::Tensor> beta,
                                c10::optional<at::Tensor> running_mean, c10::optional<at::Tensor> running_var,
@@ -198,7 +201,9 @@ at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Ten
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
                     bool causal);
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
-                               double eps, double p, int64_t seed, c10::optional<at::Tensor> step);
+                               double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
+                               c10::optional<at::Tensor> q8_out = c10::nullopt,
+                               c10::optional<at::Tensor> sc8_out = c10::nullopt);
 std::vector<at::Tensor> ln_bwd(const at::Tensor& dy, const at::Tensor& s, const at::Tensor& mean, const at::Tensor& rstd,
                                const at::Tensor& gamma, double p, int64_t seed, c10::optional<at::Tensor> step,
                                c10::optional<at::Tensor> dgamma_out, c10::optional<at::Tensor> dbeta_out,

@@ -85,8 +85,8 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
     if name in ("bert_base", "bert"):
         from .bert import BertForMLM, bert_batch
 
-        m = prepare(BertForMLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")}),
-                    device, dtype)
+        m = prepare(BertForMLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
+                               fp8=bool(kw.get("fp8", False))), device, dtype)
         seq = kw.get("seq_len", 128)
         min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
 
@@ -99,7 +99,7 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
 
         seq = kw.get("seq_len", 512)
         m = prepare(GPTForLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
-                             max_pos=max(512, seq)), device, dtype)
+                             max_pos=max(512, seq), fp8=bool(kw.get("fp8", False))), device, dtype)
         min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
 
         def make(batch, device, seed=0):

@@ -24,21 +24,28 @@ VOCAB = 30528
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False):
+    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False, fp8=False):
         super().__init__()
         self.heads = heads
-        self.qkv = MfmaLinear(hidden, 3 * hidden)
+        # fp8: the four Linears run the MX fp8 recipe of ops/linear.py (fp8 forward and bwd-data, bf16
+        # weight gradient); each LayerNorm writes the MX input of the Linear that reads its output
+        # (ln1 -> ffn1 here, ln2 -> the next layer's qkv: wire_fp8_handover)
+        f8 = "mx" if fp8 else False
+        self.fp8 = bool(fp8)
+        self.qkv = MfmaLinear(hidden, 3 * hidden, fp8=f8)
         # packed QKV in, [B, S, hidden] out: one fused kernel per direction (ops/attention.py)
         self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=causal)
-        self.proj = MfmaLinear(hidden, hidden)
+        self.proj = MfmaLinear(hidden, hidden, fp8=f8)
         # LayerNorm(x + dropout(branch)) as one fused kernel family (ops/layernorm.py)
         self.ln1 = FusedAddLayerNorm(hidden, eps=1e-12, p=dropout, seed=2 * index + 1)
-        self.ffn1 = MfmaLinear(hidden, ffn, act="gelu")
-        self.ffn2 = MfmaLinear(ffn, hidden)
+        self.ffn1 = MfmaLinear(hidden, ffn, act="gelu", fp8=f8)
+        self.ffn2 = MfmaLinear(ffn, hidden, fp8=f8)
         # ffn1's output feeds only ffn2: ffn2's bwd-data GEMM applies the GELU backward and sums
         # ffn1's bias gradient in its epilogue (ops/linear.py)
         self.ffn2.psd_gelu_input_from(self.ffn1)
         self.ln2 = FusedAddLayerNorm(hidden, eps=1e-12, p=dropout, seed=2 * index + 2)
+        if fp8:
+            self.ln1.psd_mx_output_to(self.ffn1)
         self.p = dropout
 
     def forward(self, x, lens=None):
@@ -48,14 +55,25 @@ class BertLayer(nn.Module):
         return self.ln2(x, self.ffn2(self.ffn1(x)), x_grad_to=self.ffn1)
 
 
+def wire_fp8_handover(layers) -> None:
+    """ln2 of each fp8 block writes the MX input of the next block's qkv (the last block's ln2 feeds a
+    bf16 head: no hand-over)."""
+    for prev, nxt in zip(layers, list(layers)[1:]):
+        if prev.fp8 and nxt.fp8:
+            prev.ln2.psd_mx_output_to(nxt.qkv)
+
+
 class BertForMLM(nn.Module):
-    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1):
+    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False):
         super().__init__()
         self.vocab = vocab
         # dropout(LayerNorm(word + position + token type)) on one fused kernel each way, with the
         # word table's deterministic sorted-scatter gradient (ops/embedding.py)
         self.emb = FusedBertEmbeddings(vocab, hidden, max_pos, 2, eps=1e-12, p=dropout, seed=4242)
-        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i) for i in range(layers)])
+        # fp8: MX fp8 qkv / proj / ffn1 / ffn2 in every layer; the MLM head, the decoder and the
+        # embeddings stay bf16
+        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, fp8=fp8) for i in range(layers)])
+        wire_fp8_handover(self.layers)
         self.head = MfmaLinear(hidden, hidden, act="gelu")
         self.head_ln = nn.LayerNorm(hidden, eps=1e-12)
         self.decoder = MfmaLinear(hidden, vocab)

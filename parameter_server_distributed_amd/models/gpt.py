@@ -20,17 +20,20 @@ from ..ops.embedding import FusedBertEmbeddings
 from ..ops.layernorm import bump_step
 from ..ops.linear import MfmaLinear
 from ..ops.loss import cross_entropy
-from .bert import BertLayer
+from .bert import BertLayer, wire_fp8_handover
 
 VOCAB = 40512
 
 
 class GPTForLM(nn.Module):
-    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1):
+    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False):
         super().__init__()
         self.vocab = vocab
         self.emb = FusedBertEmbeddings(vocab, hidden, max_pos, 2, eps=1e-12, p=dropout, seed=4242)
-        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True) for i in range(layers)])
+        # fp8: MX fp8 qkv / proj / ffn1 / ffn2 in every block (models/bert.py); the LM head stays bf16
+        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8)
+                                     for i in range(layers)])
+        wire_fp8_handover(self.layers)
         self.head = MfmaLinear(hidden, vocab)
         self.p = dropout
         # device step counter for the fused dropout masks (ops/layernorm.py)

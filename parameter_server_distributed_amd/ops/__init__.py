@@ -64,6 +64,27 @@ def quantize_mx(x: torch.Tensor, e5m2: bool = False):
     return q, s
 
 
+def quantize_mx_t(x: torch.Tensor, e5m2: bool = False):
+    """MX fp8 of ``x^T`` from the contiguous bf16 ``x [R, C]`` (R % 32 == 0, C % 8 == 0) in one launch and
+    one read of ``x``: ``(q [C, R], scales [C, R/32])`` with blocks of 32 along R -- bitwise
+    ``quantize_mx(x.t().contiguous(), e5m2)`` without the bf16 transpose copy (kernels/fp8_t.hip). The
+    bwd-data GEMM of an fp8 Linear takes ``W^T [in, out]`` from the working weight ``W [out, in]`` this
+    way. Host tensors take the reference on the transposed copy."""
+    if x.dim() != 2 or x.shape[0] % 32 or x.shape[1] % 8:
+        raise ValueError(f"quantize_mx_t: x must be [R, C] with R % 32 == 0 and C % 8 == 0, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        q, s = quantize_mx_ref(x.t().contiguous(), e5m2)
+        return q, s.view(x.shape[1], x.shape[0] // 32)
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_mx_t: device tensors must be bf16, got {x.dtype}")
+    x = x.contiguous()
+    R, C = x.shape
+    q = torch.empty(C, R, dtype=torch.float8_e5m2 if e5m2 else torch.float8_e4m3fn, device=x.device)
+    s = torch.empty(C, R // 32, dtype=torch.uint8, device=x.device)
+    native().quant_mx_t_(x, q, s)
+    return q, s
+
+
 def quantize_mx_ref(x: torch.Tensor, e5m2: bool = False):
     """PyTorch reference of quant_mx_kernel: per 32-block the smallest power of two 2^e with
     amax * 2^-e <= fp8 max (E8M0 byte e + 127; 127 for an all-zero block), round-to-nearest-even."""

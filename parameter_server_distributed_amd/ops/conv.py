@@ -101,7 +101,7 @@ def _q8(t2: torch.Tensor, e5m2: bool = False, scaler: "DelayedScale | None" = No
     return quantize_fp8(t2, e5m2=e5m2)
 
 
-FP8_CALLS = {"fwd": 0, "dgrad": 0, "ps_weights": 0}  # fp8 kernel launches by role (tests / logs)
+from .fp8_common import FP8_CALLS, mx_weight  # noqa: E402  (launch counters / weight operand shared with ops/linear.py)
 
 
 def _mx_on() -> bool:
@@ -126,14 +126,7 @@ def _q_weight(mod, w2: torch.Tensor):
     weights this step's forward uses (``_psd_w8``, parallel/collective_ps.py / async_ps.py: no
     per-step weight quantisation), else quantised here."""
     if _mx_on():
-        pub = getattr(mod, "_psd_w8", None) if mod is not None else None
-        got = pub(w2) if pub is not None else None
-        if got is not None:
-            FP8_CALLS["ps_weights"] += 1
-            return got
-        from . import quantize_mx
-
-        return quantize_mx(w2)
+        return mx_weight(mod, w2)
     return _q8(w2)
 
 

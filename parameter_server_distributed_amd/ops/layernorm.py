@@ -17,6 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import native
+from ..utils.config import feature as _feat
+from .handover import Q8Pending
 
 
 class _AddLNFn(torch.autograd.Function):
@@ -24,7 +26,18 @@ class _AddLNFn(torch.autograd.Function):
     def forward(ctx, x, h, weight, bias, mod, p, x_grad_to=None):
         C = native()
         shp = x.shape
-        y, s, mean, rstd = C.ln_fwd(x.contiguous(), h.contiguous(), weight, bias, mod.eps, p, mod.seed, mod.step)
+        # MX hand-over (psd_mx_output_to): the forward also writes the MX e4m3 copy of y for the fp8
+        # Linear that reads it, which then skips its quantise pass (bitwise quantize_mx(y))
+        cons = getattr(mod, "_psd_mx_to", None)
+        q8 = sc8 = None
+        if (cons is not None and _feat("fp8_ln_handover")
+                and getattr(cons, "psd_mx_input_ok", lambda _h: False)(shp[-1])):
+            q8 = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+            sc8 = torch.empty(x.numel() // 32, dtype=torch.uint8, device=x.device)
+        y, s, mean, rstd = C.ln_fwd(x.contiguous(), h.contiguous(), weight, bias, mod.eps, p, mod.seed, mod.step,
+                                    q8, sc8)
+        if q8 is not None:
+            cons._psd_q8_pending = Q8Pending(y.view(shp), q8, sc8)
         ctx.mod, ctx.p, ctx.x_grad_to = mod, p, x_grad_to
         ctx.tok = getattr(x_grad_to, "_psd_tok", None) if x_grad_to is not None else None
         # h straight from an MfmaLinear with a bias and no activation (ops/linear.py tags its
@@ -70,6 +83,15 @@ class FusedAddLayerNorm(nn.LayerNorm):
         self.p = p
         self.seed = int(seed) & 0x7FFFFFFF
         self.step = None  # device int64 counter, set by the owning model (dropout masks per step)
+        self._psd_mx_to = None  # psd_mx_output_to: the fp8 MfmaLinear that reads this LayerNorm's output
+
+    def psd_mx_output_to(self, lin) -> None:
+        """Declare that ``lin`` (an ``MfmaLinear``) reads this LayerNorm's output: when it runs the MX fp8
+        recipe (``fp8="mx"``), the fused forward also writes its MX e4m3 input operand and leaves it on
+        ``lin`` as an ``ops.handover.Q8Pending`` (feature ``fp8_ln_handover``), wired by the model as
+        ``_psd_bn`` is for the convolutions. ``lin`` uses it only for exactly the tensor returned here.
+        (Kept out of the module tree: ``lin`` is registered where the model owns it.)"""
+        object.__setattr__(self, "_psd_mx_to", lin)
 
     def psd_direct_grad_params(self):
         return [self.weight, self.bias]

@@ -8,10 +8,25 @@ backward  dx = dy' W              NN GEMM (W read N-major through ds_read_b64_tr
           db = colsum(dy')        column-sum kernel (also into the sink); for GELU the activation
                                   backward and this column sum are one pass (gelu_bwd_colsum_)
 
-fp8 (``MfmaLinear(..., fp8=True)``): the forward GEMM runs on OCP e4m3 operands with per-tensor
-amax scaling (x and W quantised each step by the amax/quant kernels) on the MX-scaled
-v_mfma_scale_f32_16x16x128_f8f6f4 (2x the bf16 MFMA rate); the backward GEMMs stay bf16 on the
-saved bf16 x and W (fp8 forward / bf16 backward recipe). Needs in_features % 128 == 0.
+fp8, MX recipe (``MfmaLinear(..., fp8="mx")``; the encoder / decoder Linears of BERT and GPT built with
+``fp8=True``): forward y = act(q(x) q(W)^T + b) and bwd-data dx = q_e5m2(dy') q_t(W) on the block-scaled
+v_mfma_scale_f32_16x16x128_f8f6f4 (``gemm_fp8_``, 2x the bf16 MFMA rate) with OCP MX operands, one E8M0
+scale per 32 K-elements; the weight and bias gradients stay bf16 on the saved bf16 x and dy', through the
+routes and grad sinks of the bf16 path.
+  q(x)     the MX e4m3 copy the producing fused LayerNorm wrote (ops/layernorm.py psd_mx_output_to,
+           feature ``fp8_ln_handover``), else one ``quantize_mx`` pass
+  q(W)     the MX e4m3 copy the PS data plane published (``pull_dtype="fp8"``, the ``_psd_w8`` hook of
+           parallel/flat.py), else one ``quantize_mx`` pass
+  q_t(W)   ``quantize_mx_t``: W^T [in, out] with blocks along ``out`` in one pass over the bf16 W
+           (kernels/fp8_t.hip); q_e5m2(dy') one ``quantize_mx`` pass (feature ``fp8_dgrad``; off: bf16 dgrad)
+Applies when in_features % 128 == 0, out_features % 128 == 0 and feature ``fp8_compute`` is on; any other
+call of the module runs the bf16 path below. A residual LayerNorm's handed-over gradient is added after
+the fp8 bwd-data GEMM (no beta = 1 epilogue), and the GELU-backward epilogue fusion is not taken (the
+e5m2-A kernel has no activation epilogue): the producing GELU Linear runs ``gelu_bwd_colsum_``.
+
+fp8, per-tensor stub (``fp8=True``): the forward GEMM alone on OCP e4m3 operands with per-tensor amax
+scaling (x and W quantised each step by the amax / quant kernels); the backward GEMMs stay bf16. Needs
+in_features % 128 == 0. No model uses it.
 
 Per-shape routing (ops/autotune.py): for bf16 the forward, dgrad and wgrad GEMMs are each timed
 once against hipBLASLt (torch.addmm / mm; bias + activation then run as separate passes) and the
@@ -31,6 +46,8 @@ import torch.nn.functional as F
 from ..utils.config import feature as _feat
 from .. import native
 from . import autotune as _at
+from .fp8_common import FP8_CALLS, mx_weight
+from .handover import take
 
 ACTS = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 
@@ -130,7 +147,21 @@ class _LinearFn(torch.autograd.Function):
         y = torch.empty(M, N, dtype=x.dtype, device=x.device)
         act = ACTS[mod.act]
         aux = torch.empty_like(y) if act == 2 else None
-        if mod.fp8 and x2.shape[1] % 128 == 0:
+        use_mx = mod.fp8 == "mx" and mod.psd_mx_input_ok(x2.shape[1])
+        if use_mx:
+            from . import quantize_mx
+
+            # the MX copy of exactly this x from the producing LayerNorm, else quantised here
+            rec = take(mod, "_psd_q8_pending", x, strides=True)
+            if rec is not None:
+                xq, sx = rec.q.view(x2.shape), rec.scales
+                mod.psd_mx_handovers += 1
+            else:
+                xq, sx = quantize_mx(x2)
+            wq, sw = mx_weight(mod, weight)
+            C.gemm_fp8_(xq, wq, sx, sw, y, bias, act, aux)
+            FP8_CALLS["lin_fwd"] += 1
+        elif mod.fp8 is True and x2.shape[1] % 128 == 0:
             from . import quantize_fp8
 
             xq, sx = quantize_fp8(x2)
@@ -155,6 +186,7 @@ class _LinearFn(torch.autograd.Function):
                    {"mfma_ct": lambda: _ct(weight, x2, y, bias, act, aux)})()
         ctx.act = act
         ctx.mod = mod
+        ctx.mx = use_mx
         # per-forward token: a residual LayerNorm that hands this forward's input gradient over
         # records it, and backward only takes a hand-over carrying its own token (a backward that
         # stopped between the two -- an exception, autograd.grad on a partial graph -- can never
@@ -166,7 +198,9 @@ class _LinearFn(torch.autograd.Function):
         # producing GELU Linear's activation backward in its epilogue when x is that Linear's output
         # of the current forward
         src = getattr(mod, "_psd_gelu_from", None)
-        fuse = (src is not None and _feat("gelu_fuse") and getattr(x, "_psd_gelu_tok", None) is not None
+        # (not on the MX fp8 path: the e5m2-A GEMM has no activation epilogue, so no hand-over is made and
+        # the producer runs gelu_bwd_colsum_ itself)
+        fuse = (src is not None and not use_mx and _feat("gelu_fuse") and getattr(x, "_psd_gelu_tok", None) is not None
                 and x._psd_gelu_tok == (id(src), src._psd_tok) and getattr(src, "_psd_gelu_pre", None) is not None)
         ctx.gelu_src = src if fuse else None
         ctx.gelu_tok = src._psd_tok if fuse else None
@@ -220,7 +254,20 @@ class _LinearFn(torch.autograd.Function):
                 got = g
                 break
         pend.clear()
-        if ctx.needs_input_grad[0] and got is not None:
+        if ctx.needs_input_grad[0] and ctx.mx and _feat("fp8_dgrad"):
+            from . import quantize_mx, quantize_mx_t
+
+            # dx = q_e5m2(dy') . q_t(W): A = dy' [M, out] e5m2, B = W^T [in, out] e4m3, MX blocks along out
+            dyq, sdy = quantize_mx(dy2, e5m2=True)
+            wtq, swt = quantize_mx_t(w)
+            dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
+            C.gemm_fp8_(dyq, wtq, sdy, swt, dx)
+            FP8_CALLS["lin_dgrad"] += 1
+            if got is not None:
+                # x's other gradient (a residual LayerNorm's): added after the GEMM (no beta = 1 fp8 epilogue)
+                dx = got.view(M, K).add_(dx)
+            dx = dx.view(ctx.in_shape)
+        elif ctx.needs_input_grad[0] and got is not None:
             # x's other gradient (a residual LayerNorm's, ops/layernorm.py): accumulated by the GEMM
             dx = got.view(M, K)
             dx.addmm_(dy2, w)
@@ -257,8 +304,12 @@ class MfmaLinear(nn.Linear):
 
     def __init__(self, in_features, out_features, bias=True, act=None, device=None, dtype=None, fp8=False):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
+        if not (fp8 is False or fp8 is True or (isinstance(fp8, str) and fp8 == "mx")):
+            raise ValueError(f"MfmaLinear: fp8 must be False, True (per-tensor, forward only) or 'mx', got {fp8!r}")
         self.act = act
         self.fp8 = fp8
+        self._psd_q8_pending = None  # ops.handover.Q8Pending of the input, left by the producing LayerNorm
+        self.psd_mx_handovers = 0  # forwards that took it (tests / logs)
         self._psd_pending_dx: list = []  # gradients of the input handed over by a residual LayerNorm
         self._psd_gelu_from = None  # psd_gelu_input_from: the GELU Linear whose output is this one's input
         self._psd_gelu_hands: dict = {}  # forward token -> (pre-activation gradient, bias gradient) from the consumer
@@ -280,6 +331,13 @@ class MfmaLinear(nn.Linear):
 
     def psd_direct_grad_params(self):
         return [p for p in (self.weight, self.bias) if p is not None]
+
+    def psd_mx_input_ok(self, in_features: int) -> bool:
+        """True when a bf16 device input of ``in_features`` columns runs the MX fp8 recipe here (else
+        the bf16 path): what the forward and the LayerNorm that would hand its MX operand over ask."""
+        w = self.weight
+        return (self.fp8 == "mx" and w.is_cuda and w.dtype == torch.bfloat16 and in_features == self.in_features
+                and self.in_features % 128 == 0 and self.out_features % 128 == 0 and _feat("fp8_compute"))
 
     def forward(self, x):
         if _ok(x, self.weight):

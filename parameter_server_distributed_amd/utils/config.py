@@ -89,11 +89,12 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "tail_gram": (True, "the recomputing tail's statistics from the Gram matrix of conv3's input"),
     "dual_recompute": (True, "stride-1 downsample blocks: neither conv3's nor the downsample conv's output stored"),
     # fp8 (Wide-ResNet-101-2)
-    "fp8_compute": (True, "fp8 convolutions where the model asks for them"),
+    "fp8_compute": (True, "fp8 convolutions / Linear layers where the model asks for them"),
     "fp8_mx": (True, "MX block scales for every fp8 operand; off: per-tensor scales"),
     "fp8_mx_handover": (True, "BN passes write the consumer's MX e4m3 input / producer's MX e5m2 dY"),
     "fp8_delayed": (True, "per-tensor fp8: delayed (previous-call amax) scaling"),
-    "fp8_dgrad": (True, "fp8 e5m2-dY bwd-data of the fp8 convolutions"),
+    "fp8_dgrad": (True, "fp8 e5m2-dY bwd-data of the fp8 convolutions and fp8 Linear layers"),
+    "fp8_ln_handover": (True, "the fused LayerNorm writes the MX e4m3 input of the fp8 Linear that consumes it"),
     "async_cached_local": (True, "async PS at world 1: inbox / publish buffers in plain (cached) device memory "
                                  "instead of uncached IPC memory (AsyncPS hands it to the native engine)"),
     "async_apply_background": (True, "async PS with SSP bound >= 1: the owner's apply on a normal-priority stream "
