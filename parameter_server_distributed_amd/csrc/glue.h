@@ -18,6 +18,40 @@ T* opt_ptr(const c10::optional<at::Tensor>& t) {
   return given(t) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
 }
 
+// a bf16 tensor's elements as the launchers take them
+inline const uint16_t* bf16(const at::Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
+inline uint16_t* bf16_mut(const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
+
+// t's elements, or null for the undefined tensor
+template <typename T>
+T* ptr_or_null(const at::Tensor& t) {
+  return t.defined() ? reinterpret_cast<T*>(t.data_ptr()) : nullptr;
+}
+
+// a per-channel vector: n contiguous elements of dtype st on like's device; an optional one may be absent
+inline void check_vec(const char* op, const at::Tensor& t, int64_t n, at::ScalarType st, const at::Tensor& like,
+                      const char* name) {
+  TORCH_CHECK(t.defined() && t.numel() == n && t.scalar_type() == st && t.is_contiguous() && t.device() == like.device(),
+              op, ": ", name, " must be a contiguous ", st, " [", n, "] on the input's device");
+}
+inline void check_vec(const char* op, const c10::optional<at::Tensor>& t, int64_t n, at::ScalarType st,
+                      const at::Tensor& like, const char* name) {
+  if (given(t)) check_vec(op, *t, n, st, like, name);
+}
+
+// the statistics block of a BN forward launch (bn_ops.cpp): checks the parameter vectors, allocates
+// the saved statistics and (training) the scale/shift on like's device, and fills gamma .. counter,
+// M, C, training, momentum and eps of a. Eval mode takes the scale/shift from ss_eval.
+struct BnFwdArgs;
+struct BnFwdStats {
+  at::Tensor mean, invstd, ss;
+};
+BnFwdStats bn_fwd_stats(BnFwdArgs& a, const at::Tensor& like, int64_t M, int64_t C,
+                        const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
+                        const c10::optional<at::Tensor>& running_mean, const c10::optional<at::Tensor>& running_var,
+                        const c10::optional<at::Tensor>& counter, double momentum, double eps, bool training = true,
+                        const c10::optional<at::Tensor>& ss_eval = c10::nullopt);
+
 inline bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
 
 // laid out like an NHWC activation: channels_last when 4-D, contiguous otherwise (its 2-D [pixels, C] view)

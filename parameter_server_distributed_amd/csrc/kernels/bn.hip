@@ -1069,23 +1069,22 @@ static hipError_t finalize_pre(const float* part, int rows, float* fold_ws, int6
 
 // BN backward from a producer-reduced gradient (kernels/convn.hip bwd modes): g is already masked
 // (and holds the residual-branch gradient), part holds `rows` rows of (sum g, sum g (x - mean)).
-hipError_t launch_bn_bwd_pre(const uint16_t* g, const uint16_t* x, const uint16_t* gamma, const float* mean,
-                             const float* invstd, const float* part, int rows, float* fold_ws, uint16_t* dgamma,
-                             uint16_t* dbeta, float* coef, uint16_t* dx, int64_t M, int C, hipStream_t st, uint8_t* dq,
-                             uint8_t* dqmx) {
-  if (M <= 0) return hipSuccess;
-  if (C % 8 != 0 || rows <= 0) return hipErrorInvalidValue;
-  if (rows > kFoldRows && !fold_ws) return hipErrorInvalidValue;
-  const hipError_t fe = finalize_pre(part, rows, fold_ws, M, C, gamma, mean, invstd, dgamma, dbeta, coef, st);
+hipError_t launch_bn_bwd_pre(const BnPreArgs& a, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  if (a.C % 8 != 0 || a.rows <= 0) return hipErrorInvalidValue;
+  if (a.rows > kFoldRows && !a.fold_ws) return hipErrorInvalidValue;
+  const hipError_t fe = finalize_pre(a.part, a.rows, a.fold_ws, a.M, a.C, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta,
+                                     a.coef, st);
   if (fe != hipSuccess) return fe;
-  if (!dx) return hipGetLastError();  // coefficients only (BN-backward fold)
-  const int64_t nvec = M * (C / 8);
-  if (dq) {
-    if (!dqmx || C % 32 != 0) return hipErrorInvalidValue;
-    elemt_launch<2, true>(elem_launch(nvec, C), g, nullptr, nullptr, nullptr, x, coef, dx, nvec, C, dq, dqmx, st);
+  if (!a.dx) return hipGetLastError();  // coefficients only (BN-backward fold)
+  const int64_t nvec = a.M * (a.C / 8);
+  if (a.dq) {
+    if (!a.dqmx || a.C % 32 != 0) return hipErrorInvalidValue;
+    elemt_launch<2, true>(elem_launch(nvec, a.C), a.g, nullptr, nullptr, nullptr, a.x, a.coef, a.dx, nvec, a.C, a.dq,
+                          a.dqmx, st);
   } else {
-    elemt_launch<2, false>(elem_launch(nvec, C), g, nullptr, nullptr, nullptr, x, coef, dx, nvec, C, nullptr, nullptr,
-                           st);
+    elemt_launch<2, false>(elem_launch(nvec, a.C), a.g, nullptr, nullptr, nullptr, a.x, a.coef, a.dx, nvec, a.C, nullptr,
+                           nullptr, st);
   }
   return hipGetLastError();
 }

@@ -95,10 +95,22 @@ hipError_t launch_bn_fwd(const BnFwdArgs& a, hipStream_t stream);
 hipError_t launch_bn_bwd(const BnBwdArgs& a, hipStream_t stream);
 // backward from a producer-reduced, already-masked gradient g (convolution bwd-data epilogue):
 // fold (> kFoldRows partial rows: fold_ws [kFoldRows * 2C]) + finalize + dx = A g + B x + C
-hipError_t launch_bn_bwd_pre(const uint16_t* g, const uint16_t* x, const uint16_t* gamma, const float* mean,
-                             const float* invstd, const float* part, int rows, float* fold_ws, uint16_t* dgamma,
-                             uint16_t* dbeta, float* coef, uint16_t* dx, int64_t M, int C, hipStream_t stream,
-                             uint8_t* dq = nullptr, uint8_t* dqmx = nullptr);
+struct BnPreArgs {
+  const uint16_t* g;      // masked upstream gradient [M, C]
+  const uint16_t* x;      // the BN's input
+  const uint16_t* gamma;  // optional
+  const float *mean, *invstd;
+  const float* part;      // [rows][2][C] sum g, sum g (x - mean)
+  int rows;
+  float* fold_ws;         // [kFoldRows * 2C] when rows > kFoldRows
+  uint16_t *dgamma, *dbeta;  // optional, bf16 [C]
+  float* coef;            // [3C]
+  uint16_t* dx;           // optional (null: coefficients only, the BN-backward fold)
+  uint8_t *dq, *dqmx;     // optional MX e5m2 copy of dx + E8M0 scales (BnBwdArgs::dq)
+  int64_t M;
+  int C;
+};
+hipError_t launch_bn_bwd_pre(const BnPreArgs& a, hipStream_t stream);
 
 struct BnDualPreArgs {
   const uint16_t* g;      // masked upstream gradient (= the residual-branch gradient) [M, C]
