@@ -68,6 +68,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("quant_mx_", &quant_mx_, py::arg("x"), py::arg("out"), py::arg("scales"));
   m.def("dequant_mx_", &dequant_mx_, py::arg("q"), py::arg("scales"), py::arg("out"));
   m.def("quant_mx_t_", &quant_mx_t_, py::arg("x"), py::arg("out"), py::arg("scales"));
+  m.def("quant_mx_dual_", &quant_mx_dual_, py::arg("x"), py::arg("q_row"), py::arg("s_row"), py::arg("q_t"),
+        py::arg("s_t"));
   m.def("quant_fp8_jit_", &quant_fp8_jit_, py::arg("x"), py::arg("out"), py::arg("scale_inv"));
   m.def("quant_fp8_delayed_", &quant_fp8_delayed_, py::arg("x"), py::arg("out"), py::arg("scale_inv"),
         py::arg("hist"), py::arg("margin") = 1.0);
@@ -107,6 +109,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_fp8_", &gemm_fp8_, py::arg("A"), py::arg("B"), py::arg("a_scale"), py::arg("b_scale"), py::arg("out"),
         py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("aux") = py::none(), py::arg("part") = py::none(),
         py::arg("shift") = py::none());
+  m.def("gemm_fp8_splitk_", &gemm_fp8_splitk_, py::arg("A"), py::arg("B"), py::arg("a_scale"), py::arg("b_scale"),
+        py::arg("out"), py::arg("accumulate") = false, py::arg("scale") = 1.0, py::arg("splits") = 0);
+  m.def("gemm_fp8_splits", &gemm_fp8_splits, py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("convn_", &convn_, py::arg("x"), py::arg("w2"), py::arg("out"), py::arg("R"), py::arg("S"), py::arg("stride"),
         py::arg("pad"), py::arg("part") = py::none(), py::arg("shift") = py::none(), py::arg("variant") = -1,
         py::arg("x2") = py::none(), py::arg("bias") = py::none(), py::arg("no_store") = false,

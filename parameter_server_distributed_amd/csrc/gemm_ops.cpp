@@ -244,6 +244,47 @@ int64_t gemm_fp8_(const at::Tensor& A, const at::Tensor& B, const at::Tensor& a_
   return a.part ? rows : 1;
 }
 
+// out[M,N] (+)= scale * dq(A) dq(B)^T via split-K fp32 slabs on the block-scaled fp8 MFMA (the fp8 weight
+// gradient of a Linear: A = q_t(dy') [out, tokens], B = q_t(x) [in, tokens], K = tokens): A [M,K], B [N,K]
+// e4m3fn with MX scales uint8 [M, K/32] / [N, K/32]; splits 0: gemm_fp8_splits
+void gemm_fp8_splitk_(const at::Tensor& A, const at::Tensor& B, const at::Tensor& a_scale, const at::Tensor& b_scale,
+                      at::Tensor out, bool accumulate, double scale, int64_t splits) {
+  for (const at::Tensor* t : {&A, &B})
+    TORCH_CHECK(t->is_cuda() && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) % 16 == 0 && aligned16(*t),
+                "psd gemm_fp8_splitk: operands must be 2-D fp8 device tensors, unit inner stride, 16-B aligned rows");
+  TORCH_CHECK(A.scalar_type() == at::kFloat8_e4m3fn && B.scalar_type() == at::kFloat8_e4m3fn,
+              "psd gemm_fp8_splitk: A and B e4m3fn");
+  const Mnk d = mnk_of(A, B, true, true);
+  const int64_t M = d.M, N = d.N, K = d.K;
+  TORCH_CHECK(d.Kb == K, "psd gemm_fp8_splitk: K mismatch");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "psd gemm_fp8_splitk: K must be a multiple of 128");
+  TORCH_CHECK(N % 8 == 0, "psd gemm_fp8_splitk: N must be a multiple of 8");
+  TORCH_CHECK(a_scale.scalar_type() == at::kByte && b_scale.scalar_type() == at::kByte && a_scale.is_cuda() &&
+                  b_scale.is_cuda() && a_scale.is_contiguous() && b_scale.is_contiguous() &&
+                  a_scale.numel() == M * (K / 32) && b_scale.numel() == N * (K / 32) && A.stride(0) == K &&
+                  B.stride(0) == K && a_scale.device() == A.device() && b_scale.device() == A.device() &&
+                  B.device() == A.device(),
+              "psd gemm_fp8_splitk: MX scales must be uint8 [M, K/32] / [N, K/32] (contiguous operands)");
+  TORCH_CHECK(out.is_cuda() && out.device() == A.device() && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
+                  out.is_contiguous(),
+              "psd gemm_fp8_splitk: out must be contiguous [M, N]");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "psd gemm_fp8_splitk: out dtype");
+  TORCH_CHECK(splits >= 0 && splits <= 4096, "psd gemm_fp8_splitk: splits");
+  const c10::DeviceGuard g(A.device());
+  const int s = splits > 0 ? (int)splits : gemm_fp8_splits((int)M, (int)N, (int)K);
+  GemmArgs a = gemm_args(A, B, true, true, d, &out, N);
+  a.a_mx = a_scale.data_ptr<uint8_t>();
+  a.b_mx = b_scale.data_ptr<uint8_t>();
+  if (s == 1 && !accumulate && scale == 1.0) {  // one split: the single-split MX GEMM writes out itself, no slab
+    check_hip(launch_gemm_fp8(a, stream_of(A)), "psd gemm_fp8_splitk (single split)");
+    return;
+  }
+  at::Tensor slab = at::empty({(int64_t)s * M * N}, A.options().dtype(at::kFloat));
+  hipError_t e = launch_gemm_fp8_splitk(a, slab.data_ptr<float>(), s, out.data_ptr(), out.scalar_type() == at::kBFloat16,
+                                        accumulate, (float)scale, stream_of(A));
+  check_hip(e, "psd gemm_fp8_splitk");
+}
+
 // out[N] (+)= column sums of x[M,N] (bias gradient)
 void colsum_(const at::Tensor& x, at::Tensor out, bool accumulate) {
   chk2d(x, "x");

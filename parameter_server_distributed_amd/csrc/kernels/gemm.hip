@@ -428,6 +428,10 @@ __device__ __forceinline__ void tile_of(int wg, int tiles_m, int tiles_n, int& t
 // MX: the block-scaled fp8 form (per-32-K E8M0 scales of A rows and B columns): each K-tile's
 // scales (BM x 4 B of A, 256 x 4 B of B) ride in SC bytes at the end of its buffer, staged by one
 // extra 4-byte LDS-DMA per wave with the A-half0 pieces (so it is counted in VM like them).
+// MX with MODE 1 (split-K, the fp8 weight gradient: K = tokens): split z runs K-tiles [kbeg, kend) of
+// whole 128-wide tiles; the scale DMA addresses by the absolute k (kb = k >> 5 of K / 32 blocks per row)
+// like the operand staging, a split of one K-tile re-stages it with its scale DMA (the same count in VM),
+// and the epilogue is the fp32 slab store (no bias / activation / dequant multiply).
 // BM = 192 (IM = 3, 48-row quadrants) keeps the 256-row LDS geometry: each A half image is padded
 // to 128 rows / columns (the last 32 masked at staging, never read), so the staging and the
 // fragment reads are the BM = 256 ones and the LDS is 160 KiB. With CT (C^T stored) it is the
@@ -491,7 +495,8 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs g) {
   static_assert(BM != 192 || (!MX && !GA && !F8 && !ST && MODE == 0), "192-row tiles: plain bf16 GEMM");
   static_assert(!ST || (MODE == 0 && !GB && ACT == 0 && AK),
                 "statistics epilogue: single split, bf16 out, no activation, K-major A (zero rows past M)");
-  static_assert(!MX || (F8 && BM == 128 && MODE == 0), "MX: fp8, 128-row tiles (LDS), single split");
+  static_assert(!MX || (F8 && BM == 128 && (MODE == 0 || (!GA && ACT == 0 && F8A == 0 && !ST))),
+                "MX: fp8, 128-row tiles (LDS); split-K (fp32 slabs): the plain e4m3 GEMM only");
   static_assert(ACT != 3 || (MODE == 0 && !F8 && !GA && !GB && !ST), "GELU-backward epilogue: bf16 single-split GEMM");
   static_assert(!GB || (!AK && !BKM && MODE == 1 && !F8 && !GA), "implicit-GEMM wgrad: M-major dY, split-K");
   static_assert(!F8 || (AK && BKM), "fp8 GEMM takes K-major operands");
@@ -1523,6 +1528,43 @@ hipError_t launch_gemm_splitk(const GemmArgs& g0, float* slab, int splits, void*
   else
     hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(grid), dim3(256), 0, st, slab, eff, mn, out, accumulate, scale);
   return hipGetLastError();
+}
+
+// Splits of the MX fp8 split-K GEMM (128 x 256 tiles, one workgroup per tile and split): as many as fit
+// ONE round of workgroups on the chip (the reasoning on gemm_splits: a second, almost empty round
+// doubles the time), at least 512 k per split (4 K-tiles: the slab traffic of a split is M x N x 8 B
+// whatever its K), at most 64.
+int gemm_fp8_splits(int M, int N, int K) {
+  const int tiles = ((M + 127) / 128) * ((N + 255) / 256);
+  int s = std::max(1, cu_count() / std::max(tiles, 1));
+  const int kmax = K / 512;
+  if (s > kmax) s = kmax;
+  if (s > 64) s = 64;
+  return s < 1 ? 1 : s;
+}
+
+// out = (acc ? out : 0) + scale * dq(A) dq(B)^T, A [M][K] / B [N][K] MX e4m3 (the contract of
+// launch_gemm_fp8's MX form, no bias / activation), split-K into fp32 slabs [splits][M][N] and the
+// deterministic slab reduce (fixed slab order, no atomics).
+hipError_t launch_gemm_fp8_splitk(const GemmArgs& g0, float* slab, int splits, void* out, int out_bf16, int accumulate,
+                                  float scale, hipStream_t st) {
+  if (g0.M <= 0 || g0.N <= 0) return hipSuccess;
+  if (!g0.a_mx || !g0.b_mx || g0.K < 128 || g0.K % 128 != 0 || !g0.a_kmajor || !g0.b_kmajor || g0.lda != g0.K ||
+      g0.ldb != g0.K || g0.N % 8 != 0 || g0.f8a != 0 || g0.bias || g0.act || g0.part || !slab || !out || splits < 1)
+    return hipErrorInvalidValue;
+  GemmArgs g = g0;
+  g.C = slab;
+  g.aux = nullptr;
+  g.c_f32 = 1;
+  g.ldc = g.N;
+  int kps = (g.K + splits - 1) / splits;
+  kps = (kps + 127) / 128 * 128;  // whole 128-wide K-tiles
+  g.k_per_split = kps;
+  if (!fits_rsrc(g, 1)) return hipErrorInvalidValue;  // (k_per_split > 0: C is one slab)
+  const int eff = (g.K + kps - 1) / kps;  // splits that own a non-empty k-range
+  hipError_t e = launch_8p_act<128, true, true, 1, true, 0, false, 0, false, true>(g, eff, st);
+  if (e != hipSuccess) return e;
+  return launch_splitk_reduce(slab, eff, (int64_t)g.M * g.N, out, out_bf16, accumulate, scale, st);
 }
 
 // One level of a split-sum tree: out[c] = sum of in[s] for s in [G c, min(G c + G, splits)), mn

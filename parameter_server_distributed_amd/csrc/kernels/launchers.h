@@ -143,5 +143,10 @@ hipError_t launch_dequant_mx(const uint8_t* q, const uint8_t* scales, int64_t n,
 // blocks along R (R % 32 == 0, C % 8 == 0); bitwise launch_quant_mx of the transposed copy
 hipError_t launch_quant_mx_t(const void* x, int64_t R, int64_t C, int e5m2, uint8_t* q, uint8_t* scales,
                              hipStream_t stream);
+// both MX copies of x [R, C] bf16 from one read (kernels/fp8_t.hip): q_row [R, C] / s_row [R * C / 32]
+// bitwise launch_quant_mx, q_t [C, R] / s_t [C, R/32] bitwise launch_quant_mx_t, each in its own format
+// (R % 32 == 0, C % 32 == 0)
+hipError_t launch_quant_mx_dual(const void* x, int64_t R, int64_t C, int e5m2_row, int e5m2_t, uint8_t* q_row,
+                                uint8_t* s_row, uint8_t* q_t, uint8_t* s_t, hipStream_t stream);
 
 }  // namespace psd

@@ -63,6 +63,13 @@ hipError_t launch_splitk_reduce(float* slab, int splits, int64_t mn, void* out, 
 // split-K GEMM into fp32 slabs [splits][M][N], then out = (acc ? out : 0) + scale * sum(slabs)
 hipError_t launch_gemm_splitk(const GemmArgs& g, float* slab, int splits, void* out, int out_bf16, int accumulate,
                               float scale, hipStream_t stream);
+// the same on the block-scaled fp8 MFMA: A [M][K], B [N][K] MX e4m3 (a_mx / b_mx set, contiguous, K % 128
+// == 0, N % 8 == 0), k_per_split rounded up to whole 128-wide K-tiles, only non-empty splits launched,
+// the deterministic reduce; hipErrorInvalidValue outside that contract
+hipError_t launch_gemm_fp8_splitk(const GemmArgs& g, float* slab, int splits, void* out, int out_bf16, int accumulate,
+                                  float scale, hipStream_t stream);
+// splits for it: one round of 128 x 256 tiles on the chip, >= 512 k per split, <= 64
+int gemm_fp8_splits(int M, int N, int K);
 // out[n] (+)= sum_m x[m][n]; part is an fp32 [kColsumPartRows * N] scratch
 constexpr int kColsumPartRows = 2048;
 // pre/xo (optional): x is dy of a GELU(tanh) output; xo = bf16(dy * gelu'(pre)) is written and summed

@@ -834,6 +834,40 @@ void quant_mx_t_(const at::Tensor& x, at::Tensor out, at::Tensor scales) {
             "quant_mx_t");
 }
 
+// both MX copies of x [R, C] bf16 from one read: q_row [R, C] / s_row [R * C / 32] (blocks along C, bitwise
+// quant_mx_) and q_t [C, R] / s_t [C, R / 32] (blocks along R, bitwise quant_mx_t_); each output's format
+// (e4m3fn / e5m2) is its tensor's dtype
+void quant_mx_dual_(const at::Tensor& x, at::Tensor q_row, at::Tensor s_row, at::Tensor q_t, at::Tensor s_t) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() && x.scalar_type() == at::kBFloat16 &&
+                  x.size(0) % 32 == 0 && x.size(1) % 32 == 0,
+              "psd: quant_mx_dual input must be a contiguous bf16 [R, C] device tensor with R % 32 == 0 and C % 32 == 0");
+  const int64_t R = x.size(0), C = x.size(1);
+  auto f8 = [](const at::Tensor& t) {
+    return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kFloat8_e5m2;
+  };
+  TORCH_CHECK(f8(q_row) && q_row.dim() == 2 && q_row.size(0) == R && q_row.size(1) == C && q_row.is_contiguous() &&
+                  q_row.device() == x.device(),
+              "psd: quant_mx_dual q_row must be a contiguous float8_e4m3fn or float8_e5m2 [R, C] tensor on x's device");
+  TORCH_CHECK(f8(q_t) && q_t.dim() == 2 && q_t.size(0) == C && q_t.size(1) == R && q_t.is_contiguous() &&
+                  q_t.device() == x.device(),
+              "psd: quant_mx_dual q_t must be a contiguous float8_e4m3fn or float8_e5m2 [C, R] tensor on x's device");
+  for (const at::Tensor* s : {&s_row, &s_t})
+    TORCH_CHECK(s->scalar_type() == at::kByte && s->is_contiguous() && s->numel() == x.numel() / 32 &&
+                    s->device() == x.device(),
+                "psd: quant_mx_dual scales must be uint8 [R * C / 32] and [C, R / 32] on x's device");
+  const c10::DeviceGuard g(x.device());
+  if (x.numel() == 0) return;
+  check_aligned(x, "x");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q_row.data_ptr()) & 15u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(q_t.data_ptr()) & 15u) == 0,
+              "psd: fp8 out must be 16-byte aligned");
+  hip_check(launch_quant_mx_dual(x.data_ptr(), R, C, q_row.scalar_type() == at::kFloat8_e5m2 ? 1 : 0,
+                                 q_t.scalar_type() == at::kFloat8_e5m2 ? 1 : 0,
+                                 reinterpret_cast<uint8_t*>(q_row.data_ptr()), s_row.data_ptr<uint8_t>(),
+                                 reinterpret_cast<uint8_t*>(q_t.data_ptr()), s_t.data_ptr<uint8_t>(), stream_of(x)),
+            "quant_mx_dual");
+}
+
 void dequant_mx_(const at::Tensor& q, const at::Tensor& scales, at::Tensor out) {
   TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.is_contiguous() && q.is_cuda() && out.numel() == q.numel() &&
                   out.is_contiguous() && q.numel() % 32 == 0,

@@ -67,6 +67,7 @@ void dequant_mx_(const at::Tensor& q, const at::Tensor& scales, at::Tensor out);
 // x [R, C] bf16 -> the MX copy of x^T: out [C, R] (e4m3fn / e5m2), scales [C, R/32]; bitwise
 // quant_mx_ of x.t().contiguous(), one launch and one read of x (kernels/fp8_t.hip)
 void quant_mx_t_(const at::Tensor& x, at::Tensor out, at::Tensor scales);
+void quant_mx_dual_(const at::Tensor& x, at::Tensor q_row, at::Tensor s_row, at::Tensor q_t, at::Tensor s_t);
 
 std::vector<at::Tensor> bn_fwd(const at::Tensor& x, c10::optional<at::Tensor> gamma, c10::optional<at::Tensor> beta,
                                c10::optional<at::Tensor> running_mean, c10::optional<at::Tensor> running_var,
@@ -182,6 +183,10 @@ int64_t conv_fwd_fp8_(const at::Tensor& x, const at::Tensor& w2, const at::Tenso
 int64_t gemm_fp8_(const at::Tensor& A, const at::Tensor& B, const at::Tensor& a_scale, const at::Tensor& b_scale,
                   at::Tensor out, c10::optional<at::Tensor> bias, int64_t act, c10::optional<at::Tensor> aux,
                   c10::optional<at::Tensor> part, c10::optional<at::Tensor> shift);
+// out[M,N] (+)= scale * dq(A) dq(B)^T on the split-K MX fp8 GEMM (A [M,K], B [N,K] e4m3fn, uint8 MX scales;
+// splits 0: gemm_fp8_splits)
+void gemm_fp8_splitk_(const at::Tensor& A, const at::Tensor& B, const at::Tensor& a_scale, const at::Tensor& b_scale,
+                      at::Tensor out, bool accumulate, double scale, int64_t splits);
 std::vector<at::Tensor> maxpool3s2_fwd(const at::Tensor& x);
 at::Tensor maxpool3s2_bwd(const at::Tensor& dy, const at::Tensor& arg, int64_t H, int64_t W,
                           const c10::optional<at::Tensor>& dy2);

@@ -40,6 +40,10 @@ hipError_t launch_dequant_mx(const uint8_t*, const uint8_t*, int64_t, void*, int
 hipError_t launch_quant_mx_t(const void*, int64_t, int64_t, int, uint8_t*, uint8_t*, hipStream_t) {
   return hipErrorNotSupported;
 }
+hipError_t launch_quant_mx_dual(const void*, int64_t, int64_t, int, int, uint8_t*, uint8_t*, uint8_t*, uint8_t*,
+                                hipStream_t) {
+  return hipErrorNotSupported;
+}
 hipError_t launch_sumsq_partials(const void*, int32_t, int64_t, float*, hipStream_t, int) { return hipErrorNotSupported; }
 hipError_t launch_clip_finalize(const float*, int64_t, float, float*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_xfer(const XferList&, hipStream_t) { return hipErrorNotSupported; }

@@ -85,6 +85,32 @@ def quantize_mx_t(x: torch.Tensor, e5m2: bool = False):
     return q, s
 
 
+def quantize_mx_dual(x: torch.Tensor, e5m2_row: bool = False, e5m2_t: bool = False):
+    """Both MX fp8 copies of the contiguous bf16 ``x [R, C]`` (R % 32 == 0, C % 32 == 0) from one launch and
+    one read of ``x``: ``(q_row [R, C], s_row [R * C / 32], q_t [C, R], s_t [C, R/32])`` -- the first pair
+    bitwise ``quantize_mx(x, e5m2_row)`` (blocks along C), the second bitwise ``quantize_mx_t(x, e5m2_t)``
+    (blocks along R) (kernels/fp8_t.hip quant_mx_dual_kernel). An fp8 Linear's backward takes dy' this way:
+    the e5m2 row copy for the bwd-data GEMM, the e4m3 transposed copy for the weight gradient. Host tensors
+    take the reference twice."""
+    if x.dim() != 2 or x.shape[0] % 32 or x.shape[1] % 32:
+        raise ValueError(f"quantize_mx_dual: x must be [R, C] with R % 32 == 0 and C % 32 == 0, got {tuple(x.shape)}")
+    R, C = x.shape
+    if not x.is_cuda:
+        qr, sr = quantize_mx_ref(x.contiguous(), e5m2_row)
+        qt, st = quantize_mx_ref(x.t().contiguous(), e5m2_t)
+        return qr, sr, qt, st.view(C, R // 32)
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_mx_dual: device tensors must be bf16, got {x.dtype}")
+    x = x.contiguous()
+    f8 = lambda e5: torch.float8_e5m2 if e5 else torch.float8_e4m3fn  # noqa: E731
+    qr = torch.empty(R, C, dtype=f8(e5m2_row), device=x.device)
+    sr = torch.empty(R * C // 32, dtype=torch.uint8, device=x.device)
+    qt = torch.empty(C, R, dtype=f8(e5m2_t), device=x.device)
+    st = torch.empty(C, R // 32, dtype=torch.uint8, device=x.device)
+    native().quant_mx_dual_(x, qr, sr, qt, st)
+    return qr, sr, qt, st
+
+
 def quantize_mx_ref(x: torch.Tensor, e5m2: bool = False):
     """PyTorch reference of quant_mx_kernel: per 32-block the smallest power of two 2^e with
     amax * 2^-e <= fp8 max (E8M0 byte e + 127; 127 for an all-zero block), round-to-nearest-even."""

@@ -5,8 +5,9 @@ from __future__ import annotations
 import torch
 
 # fp8 kernel launches by role (tests / logs): "fwd" / "dgrad" the convolutions, "lin_fwd" / "lin_dgrad" the
-# Linear layers, "ps_weights" forwards (of either) that read the MX weight copy the PS data plane published
-FP8_CALLS = {"fwd": 0, "dgrad": 0, "ps_weights": 0, "lin_fwd": 0, "lin_dgrad": 0}
+# Linear layers ("lin_wgrad" their fp8 weight gradients, feature ``fp8_wgrad``), "ps_weights" forwards (of
+# either) that read the MX weight copy the PS data plane published
+FP8_CALLS = {"fwd": 0, "dgrad": 0, "ps_weights": 0, "lin_fwd": 0, "lin_dgrad": 0, "lin_wgrad": 0}
 
 
 def mx_weight(mod, w2: torch.Tensor):

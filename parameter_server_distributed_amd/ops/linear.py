@@ -12,13 +12,20 @@ fp8, MX recipe (``MfmaLinear(..., fp8="mx")``; the encoder / decoder Linears of 
 ``fp8=True``): forward y = act(q(x) q(W)^T + b) and bwd-data dx = q_e5m2(dy') q_t(W) on the block-scaled
 v_mfma_scale_f32_16x16x128_f8f6f4 (``gemm_fp8_``, 2x the bf16 MFMA rate) with OCP MX operands, one E8M0
 scale per 32 K-elements; the weight and bias gradients stay bf16 on the saved bf16 x and dy', through the
-routes and grad sinks of the bf16 path.
+routes and grad sinks of the bf16 path -- unless feature ``fp8_wgrad`` (default off) is on and tokens % 128
+== 0: then dW = q_t(dy') q_t(x)^T, both operands e4m3 with blocks of 32 along the tokens (K = tokens), on
+the split-K form of the same MFMA kernel (``gemm_fp8_splitk_``: fp32 slabs, deterministic reduce), written
+where the bf16 route writes (the grad sink's bf16 / fp32 view, else a fresh bf16 tensor). The bias gradient
+stays as it is.
   q(x)     the MX e4m3 copy the producing fused LayerNorm wrote (ops/layernorm.py psd_mx_output_to,
            feature ``fp8_ln_handover``), else one ``quantize_mx`` pass
   q(W)     the MX e4m3 copy the PS data plane published (``pull_dtype="fp8"``, the ``_psd_w8`` hook of
            parallel/flat.py), else one ``quantize_mx`` pass
   q_t(W)   ``quantize_mx_t``: W^T [in, out] with blocks along ``out`` in one pass over the bf16 W
            (kernels/fp8_t.hip); q_e5m2(dy') one ``quantize_mx`` pass (feature ``fp8_dgrad``; off: bf16 dgrad)
+  q_t(dy') with ``fp8_wgrad``: the transposed e4m3 half of one ``quantize_mx_dual`` pass over dy' whose e5m2
+           row half (bitwise ``quantize_mx``'s) feeds bwd-data, else ``quantize_mx_t(dy')``; q_t(x) one
+           ``quantize_mx_t`` pass over the saved bf16 x
 Applies when in_features % 128 == 0, out_features % 128 == 0 and feature ``fp8_compute`` is on; any other
 call of the module runs the bf16 path below. A residual LayerNorm's handed-over gradient is added after
 the fp8 bwd-data GEMM (no beta = 1 epilogue), and the GELU-backward epilogue fusion is not taken (the
@@ -254,11 +261,17 @@ class _LinearFn(torch.autograd.Function):
                 got = g
                 break
         pend.clear()
+        # fp8 weight gradient (feature fp8_wgrad): MX blocks run along the tokens, whole 128-wide K-tiles
+        wgrad8 = ctx.mx and ctx.needs_input_grad[1] and M % 128 == 0 and _feat("fp8_wgrad")
+        dyT = sdyT = None  # q_t(dy') [out, tokens] e4m3, when the dual quantiser below made it
         if ctx.needs_input_grad[0] and ctx.mx and _feat("fp8_dgrad"):
-            from . import quantize_mx, quantize_mx_t
+            from . import quantize_mx, quantize_mx_dual, quantize_mx_t
 
             # dx = q_e5m2(dy') . q_t(W): A = dy' [M, out] e5m2, B = W^T [in, out] e4m3, MX blocks along out
-            dyq, sdy = quantize_mx(dy2, e5m2=True)
+            if wgrad8:  # one read of dy' for both of its MX copies; the row half is bitwise quantize_mx's
+                dyq, sdy, dyT, sdyT = quantize_mx_dual(dy2, e5m2_row=True, e5m2_t=False)
+            else:
+                dyq, sdy = quantize_mx(dy2, e5m2=True)
             wtq, swt = quantize_mx_t(w)
             dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
             C.gemm_fp8_(dyq, wtq, sdy, swt, dx)
@@ -285,8 +298,18 @@ class _LinearFn(torch.autograd.Function):
             dw = sink(ctx.mod.weight) if sink is not None else None
             if dw is None:
                 dw = torch.empty(w.shape, dtype=w.dtype, device=w.device)
-            _route(("wgrad", M, K, N), lambda: C.gemm_splitk_(dy2, x2, False, False, dw, False, 1.0, 0),
-                   lambda: torch.mm(dy2.t(), x2, out=dw), dw)()
+            if wgrad8:
+                from . import quantize_mx_t
+
+                # dW = q_t(dy') . q_t(x)^T: A = dy'^T [out, tokens], B = x^T [in, tokens], both e4m3, K = tokens
+                if dyT is None:
+                    dyT, sdyT = quantize_mx_t(dy2)
+                xT, sxT = quantize_mx_t(x2)
+                C.gemm_fp8_splitk_(dyT, xT, sdyT, sxT, dw, False, 1.0, 0)
+                FP8_CALLS["lin_wgrad"] += 1
+            else:
+                _route(("wgrad", M, K, N), lambda: C.gemm_splitk_(dy2, x2, False, False, dw, False, 1.0, 0),
+                       lambda: torch.mm(dy2.t(), x2, out=dw), dw)()
         bh = getattr(ctx.mod, "_psd_bias_hand", None)
         ctx.mod._psd_bias_hand = None
         if db is None and bh is not None and bh[0] == ctx.tok and bh[1] == dy2.data_ptr():

@@ -94,6 +94,7 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "fp8_mx_handover": (True, "BN passes write the consumer's MX e4m3 input / producer's MX e5m2 dY"),
     "fp8_delayed": (True, "per-tensor fp8: delayed (previous-call amax) scaling"),
     "fp8_dgrad": (True, "fp8 e5m2-dY bwd-data of the fp8 convolutions and fp8 Linear layers"),
+    "fp8_wgrad": (False, "fp8 e4m3 x e4m3 split-K weight gradient of the fp8 Linear layers (tokens % 128 == 0); off: bf16"),
     "fp8_ln_handover": (True, "the fused LayerNorm writes the MX e4m3 input of the fp8 Linear that consumes it"),
     "async_cached_local": (True, "async PS at world 1: inbox / publish buffers in plain (cached) device memory "
                                  "instead of uncached IPC memory (AsyncPS hands it to the native engine)"),

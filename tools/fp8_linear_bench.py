@@ -8,6 +8,10 @@
   q(x), q(W), q(dy)    the stand-alone quantize_mx passes the recipe runs when no hand-over / published
                        copy arrives; q_t(W) = quant_mx_t_ against a transpose copy + quant_mx_
   LayerNorm forward    with and without the MX side output (the hand-over that replaces q(x))
+  weight gradient      (feature fp8_wgrad) the bf16 weight gradient as routed today; gemm_fp8_splitk_ on MX
+                       e4m3 dy^T, x^T alone; quantize_mx_dual(dy) against the quantize_mx(e5m2) + quantize_mx_t
+                       passes it replaces; quantize_mx_t(x); and the sums of the two arms: bf16 = wgrad +
+                       q_e5m2(dy) (what bwd-data needs anyway), fp8 = GEMM + q_dual(dy) + q_t(x)
 
 Variants are interleaved over rounds in one process; the table gives the median and the minimum (us).
 Random operands (zero-filled ones read high on this chip).
@@ -23,8 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from parameter_server_distributed_amd import native  # noqa: E402
-from parameter_server_distributed_amd.ops import quantize_mx, quantize_mx_t  # noqa: E402
-from parameter_server_distributed_amd.ops.linear import MfmaLinear, _dgrad_route  # noqa: E402
+from parameter_server_distributed_amd.ops import quantize_mx, quantize_mx_dual, quantize_mx_t  # noqa: E402
+from parameter_server_distributed_amd.ops.linear import MfmaLinear, _dgrad_route, _route  # noqa: E402
 
 SHAPES = [("qkv", 768, 2304, None), ("proj", 768, 768, None), ("ffn1", 768, 3072, "gelu"), ("ffn2", 3072, 768, None)]
 
@@ -106,6 +110,39 @@ def main():
         cells = " | ".join(f"{res[k][0]:.1f} ({res[k][1]:.1f})" for k in
                            ("bf16_fwd", "fp8_fwd", "qx", "qw", "bf16_dgrad", "fp8_dgrad", "qdy", "qtw", "t_qw"))
         print(f"| {name} | {K} | {N} | {cells} |", flush=True)
+    # the weight gradient (feature fp8_wgrad): dW [N, K] = dy^T x over M tokens
+    print("\n| layer | K | N | bf16 wgrad | fp8 wgrad GEMM | q_dual(dy) | q_e5m2(dy) + q_t(dy) | q_t(x) | "
+          "bf16 arm: wgrad + q_e5m2(dy) | fp8 arm: GEMM + q_dual(dy) + q_t(x) | splits |")
+    print("|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|---:|")
+    for name, K, N, _act in SHAPES:
+        x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+        dy = torch.randn(M, N, device=dev).to(torch.bfloat16)
+        dwb = torch.empty(N, K, device=dev, dtype=torch.bfloat16)
+        dw8 = torch.empty_like(dwb)
+        gq, sg = quantize_mx_t(dy)
+        xq, sx = quantize_mx_t(x)
+
+        def bf16_wgrad():  # the route the module's backward takes for this shape (ops/autotune.py)
+            _route(("wgrad", M, K, N), lambda: C.gemm_splitk_(dy, x, False, False, dwb, False, 1.0, 0),
+                   lambda: torch.mm(dy.t(), x, out=dwb), dwb)()
+
+        def two_passes():  # what the dual kernel replaces
+            quantize_mx(dy, e5m2=True)
+            quantize_mx_t(dy)
+
+        res = interleaved({
+            "bf16_wgrad": bf16_wgrad,
+            "fp8_wgrad": lambda: C.gemm_fp8_splitk_(gq, xq, sg, sx, dw8, False, 1.0, 0),
+            "qdual": lambda: quantize_mx_dual(dy, e5m2_row=True, e5m2_t=False),
+            "q2": two_passes,
+            "qtx": lambda: quantize_mx_t(x),
+            "qdy": lambda: quantize_mx(dy, e5m2=True),
+        }, a.rounds, a.iters)
+        arm_b = tuple(res["bf16_wgrad"][i] + res["qdy"][i] for i in (0, 1))
+        arm_8 = tuple(res["fp8_wgrad"][i] + res["qdual"][i] + res["qtx"][i] for i in (0, 1))
+        cells = " | ".join(f"{res[k][0]:.1f} ({res[k][1]:.1f})" for k in ("bf16_wgrad", "fp8_wgrad", "qdual", "q2", "qtx"))
+        print(f"| {name} | {K} | {N} | {cells} | {arm_b[0]:.1f} ({arm_b[1]:.1f}) | {arm_8[0]:.1f} ({arm_8[1]:.1f}) | "
+              f"{C.gemm_fp8_splits(N, K, M)} |", flush=True)
     # the LayerNorm forward with and without the MX side output (H = 768)
     H = 768
     xs = torch.randn(M, H, device=dev).to(torch.bfloat16)
