@@ -13,12 +13,18 @@
 namespace psd {
 
 namespace {
+// packed documents are served by the causal kernels only (checked first: an argument error, whatever the tensors)
+void check_docs(const c10::optional<at::Tensor>& doc_start, bool causal) {
+  TORCH_CHECK(!given(doc_start) || causal,
+              "psd attn: doc_start needs causal=True (the kernels do not serve bidirectional packing)");
+}
 void check_attn(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd attn: ", what,
               " must be a contiguous bf16 device tensor");
 }
 AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed, const c10::optional<at::Tensor>& step,
-                   const c10::optional<at::Tensor>& lens, int64_t grid_cap, bool causal) {
+                   const c10::optional<at::Tensor>& lens, int64_t grid_cap, bool causal,
+                   const c10::optional<at::Tensor>& doc_start) {
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
   const int64_t dh = qkv.size(2) / (3 * heads);
   TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh) || attn_long_supported((int)qkv.size(1), (int)dh),
@@ -44,16 +50,24 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
   TORCH_CHECK(grid_cap >= 0 && grid_cap <= INT32_MAX, "psd attn: grid_cap must be >= 0");
   a.grid_cap = (int32_t)grid_cap;
   a.causal = causal ? 1 : 0;  // query q sees keys <= q (and < its length): the CAUSAL kernel copies
+  if (given(doc_start)) {  // packed documents: clamped and compared on the device only, never read by the host
+    TORCH_CHECK(doc_start->scalar_type() == at::kInt && doc_start->is_contiguous() && doc_start->dim() == 2 &&
+                    doc_start->size(0) == qkv.size(0) && doc_start->size(1) == qkv.size(1) &&
+                    doc_start->device() == qkv.device(),
+                "psd attn: doc_start must be a contiguous int32 [B, S] tensor on qkv's device");
+    a.doc = doc_start->data_ptr<int32_t>();
+  }
   return a;
 }
 }  // namespace
 
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal) {
+                                 bool causal, c10::optional<at::Tensor> doc_start) {
+  check_docs(doc_start, causal);
   check_attn(qkv, "qkv");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start);
   at::Tensor o = at::empty({qkv.size(0), qkv.size(1), qkv.size(2) / 3}, qkv.options());
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
@@ -69,17 +83,19 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
 // deterministic column reduce (with lens the padded rows of dqkv are written as zeros, so the same
 // sums hold).
 // lens (optional, int32 [B]): valid rows per sequence; grid_cap > 0 bounds the persistent grid (tests);
-// causal: the mask the forward used (keys <= q).
+// causal: the mask the forward used (keys <= q); doc_start (optional, int32 [B, S], causal only): the
+// document starts the forward used (keys doc_start[b, q] <= key <= q).
 at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal) {
+                    bool causal, c10::optional<at::Tensor> doc_start) {
+  check_docs(doc_start, causal);
   at::Tensor dout = dout_in.contiguous();
   check_attn(dout, "dout");
   check_attn(qkv, "qkv");
   check_attn(o, "o");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start);
   TORCH_CHECK(o.sizes() == dout.sizes() && o.size(0) == qkv.size(0) && o.size(1) == qkv.size(1) &&
                   o.size(2) * 3 == qkv.size(2),
               "psd attn bwd: o / dout must be [B, S, H*Dh]");

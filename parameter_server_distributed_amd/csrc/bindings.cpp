@@ -178,10 +178,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("counter") = py::none());
   m.def("stem_wgrad", &stem_wgrad);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
-        py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false);
+        py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
+        py::arg("doc_start") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("heads"),
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
-        py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false);
+        py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
+        py::arg("doc_start") = py::none());
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
         py::arg("sc8_out") = py::none());
@@ -190,11 +192,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dbeta_out") = py::none(), py::arg("dhsum_out") = py::none());
   m.def("emb_ln_fwd", &emb_ln_fwd, py::arg("ids"), py::arg("types"), py::arg("W"), py::arg("P"), py::arg("T"),
         py::arg("gamma"), py::arg("beta"), py::arg("S"), py::arg("eps"), py::arg("p"), py::arg("seed"),
-        py::arg("step") = py::none());
+        py::arg("step") = py::none(), py::arg("pos_ids") = py::none());
   m.def("emb_ln_bwd", &emb_ln_bwd, py::arg("dy"), py::arg("ids"), py::arg("types"), py::arg("W"), py::arg("P"),
         py::arg("T"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("S"), py::arg("p"), py::arg("seed"),
         py::arg("step") = py::none(), py::arg("dgamma") = py::none(), py::arg("dbeta") = py::none(),
-        py::arg("dT") = py::none());
+        py::arg("dT") = py::none(), py::arg("pos_ids") = py::none());
   m.def("bn_pool_bwd", &bn_pool_bwd, py::arg("gpool"), py::arg("gpool2"), py::arg("arg"), py::arg("x"), py::arg("gamma"),
         py::arg("save_mean"), py::arg("save_invstd"), py::arg("ss"), py::arg("dgamma_out") = py::none(),
         py::arg("dbeta_out") = py::none());

@@ -66,10 +66,16 @@ __device__ __forceinline__ void stage_rows(uint8_t* lds, const uint16_t* src, in
 // (The length-aware copy asks for two waves per SIMD: left alone the compiler takes 233 + 80 registers
 // at NW = 4, one workgroup per CU instead of two; a minimum of 1 is the default and leaves the
 // full-length copy as it was.)
-template <int NW, bool VARLEN, bool CAUSAL>
+// DOCS (a.doc; always with CAUSAL): query q sees keys doc[q] <= key <= q. Wave w walks key blocks
+// jlo <= j <= w, jlo = doc[32 w] >> 5 (the block's first query has the smallest start), and keys < doc[q]
+// of the blocks up to the one with the largest start of the wave go to -inf by the same select. A valid
+// query sees itself and a padded one (doc not read: start 0) key 32 w, so the row max stays finite. The
+// starts ride in the item prefetch; with a.doc null the launchers never pick this copy.
+template <int NW, bool VARLEN, bool CAUSAL, bool DOCS = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VARLEN ? 2 : 1)))
 void attn_fwd_kernel(AttnArgs a) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
+  static_assert(CAUSAL || !DOCS, "the document copy is causal");
   constexpr int S = 32 * NW;
   constexpr int NT = 64 * NW;
   constexpr int CH = S * 8 / NT;  // 16-B chunks per lane per tile (= 4)
@@ -87,6 +93,7 @@ void attn_fwd_kernel(AttnArgs a) {
   const bool drop = a.thresh != 0u;
 
   u32x4 pk[CH], pv[CH], pq[4];
+  int pdq = 0;  // DOCS: the start of query q's document (0 for a padded query)
   auto fetch = [&](int bh) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
@@ -108,6 +115,7 @@ void attn_fwd_kernel(AttnArgs a) {
       if (!VARLEN || q < Lf) q4 = *reinterpret_cast<const u32x4*>(base + (int64_t)q * qkv_rs + 16 * ks + 8 * hh);
       pq[ks] = q4;
     }
+    if constexpr (DOCS) pdq = q < Lf ? doc_of<DOCS>(a, b, S, q) : 0;
   };
   if ((int)blockIdx.x < nitems) fetch(blockIdx.x);
 
@@ -124,15 +132,22 @@ void attn_fwd_kernel(AttnArgs a) {
     abf16x8 qf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = __builtin_bit_cast(abf16x8, pq[ks]);
+    const int dq = pdq;
     __syncthreads();
     if (bh + (int)gridDim.x < nitems) fetch(bh + gridDim.x);  // in flight during this item
 
     if (!VARLEN || q0 < L) {
       const bool vq = !VARLEN || q < L;  // a padded query of the partial block: zero q, stores zeros
+      // DOCS: first key block walked, and the last one with a key before some query's document
+      int jlo = 0, jhi = -1;
+      if constexpr (DOCS) {
+        jlo = __builtin_amdgcn_readfirstlane(dq) >> 5;
+        jhi = __builtin_amdgcn_readlane(dq, __builtin_amdgcn_readfirstlane(min(31, L - 1 - q0))) >> 5;
+      }
       af32x16 sc[NW];  // S^T tiles: lane owns query q, keys 32j + acc_row(i)
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w) || (DOCS && j < jlo)) continue;
         sc[j] = zero16();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
@@ -141,6 +156,13 @@ void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
             for (int i = 0; i < 16; ++i)
               if (32 * j + acc_row(i, hh) > q || 32 * j + acc_row(i, hh) >= L) sc[j][i] = -INFINITY;
+          }
+          if constexpr (DOCS) {
+            if (j <= jhi) {  // keys of an earlier document
+#pragma unroll
+              for (int i = 0; i < 16; ++i)
+                if (32 * j + acc_row(i, hh) < dq) sc[j][i] = -INFINITY;
+            }
           }
         } else if constexpr (VARLEN) {
           if (j == nb - 1) {  // the partial key block: keys >= L leave the max and the sum
@@ -153,7 +175,7 @@ void attn_fwd_kernel(AttnArgs a) {
       float m = -INFINITY;
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w) || (DOCS && j < jlo)) continue;
 #pragma unroll
         for (int i = 0; i < 16; ++i) m = fmaxf(m, sc[j][i]);
       }
@@ -161,7 +183,7 @@ void attn_fwd_kernel(AttnArgs a) {
       float l = 0.f;
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w) || (DOCS && j < jlo)) continue;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           sc[j][i] = exp2f((sc[j][i] - m) * sl);
@@ -177,7 +199,7 @@ void attn_fwd_kernel(AttnArgs a) {
       af32x16 ot[2] = {zero16(), zero16()};
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if ((VARLEN && j >= nb) || (CAUSAL && j > w)) continue;
+        if ((VARLEN && j >= nb) || (CAUSAL && j > w) || (DOCS && j < jlo)) continue;
 #pragma unroll
         for (int ks2 = 0; ks2 < 2; ++ks2) {
           float v[8];
@@ -242,9 +264,21 @@ void attn_fwd_kernel(AttnArgs a) {
 // chunks 2 w <= ks < 2 nb, i.e. query blocks w .. nb - 1 of key block w, and phase 3 (query block w)
 // over the key chunks ks < 2 (w + 1) <= 2 nb, i.e. key blocks 0 .. w of query block w: both inside
 // what phase 1 of this item wrote.
-template <int NW, bool VARLEN, bool CAUSAL>
-__global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
+//
+// DOCS (always with CAUSAL): the clamped starts of the valid rows are staged in LDS with the item
+// (doc_s, zeros past L). Key block w is visible to the query blocks w <= t < tend, tend the first t with
+// doc[32 t] > 32 w + 31 (monotone starts: every later block is invisible too), and query block w sees the
+// key blocks jlo = doc[32 w] >> 5 <= j <= w. Phase 1 writes exactly the blocks w <= t < tend with zeros
+// at keys < doc[q]; phase 2 reduces over the query chunks 2 w <= ks < 2 tend and phase 3 over the key
+// chunks 2 jlo <= ks < 2 (w + 1). For a well-formed row t < tend(j) is jlo(t) <= j, so both read only
+// what phase 1 of this item wrote; no skipped block is read.
+// (The document copy asks for two waves per SIMD, as the forward's length-aware copies do: left alone
+// the compiler takes 222 + 64 registers at NW = 2; a minimum of 1 is the default.)
+template <int NW, bool VARLEN, bool CAUSAL, bool DOCS = false>
+__global__ __launch_bounds__(128 * NW) __attribute__((amdgpu_waves_per_eu(DOCS ? 2 : 1)))
+void attn_bwd_kernel(AttnArgs a) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
+  static_assert(CAUSAL || !DOCS, "the document copy is causal");
   constexpr int S = 32 * NW, LDP = S + 8;
   constexpr int NT = 128 * NW;
   constexpr int CH = S * 8 / NT;  // 16-B chunks per lane per tile (= 2)
@@ -259,6 +293,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
   float* lse_s = reinterpret_cast<float*>(dS + S * LDP * 2);
   float* D_s = lse_s + S;
   float* cs_s = D_s + S;  // [NW][3][64] per-key/query-block column sums of dq, dk, dv (bpart)
+  int* doc_s = reinterpret_cast<int*>(cs_s + NW * 3 * 64);  // DOCS: [S] document starts (bwd_lds adds them)
 
   const int lane = threadIdx.x & 63, hh = lane >> 5;
   const int w = threadIdx.x >> 7, sub = (threadIdx.x >> 6) & 1;  // 32-row block, half of its work
@@ -271,7 +306,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
 
   // register prefetch of one item: tile t (Q, K, V, dO, O) chunk i = row c >> 3, 16-B column c & 7
   u32x4 pf[5][CH];
-  float plse = 0.f;
+  float plse = 0.f;  // (DOCS: threads S .. 2 S - 1 carry the document start of row tid - S in it, as int bits)
   auto fetch = [&](int bh) {
     const int b = bh / a.H, h = bh % a.H;
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
@@ -292,6 +327,10 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       }
     }
     if (threadIdx.x < S) plse = (!VARLEN || (int)threadIdx.x < Lf) ? a.lse[(int64_t)bh * S + threadIdx.x] : 0.f;
+    if constexpr (DOCS) {
+      const int r = (int)threadIdx.x - S;
+      if (r >= 0 && r < S) plse = __int_as_float(r < Lf ? doc_of<DOCS>(a, b, S, r) : 0);
+    }
   };
   if ((int)blockIdx.x < nitems) fetch(blockIdx.x);
 
@@ -320,12 +359,24 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       if (ch == 0) D_s[r] = s;
     }
     if (threadIdx.x < S) lse_s[threadIdx.x] = plse;
+    if constexpr (DOCS) {
+      if (threadIdx.x >= S && threadIdx.x < 2 * S) doc_s[threadIdx.x - S] = __float_as_int(plse);
+    }
     __syncthreads();
     if (bh + (int)gridDim.x < nitems) fetch(bh + gridDim.x);  // in flight during this item's phases
 
     // phase 1: waves (w, sub) own keys k0..k0+31; recompute S^T and dP^T against the query blocks
     // t = sub, sub + 2, ...
     const int k0 = 32 * w;
+    // DOCS: query blocks [w, tend) see key block w (tend <= nb)
+    int tend = nb;
+    if constexpr (DOCS) {
+      if (w < nb) {
+#pragma unroll
+        for (int t = NW - 1; t >= 0; --t)
+          if (t >= w && t < nb && __builtin_amdgcn_readfirstlane(doc_s[32 * t]) > k0 + 31) tend = t;
+      }
+    }
     if (!VARLEN || w < nb) {
       abf16x8 kf[4], vf[4];
 #pragma unroll
@@ -335,7 +386,7 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       }
 #pragma unroll
       for (int t = sub; t < NW; t += 2) {
-        if ((VARLEN && t >= nb) || (CAUSAL && t < w)) continue;
+        if ((VARLEN && t >= (DOCS ? tend : nb)) || (CAUSAL && t < w)) continue;
         af32x16 st = zero16(), dpt = zero16();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -344,6 +395,15 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
         }
         const int q = 32 * t + (lane & 31);
         const float lse2 = lse_s[q] * 1.4426950408889634f, Dq = D_s[q];
+        // DOCS: one window test for the three masks below. Query q sees keys doc[q] <= key <= q when
+        // q < L (then key < L too); krel = key - doc[q] of the lane's first key, kspan = q - doc[q], or
+        // -1 (no key) for a padded query, compared as unsigned
+        int krel = 0, kspan = 0;
+        if constexpr (DOCS) {
+          const int dq = doc_s[q];
+          krel = k0 + 4 * hh - dq;
+          kspan = q < L ? q - dq : -1;
+        }
         const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -364,11 +424,15 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
             }
             pv[e] = pd;
             dv[e] = p * (dp - Dq);
-            if constexpr (VARLEN) {  // masked key or padded query: exact zeros into Pd and dS
-              if (q >= L || k0 + 8 * g + 4 * hh + e >= L) pv[e] = dv[e] = 0.f;
-            }
-            if constexpr (CAUSAL) {  // a future key of the diagonal block (t > w has every key <= q)
-              if (k0 + 8 * g + 4 * hh + e > q) pv[e] = dv[e] = 0.f;
+            if constexpr (DOCS) {  // padded query, key of an earlier document or future key: exact zeros
+              if (kspan < 0 || (uint32_t)(krel + 8 * g + e) > (uint32_t)kspan) pv[e] = dv[e] = 0.f;
+            } else {
+              if constexpr (VARLEN) {  // masked key or padded query: exact zeros into Pd and dS
+                if (q >= L || k0 + 8 * g + 4 * hh + e >= L) pv[e] = dv[e] = 0.f;
+              }
+              if constexpr (CAUSAL) {  // a future key of the diagonal block (t > w has every key <= q)
+                if (k0 + 8 * g + 4 * hh + e > q) pv[e] = dv[e] = 0.f;
+              }
             }
           }
           const int off = q * LDP * 2 + (k0 + 8 * g + 4 * hh) * 2;
@@ -387,7 +451,9 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
       af32x16 dv = zero16(), dk = zero16();
 #pragma unroll
       for (int ks = 0; ks < S / 16; ++ks) {
-        if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a key block past L keeps its zeros
+        // a key block past L keeps its zeros (DOCS: tend for nb, the documents that start after the key
+        // block see none of its keys either)
+        if (VARLEN && (w >= nb || ks >= 2 * (DOCS ? tend : nb))) break;
         if (CAUSAL && ks < 2 * w) continue;              // queries before the key block see none of its keys
         dv = mfma(trfrag(Pd, LDP * 2, 16 * ks, k0), trfrag(dOs, LDT * 2, 16 * ks, 32 * dt), dv);
         dk = mfma(trfrag(dS, LDP * 2, 16 * ks, k0), trfrag(Qs, LDT * 2, 16 * ks, 32 * dt), dk);
@@ -416,10 +482,15 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
     {
       const int dt = sub;
       af32x16 dq = zero16();
+      int jlo = 0;  // DOCS: query block w sees key blocks [jlo, w]
+      if constexpr (DOCS) {
+        if (w < nb) jlo = __builtin_amdgcn_readfirstlane(doc_s[32 * w]) >> 5;
+      }
 #pragma unroll
       for (int ks = 0; ks < S / 16; ++ks) {
         if (VARLEN && (w >= nb || ks >= 2 * nb)) break;  // a query block past L keeps its zeros
         if (CAUSAL && ks >= 2 * (w + 1)) break;          // keys after the query block
+        if (DOCS && ks < 2 * jlo) continue;              // keys before the first document of the query block
         dq = mfma(rowfrag(dS, LDP * 2, q0, 16 * ks), trfrag(Ks, LDT * 2, 16 * ks, 32 * dt), dq);
       }
       const int d = 32 * dt + (lane & 31);
@@ -454,44 +525,49 @@ __global__ __launch_bounds__(128 * NW) void attn_bwd_kernel(AttnArgs a) {
 bool attn_supported(int S, int head_dim) { return head_dim == D && S >= 32 && S <= 128 && S % 32 == 0; }
 
 static int fwd_lds(int S) { return 2 * S * LDT * 2; }
-static int bwd_lds(int S) { return 4 * S * LDT * 2 + 2 * S * (S + 8) * 2 + 2 * S * 4 + (S / 32) * 3 * 64 * 4; }
+static int bwd_lds(int S, bool docs) {  // docs: + the [S] document starts
+  return 4 * S * LDT * 2 + 2 * S * (S + 8) * 2 + 2 * S * 4 + (S / 32) * 3 * 64 * 4 + (docs ? S * 4 : 0);
+}
 
-template <int NW, bool VARLEN, bool CAUSAL>
+template <int NW, bool VARLEN, bool CAUSAL, bool DOCS = false>
 static hipError_t launch_fwd_t(const AttnArgs& a, hipStream_t st) {
   const int lds = fwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL, DOCS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items bh, bh + grid, ...
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL>), 64 * NW,
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_kernel<NW, VARLEN, CAUSAL, DOCS>), 64 * NW,
                                                    lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
   int grid = std::min(a.B * a.H, per_cu * cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
-  hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN, CAUSAL>), dim3(grid), dim3(64 * NW), lds, st, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<NW, VARLEN, CAUSAL, DOCS>), dim3(grid), dim3(64 * NW), lds, st, a);
   return hipGetLastError();
 }
-template <int NW, bool VARLEN, bool CAUSAL>
+template <int NW, bool VARLEN, bool CAUSAL, bool DOCS = false>
 static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
-  const int lds = bwd_lds(32 * NW);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW, VARLEN, CAUSAL>),
+  const int lds = bwd_lds(32 * NW, DOCS);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<NW, VARLEN, CAUSAL, DOCS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return e;
   // persistent: one workgroup per CU (the LDS image admits one), each walks items bh, bh + grid, ...
   int grid = std::min(a.B * a.H, cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
-  hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN, CAUSAL>), dim3(grid), dim3(128 * NW), lds, st, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<NW, VARLEN, CAUSAL, DOCS>), dim3(grid), dim3(128 * NW), lds, st, a);
   return hipGetLastError();
 }
 
-// (VARLEN, CAUSAL): full length, lengths, causal (with or without lengths); without a.causal the choice
-// is the one made before the causal copies existed
-#define PSD_ATTN_PICK(fn, nw) \
-  (a.causal ? fn<nw, true, true>(a, st) : a.lens ? fn<nw, true, false>(a, st) : fn<nw, false, false>(a, st))
+// (VARLEN, CAUSAL, DOCS): full length, lengths, causal (with or without lengths), causal with documents;
+// without a.doc the choice is the one made before the document copies existed
+#define PSD_ATTN_PICK(fn, nw)                                                  \
+  (a.doc      ? fn<nw, true, true, true>(a, st)                                \
+   : a.causal ? fn<nw, true, true>(a, st)                                      \
+   : a.lens   ? fn<nw, true, false>(a, st)                                     \
+              : fn<nw, false, false>(a, st))
 
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal)) return hipErrorInvalidValue;
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_fwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_fwd_t, 2);
@@ -500,7 +576,7 @@ hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   }
 }
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D)) return hipErrorInvalidValue;
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal)) return hipErrorInvalidValue;
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_bwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_bwd_t, 2);

@@ -46,6 +46,16 @@
 // tile-major, heaviest first (qt descending for forward / dQ, kt ascending for dK/dV): a workgroup's
 // items it, it + grid, .. then spread over the tiles. Only the item-to-workgroup map changes: every
 // item is still computed whole by one workgroup, so no result depends on it.
+// Documents (DOCS instantiations, a.doc; always causal): query q sees keys doc[q] <= key <= q (and < L);
+// doc is clamped to [0, t] where it is read, only compared, and never read at a position >= L. Forward
+// and dQ start the chunk walk of tile qt at the chunk of its first query's start; a wave computes only
+// in the chunks that overlap [doc[q0], q0 + 31], skips the 32-key blocks that end before doc[q0] and
+// masks keys < doc[q] by element. A wave can then compute a chunk in which some lanes see no key: while
+// a lane's running max is -inf its alpha is 1 and its p is 0, by select (see the forward). dK/dV stops
+// its query-chunk walk at the first chunk whose first query starts past the tile's last key (starts are
+// monotone: so does every later chunk), skips the 32-query blocks whose first query starts past the
+// wave's last key and writes exact zeros where key < doc[query]; the chunk's starts ride in LDS beside
+// lse and D. With a.doc null the launchers pick the copies they picked before.
 // Bias hand-over: bpart[(b * ceil(S/128) + tile)][3*H*64] gets the fp32 column sums of the item's dQ
 // (dQ pass) and dK, dV (dK/dV pass), summed in a fixed order; launch_colsum_final reduces the rows.
 #include <algorithm>
@@ -137,8 +147,10 @@ __device__ __forceinline__ float wave_colsum(float* red, const af32x16 (&t)[2]) 
 }  // namespace
 
 // Forward. Persistent over items (bh, query tile); LDS: K and V chunk tiles, two buffers.
-template <bool VARLEN, bool CAUSAL>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false>
 __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
+  static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
+  static_assert(CAUSAL || !DOCS, "the document copy is causal");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
   const int S = a.S, HD = a.H * D;
@@ -163,22 +175,35 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
     int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;  // key chunks with a valid key; none for a padded tile
     if (CAUSAL) nck = min(nck, 2 * (qt + 1));        // and with a key <= the tile's last query
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
+    // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
+    // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
+    // (a padded query: doc is not read, start 0). (Loading the first chunk index one item ahead, so that
+    // the first K / V fetch does not wait for it, measured 1 % slower forward + backward: not done.)
+    int c0 = 0, dlo = 0, dhi = 0, dq = 0;
+    if constexpr (DOCS) {
+      if (nck > 0) c0 = doc_of<DOCS>(a, b, S, 128 * qt) >> 6;
+      if (vq) dq = doc_of<DOCS>(a, b, S, q);
+      if (live) {
+        dlo = __builtin_amdgcn_readfirstlane(dq);
+        dhi = __builtin_amdgcn_readlane(dq, __builtin_amdgcn_readfirstlane(min(31, L - 1 - q0)));
+      }
+    }
 
     abf16x8 qf[4];
     lane_frags(qf, base + (int64_t)q * qkv_rs, vq, hh);
     u32x4 pk[2], pv[2];
-    if (nck > 0) {
-      fetch_rows(pk, base + HD, qkv_rs, 0, L);
-      fetch_rows(pv, base + 2 * HD, qkv_rs, 0, L);
-      put_rows(smem, pk);
-      put_rows(smem + TILE_B, pv);
+    if (nck > 0) {  // the first chunk walked, into its own buffer
+      fetch_rows(pk, base + HD, qkv_rs, KC * c0, L);
+      fetch_rows(pv, base + 2 * HD, qkv_rs, KC * c0, L);
+      put_rows(smem + (c0 & 1) * 2 * TILE_B, pk);
+      put_rows(smem + (c0 & 1) * 2 * TILE_B + TILE_B, pv);
     }
     __syncthreads();
 
     float m = -INFINITY, l = 0.f;  // l: this lane half's share of the row sum
     af32x16 ot[2] = {zero16(), zero16()};
     const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
-    for (int c = 0; c < nck; ++c) {
+    for (int c = c0; c < nck; ++c) {
       const uint8_t* Ks = smem + (c & 1) * 2 * TILE_B;
       const uint8_t* Vs = Ks + TILE_B;
       const bool more = c + 1 < nck;
@@ -187,7 +212,8 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
       }
       // causal: a wave computes in chunks with 64 c <= q0 only and leaves m, l, ot alone in the others
-      if (live && (!CAUSAL || KC * c <= q0)) {
+      // (documents: nor in a chunk that ends before the start of its first query's document)
+      if (live && (!CAUSAL || KC * c <= q0) && (!DOCS || KC * c + KC - 1 >= dlo)) {
         const int kb0 = KC * c;
         af32x16 sc[2];  // S^T tiles: lane owns query q, keys kb0 + 32 j + acc_row(i)
         float cm = -INFINITY;
@@ -195,14 +221,19 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
           if (CAUSAL && kb0 + 32 * j > q0) continue;  // every key of the block is past the wave's queries
+          if (DOCS && kb0 + 32 * j + 31 < dlo) continue;  // or before the documents of all of them
           // end of the keys this lane's query sees: L, and q + 1 in the block on the diagonal
           const int kend = CAUSAL && kb0 + 32 * j == q0 ? min(L, q + 1) : L;
+          // first key this lane's query sees: its document's start, in the blocks that hold a key before
+          // the largest start of the wave; 0 (no test) elsewhere
+          const int kbeg = DOCS && kb0 + 32 * j < dhi ? dq : 0;
           sc[j] = zero16();
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) sc[j] = mfma(rowfrag(Ks, LDT * 2, 32 * j, 16 * ks), qf[ks], sc[j]);
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             if (VARLEN && kb0 + 32 * j + acc_row(i, hh) >= kend) sc[j][i] = -INFINITY;  // leaves the max and the sum
+            if (DOCS && kb0 + 32 * j + acc_row(i, hh) < kbeg) sc[j][i] = -INFINITY;
             cm = fmaxf(cm, sc[j][i]);
           }
         }
@@ -210,8 +241,16 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         // key kb0 is valid in every chunk walked, so cm is finite; m = -inf on the first chunk gives alpha 0.
         // Causal: per wave, a chunk is computed only when kb0 = 64 c <= q0 (q0 a multiple of 32, 64 c of 64),
         // and then key kb0 <= q0 <= q is visible to every query of the wave and kb0 <= q0 < L: cm stays finite
+        // Documents: a wave computes a chunk in which some lanes see no key (a document that starts inside
+        // the wave's queries: the earlier queries see the chunk before it, the later ones do not). Their m
+        // and cm are both -inf and (m - mn), (s - m) would be NaN: by select, alpha = 1 and p = 0 while the
+        // lane's running max is -inf (l and ot are still zero then). A lane with a finite max takes the
+        // arithmetic above unchanged. A valid query sees itself, so no lane ends with m = -inf.
         const float mn = fmaxf(m, cm);
-        const float alpha = aexp2((m - mn) * sl);
+        float alpha = aexp2((m - mn) * sl);
+        if constexpr (DOCS) {
+          if (mn == -INFINITY) alpha = 1.f;
+        }
         m = mn;
         l *= alpha;
 #pragma unroll
@@ -222,6 +261,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
           if (CAUSAL && kb0 + 32 * j > q0) continue;
+          if (DOCS && kb0 + 32 * j + 31 < dlo) continue;
 #pragma unroll
           for (int ks2 = 0; ks2 < 2; ++ks2) {
             float v[8];
@@ -233,7 +273,10 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const float p = aexp2((sc[j][8 * ks2 + e] - m) * sl);
+              float p = aexp2((sc[j][8 * ks2 + e] - m) * sl);
+              if constexpr (DOCS) {
+                if (m == -INFINITY) p = 0.f;
+              }
               l += p;
               v[e] = p;
               if (drop) v[e] = kp[e] ? p * a.rescale : 0.f;
@@ -265,8 +308,10 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
 }
 
 // Backward, dQ pass: the forward's item and orientation; also writes D = rowsum(dO . O) to dsum.
-template <bool VARLEN, bool CAUSAL>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false>
 __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __restrict__ dsum) {
+  static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
+  static_assert(CAUSAL || !DOCS, "the document copy is causal");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   float* red = reinterpret_cast<float*>(smem);
   float* cs_s = reinterpret_cast<float*>(smem + RED_B);  // [4][64]
@@ -293,6 +338,19 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
     int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;
     if (CAUSAL) nck = min(nck, 2 * (qt + 1));
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
+    // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
+    // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
+    // (a padded query: doc is not read, start 0). (Loading the first chunk index one item ahead, so that
+    // the first K / V fetch does not wait for it, measured 1 % slower forward + backward: not done.)
+    int c0 = 0, dlo = 0, dhi = 0, dq = 0;
+    if constexpr (DOCS) {
+      if (nck > 0) c0 = doc_of<DOCS>(a, b, S, 128 * qt) >> 6;
+      if (vq) dq = doc_of<DOCS>(a, b, S, q);
+      if (live) {
+        dlo = __builtin_amdgcn_readfirstlane(dq);
+        dhi = __builtin_amdgcn_readlane(dq, __builtin_amdgcn_readfirstlane(min(31, L - 1 - q0)));
+      }
+    }
     const int64_t orow = ((int64_t)b * S + q) * HD + h * D;
 
     abf16x8 qf[4], dof[4];
@@ -313,17 +371,17 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
       }
     }
     u32x4 pk[2], pv[2];
-    if (nck > 0) {
-      fetch_rows(pk, base + HD, qkv_rs, 0, L);
-      fetch_rows(pv, base + 2 * HD, qkv_rs, 0, L);
-      put_rows(smem, pk);
-      put_rows(smem + TILE_B, pv);
+    if (nck > 0) {  // the first chunk walked, into its own buffer
+      fetch_rows(pk, base + HD, qkv_rs, KC * c0, L);
+      fetch_rows(pv, base + 2 * HD, qkv_rs, KC * c0, L);
+      put_rows(smem + (c0 & 1) * 2 * TILE_B, pk);
+      put_rows(smem + (c0 & 1) * 2 * TILE_B + TILE_B, pv);
     }
     __syncthreads();
 
     af32x16 dqt[2] = {zero16(), zero16()};  // dQ^T: lane owns query q, d = 32 dt + acc_row(i)
     const uint64_t rowidx = ((uint64_t)bh * S + q) * S;
-    for (int c = 0; c < nck; ++c) {
+    for (int c = c0; c < nck; ++c) {
       const uint8_t* Ks = smem + (c & 1) * 2 * TILE_B;
       const uint8_t* Vs = Ks + TILE_B;
       const bool more = c + 1 < nck;
@@ -331,13 +389,15 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
         fetch_rows(pk, base + HD, qkv_rs, KC * (c + 1), L);
         fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
       }
-      if (live && (!CAUSAL || KC * c <= q0)) {
+      if (live && (!CAUSAL || KC * c <= q0) && (!DOCS || KC * c + KC - 1 >= dlo)) {
         const int kb0 = KC * c;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && kb0 + 32 * j >= L) continue;
           if (CAUSAL && kb0 + 32 * j > q0) continue;  // every key of the block is past the wave's queries
+          if (DOCS && kb0 + 32 * j + 31 < dlo) continue;  // or before the documents of all of them
           const int kend = CAUSAL && kb0 + 32 * j == q0 ? min(L, q + 1) : L;  // as in the forward
+          const int kbeg = DOCS && kb0 + 32 * j < dhi ? dq : 0;
           af32x16 st = zero16(), dpt = zero16();
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
@@ -362,6 +422,9 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
               v[e] = p * (dp - Dq);
               if constexpr (VARLEN) {  // masked key or padded query: exact zero
                 if (!vq || kb0 + 32 * j + acc_row(i, hh) >= kend) v[e] = 0.f;
+              }
+              if constexpr (DOCS) {  // a key of an earlier document
+                if (kb0 + 32 * j + acc_row(i, hh) < kbeg) v[e] = 0.f;
               }
             }
             const abf16x8 dsb = pack8(v);
@@ -395,10 +458,13 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
 
 // Backward, dK/dV pass: item (bh, 128-key tile), the key on the lane. LDS: Q and dO chunk tiles, two
 // buffers, plus the chunk's lse and D.
-template <bool VARLEN, bool CAUSAL>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void attn_long_dkv_kernel(AttnArgs a, const float* __restrict__ dsum) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B + 2 * 2 * KC * 4];
-  float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B);  // [buf][lse, D][64]
+  static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
+  static_assert(CAUSAL || !DOCS, "the document copy is causal");
+  constexpr int NR = DOCS ? 3 : 2;  // per-row values of a chunk: lse, D and (DOCS) the document start
+  __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B + 2 * NR * KC * 4];
+  float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B);  // [buf][lse, D(, doc)][64]
   float* red = reinterpret_cast<float*>(smem);
   float* cs_s = reinterpret_cast<float*>(smem + RED_B);  // [4][2][64]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
@@ -437,13 +503,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
         const int r = KC * c + (threadIdx.x & (KC - 1));
         pr = r < L ? (threadIdx.x < KC ? a.lse : dsum)[(int64_t)bh * S + r] : 0.f;
       }
+      if constexpr (DOCS) {  // the third wave: the chunk's document starts (as int bits; zeros past L)
+        if (threadIdx.x >= 2 * KC && threadIdx.x < 3 * KC) {
+          const int r = KC * c + (threadIdx.x & (KC - 1));
+          pr = __int_as_float(r < L ? doc_of<DOCS>(a, b, S, r) : 0);
+        }
+      }
     };
     auto put = [&](int bf) {
       put_rows(smem + bf * 2 * TILE_B, pq);
       put_rows(smem + bf * 2 * TILE_B + TILE_B, pd);
-      if (threadIdx.x < 2 * KC) row_s[bf * 2 * KC + threadIdx.x] = pr;
+      if (threadIdx.x < NR * KC) row_s[bf * NR * KC + threadIdx.x] = pr;
     };
     const int c0 = CAUSAL ? 2 * kt : 0;  // causal: queries before the key tile see none of it (c0 < nqc when nqc > 0)
+    // DOCS: the walk stops at the first chunk whose first query's document starts past the tile's last
+    // key; monotone starts make every later chunk invisible too. Lane c tests chunk c (at most 8 chunks).
+    int cend = nqc;
+    if constexpr (DOCS) {
+      const bool past = lane >= c0 && lane < nqc && doc_of<DOCS>(a, b, S, KC * lane) > 128 * kt + 127;  // 64 lane < L
+      const uint64_t bal = __ballot(past);
+      if (bal) cend = __ffsll((unsigned long long)bal) - 1;
+    }
     if (nqc > 0) {
       fetch(c0);
       put(c0 & 1);
@@ -451,12 +531,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
     __syncthreads();
 
     af32x16 dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};  // lane owns key kg, d = 32 dt + acc_row(i)
-    for (int c = c0; c < nqc; ++c) {
+    for (int c = c0; c < (DOCS ? cend : nqc); ++c) {
       const uint8_t* Qs = smem + (c & 1) * 2 * TILE_B;
       const uint8_t* dOs = Qs + TILE_B;
-      const float* lse_s = row_s + (c & 1) * 2 * KC;
+      const float* lse_s = row_s + (c & 1) * NR * KC;
       const float* D_s = lse_s + KC;
-      const bool more = c + 1 < nqc;
+      const int* doc_s = reinterpret_cast<const int*>(D_s + KC);  // DOCS only
+      const bool more = c + 1 < (DOCS ? cend : nqc);
       if (more) fetch(c + 1);
       if (live) {
         const int qb0 = KC * c;
@@ -466,6 +547,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
         for (int j = 0; j < 2; ++j) {
           if (VARLEN && qb0 + 32 * j >= L) continue;
           if (CAUSAL && qb0 + 32 * j < k0) continue;  // every query of the block is before the wave's keys
+          if constexpr (DOCS) {  // or its first query's (so every query's) document starts past them
+            if (__builtin_amdgcn_readfirstlane(doc_s[32 * j]) > k0 + 31) continue;
+          }
           const int qfirst = CAUSAL && qb0 + 32 * j == k0 ? kg : 0;  // first query that sees this lane's key
           af32x16 st = zero16(), dpt = zero16();  // S and dP: rows = queries qb0 + 32 j + acc_row(i), col = key kg
 #pragma unroll
@@ -491,6 +575,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
               dv[e] = p * (dp - D_s[ql]);
               if constexpr (VARLEN) {  // masked key or padded query: exact zeros
                 if (!vk || qg >= L || (CAUSAL && qg < qfirst)) pv[e] = dv[e] = 0.f;
+              }
+              if constexpr (DOCS) {  // the key is of an earlier document than the query
+                if (kg < doc_s[ql]) pv[e] = dv[e] = 0.f;
               }
             }
             const abf16x8 pb = pack8(pv), dsb = pack8(dv);
@@ -533,6 +620,7 @@ int attn_long_bpart_rows(int B, int S) { return B * ((S + 127) / 128); }
 
 template <typename K, typename... Extra>
 static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra... extra) {
+  if (a.doc && !a.causal) return hipErrorInvalidValue;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items it, it + grid, ...
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), NT, 0) != hipSuccess || per_cu < 1)
@@ -545,10 +633,11 @@ static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra
   return hipGetLastError();
 }
 
-// (VARLEN, CAUSAL): full length, lengths, causal (with or without lengths); without a.causal the choice
-// is the one made before the causal copies existed
+// (VARLEN, CAUSAL, DOCS): full length, lengths, causal (with or without lengths), causal with documents;
+// without a.doc the choice is the one made before the document copies existed
 #define PSD_ATTN_LONG_PICK(k, ...)                                               \
-  (a.causal ? launch_long(&k<true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)      \
+  (a.doc ? launch_long(&k<true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
+   : a.causal ? launch_long(&k<true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
             : a.lens ? launch_long(&k<true, false>, a, st __VA_OPT__(, ) __VA_ARGS__) \
                      : launch_long(&k<false, false>, a, st __VA_OPT__(, ) __VA_ARGS__))
 

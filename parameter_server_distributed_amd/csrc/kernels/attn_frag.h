@@ -94,6 +94,18 @@ __device__ __forceinline__ int item_len(const AttnArgs& a, int b, int S) {
 }
 __device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
 
+// packed documents (DOCS copies, a.doc given; always causal): first token of the document of token t of
+// sequence b, clamped to [0, t] here on the device. The value is only ever compared with key and query
+// indices, never used as an address; callers pass t < L only, so entries past a length are never read.
+template <bool DOCS>
+__device__ __forceinline__ int doc_of(const AttnArgs& a, int b, int S, int t) {
+  if constexpr (DOCS) {
+    return min(max(a.doc[(int64_t)b * S + t], 0), t);
+  } else {
+    return 0;
+  }
+}
+
 }  // namespace
 
 }  // namespace psd

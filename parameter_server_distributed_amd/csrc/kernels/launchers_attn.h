@@ -23,6 +23,9 @@ struct AttnArgs {
                           // 0 .. clamp(lens[b], 0, S) - 1; read by the kernel only, never by the host
   int32_t grid_cap;       // 0: the launcher's own grid; > 0: at most this many (persistent) workgroups
   int32_t causal;         // != 0: query q sees keys <= q only (and < its length, with lens); the CAUSAL copies
+  const int32_t* doc;     // [B, S] device document starts or null (off); causal only: query q sees keys
+                          // doc[b, q] <= key <= q. Clamped to [0, t] and only compared on the device, entries
+                          // at positions >= the length are never read; the DOCS copies
 };
 bool attn_supported(int S, int head_dim);
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t stream);

@@ -29,12 +29,14 @@ struct LnArgs {
   float p;                // dropout probability (0: identity)
   uint32_t seed;          // per call site
 };
-// BERT's embedding tail y = dropout_p(LayerNorm(W[id] + P[row % S] + T[type])) (kernels/layernorm.hip)
+// BERT's embedding tail y = dropout_p(LayerNorm(W[id] + P[row % S] + T[type])) (kernels/layernorm.hip; with
+// position ids, P[pos[row]]: packed documents restart their positions)
 // and its backward: dx (the gradient of the embedding sum, for the word table's sorted scatter),
 // dgamma / dbeta and -- for <= 2 token types -- the type table's gradient, all from one pass.
 struct EmbLnArgs {
   const int64_t* ids;     // [rows] word ids (outside [0, V): a zero row)
   const int64_t* types;   // [rows] token types (outside [0, NT): a zero row)
+  const int64_t* pos;     // [rows] position ids or null: row r reads P[clamp(pos[r], 0, max_pos - 1)], else P[r % S]
   const uint16_t* W;      // [V, H] word table
   const uint16_t* P;      // [>= S, H] position table (row = row index % S)
   const uint16_t* T;      // [NT, H] token-type table
@@ -53,6 +55,7 @@ struct EmbLnArgs {
   int64_t rows;
   int64_t V;
   int32_t S;
+  int32_t max_pos;        // rows of P
   int32_t NT;
   int32_t H;
   float eps;

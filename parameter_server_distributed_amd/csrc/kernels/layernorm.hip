@@ -318,13 +318,14 @@ struct EmbRows {
 // a row's ids, loaded one row ahead of its gathers (a gather right behind its own id load waits a
 // full memory round trip before it can issue)
 struct EmbIds {
-  int64_t id, ty;
+  int64_t id, ty, ps;
 };
 __device__ __forceinline__ EmbIds emb_ids(const EmbLnArgs& a, int64_t r) {
-  EmbIds o{-1, -1};
+  EmbIds o{-1, -1, 0};
   if (r < a.rows) {
     o.id = a.ids[r];
     o.ty = a.types ? a.types[r] : 0;
+    if (a.pos) o.ps = a.pos[r];  // a runtime branch on a kernel argument: one set of instantiations
   }
   return o;
 }
@@ -334,7 +335,8 @@ __device__ __forceinline__ void emb_fetch(const EmbLnArgs& a, int64_t r, EmbIds 
   constexpr int H = 64 * E;
   const int64_t id = ids.id;
   const int64_t ty = ids.ty;
-  const int64_t s = r % a.S;
+  // position row: the column index, or the given position id clamped into the table
+  const int64_t s = a.pos ? min(max(ids.ps, (int64_t)0), (int64_t)a.max_pos - 1) : r % a.S;
   o.ty = (ty >= 0 && ty < a.NT) ? (int)ty : -1;
   if (id >= 0 && id < a.V) {
     load_e<E>(a.W + id * H + c0, o.w);

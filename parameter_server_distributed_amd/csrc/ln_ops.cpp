@@ -115,7 +115,7 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
 namespace {
 EmbLnArgs emb_args(const at::Tensor& ids, const at::Tensor& types, const at::Tensor& W, const at::Tensor& P,
                    const at::Tensor& T, const at::Tensor& gamma, int64_t S, double p, int64_t seed,
-                   const c10::optional<at::Tensor>& step) {
+                   const c10::optional<at::Tensor>& step, const c10::optional<at::Tensor>& pos) {
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous(), "psd emb ln: ids (int64)");
   TORCH_CHECK(types.is_cuda() && types.scalar_type() == at::kLong && types.is_contiguous() &&
                   types.numel() == ids.numel(),
@@ -133,6 +133,13 @@ EmbLnArgs emb_args(const at::Tensor& ids, const at::Tensor& types, const at::Ten
   EmbLnArgs a{};
   a.ids = ids.data_ptr<int64_t>();
   a.types = types.data_ptr<int64_t>();
+  if (given(pos)) {  // position ids (packed documents): clamped into the table on the device
+    TORCH_CHECK(pos->is_cuda() && pos->scalar_type() == at::kLong && pos->is_contiguous() &&
+                    pos->numel() == ids.numel() && pos->device() == ids.device(),
+                "psd emb ln: pos_ids (int64, like ids)");
+    a.pos = pos->data_ptr<int64_t>();
+  }
+  a.max_pos = (int32_t)P.size(0);
   a.W = cu16(W);
   a.P = cu16(P);
   a.T = cu16(T);
@@ -152,8 +159,8 @@ EmbLnArgs emb_args(const at::Tensor& ids, const at::Tensor& types, const at::Ten
 std::vector<at::Tensor> emb_ln_fwd(const at::Tensor& ids, const at::Tensor& types, const at::Tensor& W,
                                    const at::Tensor& P, const at::Tensor& T, const at::Tensor& gamma,
                                    const at::Tensor& beta, int64_t S, double eps, double p, int64_t seed,
-                                   c10::optional<at::Tensor> step) {
-  EmbLnArgs a = emb_args(ids, types, W, P, T, gamma, S, p, seed, step);
+                                   c10::optional<at::Tensor> step, c10::optional<at::Tensor> pos_ids) {
+  EmbLnArgs a = emb_args(ids, types, W, P, T, gamma, S, p, seed, step, pos_ids);
   check_bf16(beta, "beta");
   TORCH_CHECK(beta.numel() == a.H, "psd emb ln: beta");
   const c10::DeviceGuard g(W.device());
@@ -175,8 +182,8 @@ std::vector<at::Tensor> emb_ln_bwd(const at::Tensor& dy_in, const at::Tensor& id
                                    const at::Tensor& gamma, const at::Tensor& mean, const at::Tensor& rstd, int64_t S,
                                    double p, int64_t seed, c10::optional<at::Tensor> step,
                                    c10::optional<at::Tensor> dgamma_out, c10::optional<at::Tensor> dbeta_out,
-                                   c10::optional<at::Tensor> dT_out) {
-  EmbLnArgs a = emb_args(ids, types, W, P, T, gamma, S, p, seed, step);
+                                   c10::optional<at::Tensor> dT_out, c10::optional<at::Tensor> pos_ids) {
+  EmbLnArgs a = emb_args(ids, types, W, P, T, gamma, S, p, seed, step, pos_ids);
   at::Tensor dy = dy_in.contiguous();
   check_bf16(dy, "dy");
   TORCH_CHECK(dy.numel() == a.rows * a.H && mean.numel() == a.rows && rstd.numel() == a.rows &&

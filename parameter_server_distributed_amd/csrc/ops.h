@@ -200,11 +200,11 @@ std::vector<at::Tensor> stem_fwd(const at::Tensor& x, const at::Tensor& w, const
 at::Tensor stem_wgrad(const at::Tensor& x, const at::Tensor& dy);
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal);
+                                 bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt);
 at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal);
+                    bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt);
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
                                double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
                                c10::optional<at::Tensor> q8_out = c10::nullopt,
@@ -216,13 +216,13 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy, const at::Tensor& s, const 
 std::vector<at::Tensor> emb_ln_fwd(const at::Tensor& ids, const at::Tensor& types, const at::Tensor& W,
                                    const at::Tensor& P, const at::Tensor& T, const at::Tensor& gamma,
                                    const at::Tensor& beta, int64_t S, double eps, double p, int64_t seed,
-                                   c10::optional<at::Tensor> step);
+                                   c10::optional<at::Tensor> step, c10::optional<at::Tensor> pos_ids = c10::nullopt);
 std::vector<at::Tensor> emb_ln_bwd(const at::Tensor& dy, const at::Tensor& ids, const at::Tensor& types,
                                    const at::Tensor& W, const at::Tensor& P, const at::Tensor& T,
                                    const at::Tensor& gamma, const at::Tensor& mean, const at::Tensor& rstd, int64_t S,
                                    double p, int64_t seed, c10::optional<at::Tensor> step,
                                    c10::optional<at::Tensor> dgamma_out, c10::optional<at::Tensor> dbeta_out,
-                                   c10::optional<at::Tensor> dT_out);
+                                   c10::optional<at::Tensor> dT_out, c10::optional<at::Tensor> pos_ids = c10::nullopt);
 std::vector<at::Tensor> bn_pool_bwd(const at::Tensor& gpool, c10::optional<at::Tensor> gpool2, const at::Tensor& arg,
                                     const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& save_mean,
                                     const at::Tensor& save_invstd, const at::Tensor& ss,

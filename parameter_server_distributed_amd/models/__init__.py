@@ -101,9 +101,10 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
         m = prepare(GPTForLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
                              max_pos=max(512, seq), fp8=bool(kw.get("fp8", False))), device, dtype)
         min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
+        pack = kw.get("pack_docs")  # (lo, hi): rows packed with documents of lengths in [lo, hi]
 
         def make(batch, device, seed=0):
-            return gpt_batch(batch, seq, m.vocab, device, seed, min_len=min_len)
+            return gpt_batch(batch, seq, m.vocab, device, seed, min_len=min_len, docs=pack)
 
         return ModelSpec("gpt_small", m, make, m.loss, "sequences")
     raise KeyError(f"unknown model {name!r}; available: {MODELS}")

@@ -48,10 +48,11 @@ class BertLayer(nn.Module):
             self.ln1.psd_mx_output_to(self.ffn1)
         self.p = dropout
 
-    def forward(self, x, lens=None):
+    def forward(self, x, lens=None, doc_start=None):
         # each residual LayerNorm hands the gradient of its x input to the Linear that also reads x
         # (folded into that Linear's bwd-data GEMM, ops/layernorm.py)
-        x = self.ln1(x, self.proj(self.attn(self.qkv(x), lens)), x_grad_to=self.qkv)
+        # doc_start: packed documents (ops/attention.py), passed on to the attention
+        x = self.ln1(x, self.proj(self.attn(self.qkv(x), lens, doc_start)), x_grad_to=self.qkv)
         return self.ln2(x, self.ffn2(self.ffn1(x)), x_grad_to=self.ffn1)
 
 

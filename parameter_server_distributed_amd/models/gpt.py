@@ -47,13 +47,19 @@ class GPTForLM(nn.Module):
 
     def forward(self, batch):
         # (ids,) or, for a padded batch, (ids, lens): int32 [B] lengths, positions >= lens[b] are padding
-        # that no attention key or query row reads. Logits of every position: [B*S, vocab]
+        # that no attention key or query row reads. Packed documents: (ids, lens, doc_start), doc_start
+        # int32 [B, S] (ops/attention.py): a token attends inside its own document only and its position
+        # id restarts there, t - doc_start[b, t]. Logits of every position: [B*S, vocab]
         ids = batch[0]
         lens = batch[1] if len(batch) > 1 else None
+        doc_start = batch[2] if len(batch) > 2 else None
         bump_step(self)
-        x = self.emb(ids, torch.zeros_like(ids))
+        pos_ids = None
+        if doc_start is not None:
+            pos_ids = torch.arange(ids.shape[1], device=ids.device)[None, :] - doc_start.long()
+        x = self.emb(ids, torch.zeros_like(ids), pos_ids)
         for layer in self.layers:
-            x = layer(x, lens)
+            x = layer(x, lens, doc_start)
         return self.head(x.reshape(-1, x.shape[-1]))
 
     @staticmethod
@@ -61,15 +67,45 @@ class GPTForLM(nn.Module):
         return cross_entropy(logits, labels)  # fused bf16 softmax-CE kernels (ops/loss.py)
 
 
-def gpt_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, min_len: int | None = None):
+def gpt_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, min_len: int | None = None,
+              docs: tuple[int, int] | None = None):
     """Synthetic language-model batch: random ids and the next-token labels ``[B*S]``,
     ``labels[b, s] = ids[b, s + 1]``; the last position has no next token and gets -100, which the loss
     ignores.
 
     With ``min_len`` the sequences are padded: lengths are uniform in [min_len, seq], ids past a length
-    are 0, every position ``s >= L - 1`` gets label -100 and the batch tuple gains ``lens`` (int32 [B])."""
+    are 0, every position ``s >= L - 1`` gets label -100 and the batch tuple gains ``lens`` (int32 [B]).
+
+    With ``docs=(lo, hi)`` every row is packed with documents of length uniform in [lo, hi], laid end to
+    end; the last one is cut at ``seq``. No label crosses a boundary: each document's last token gets
+    -100. Returns ``((ids, lens, doc_start), labels)`` with ``lens`` full and ``doc_start`` int32 [B, S]
+    (ops/attention.doc_starts). Not with ``min_len``."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     ids = torch.randint(0, vocab, (batch, seq), generator=g)
+    if docs is not None:
+        if min_len is not None:
+            raise ValueError("gpt_batch: docs (packed rows) cannot be combined with min_len (padded rows)")
+        lo, hi = int(docs[0]), int(docs[1])
+        if not 1 <= lo <= hi:
+            raise ValueError(f"docs must be (lo, hi) with 1 <= lo <= hi, got {docs}")
+        from ..ops.attention import doc_starts
+
+        rows = []
+        for _ in range(batch):
+            row, t = [], 0
+            while t < seq:
+                n = min(int(torch.randint(lo, hi + 1, (1,), generator=g)), seq - t)
+                row.append(n)
+                t += n
+            rows.append(row)
+        ds = doc_starts(rows, seq)
+        labels = torch.full((batch, seq), -100, dtype=torch.long)
+        labels[:, :-1] = ids[:, 1:]
+        last = torch.ones(batch, seq, dtype=torch.bool)  # a document's last token: the next one starts anew
+        last[:, :-1] = ds[:, 1:] != ds[:, :-1]
+        labels[last] = -100
+        lens = torch.full((batch,), seq, dtype=torch.int32)
+        return (ids.to(device), lens.to(device), ds.to(device)), labels.reshape(-1).to(device)
     if min_len is None:
         lens = torch.full((batch,), seq, dtype=torch.long)
     else:

@@ -25,8 +25,18 @@ the diagonal; the dropout hash index is unchanged, so the kept set is the same m
 ``k <= q``. Rows ``<= j`` of the output do not depend on rows ``> j`` of a finite qkv; future rows inside
 a diagonal block are loaded, so -- unlike padding -- NaN or inf there is not covered.
 
+Packed documents pass ``doc_start`` (int32 ``[B, S]`` on qkv's device, ``doc_starts`` builds it):
+``doc_start[b, t]`` is the index of the first token of the document token ``t`` belongs to. With
+``causal=True`` query ``q`` sees key ``k`` iff both are of one document, ``k <= q`` and ``k < lens[b]`` --
+for a well-formed row ``doc_start[b, q] <= k <= q``. The document copies of both kernel families skip
+the 32-row blocks of other documents; entries at positions past a length are never read, the values
+are clamped to ``[0, t]`` and only compared on the device. All zeros is bitwise the plain causal call.
+With ``causal=False`` the kernels do not serve a ``doc_start``: the module then takes SDPA with the
+symmetric same-document mask, and the native op raises. Arbitrary masks are not supported.
+
 CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128, 192, 256, 320, 384, 448, 512}
-use SDPA -- the reference the tests compare against -- with the same length and causal semantics.
+use SDPA -- the reference the tests compare against -- with the same length, causal and document
+semantics.
 """
 from __future__ import annotations
 
@@ -39,17 +49,50 @@ from ..utils.config import feature as _feat
 from .. import native
 
 
+def doc_starts(doc_lens, S: int, device=None) -> torch.Tensor:
+    """``doc_start`` (int32 ``[B, S]``) from per-row lists of document lengths, laid end to end from
+    position 0. A row's documents may sum to less than ``S``: every remaining position is padding and
+    gets its own index (a one-token document). Lengths must be positive and sum to at most ``S``."""
+    out = torch.arange(S, dtype=torch.int32).repeat(len(doc_lens), 1)
+    for b, row in enumerate(doc_lens):
+        t = 0
+        for n in row:
+            n = int(n)
+            if n < 1 or t + n > S:
+                raise ValueError(f"row {b}: document lengths {list(row)} do not fit {S} positions")
+            out[b, t:t + n] = t
+            t += n
+    return out.to(device) if device is not None else out
+
+
+def check_doc_start(t: torch.Tensor) -> None:
+    """Raise ``ValueError`` unless ``t`` is a well-formed ``doc_start``: int32 ``[B, S]``, every row
+    non-decreasing, ``t[b, i] <= i`` (and >= 0) and ``t[b, t[b, i]] == t[b, i]``. Reads the tensor back
+    (a device sync): for tests and debugging, never on the hot path."""
+    if t.dim() != 2 or t.dtype != torch.int32:
+        raise ValueError(f"doc_start must be an int32 [B, S] tensor, got {t.dtype} {tuple(t.shape)}")
+    v = t.long()
+    S = v.shape[1]
+    idx = torch.arange(S, device=v.device)[None, :]
+    if S and bool((v[:, 1:] < v[:, :-1]).any()):
+        raise ValueError("doc_start: a row is not non-decreasing")
+    if bool(((v < 0) | (v > idx)).any()):
+        raise ValueError("doc_start: an entry is outside [0, t]")
+    if not torch.equal(torch.gather(v, 1, v), v):
+        raise ValueError("doc_start: doc_start[doc_start[t]] != doc_start[t] (a start that is not its own start)")
+
+
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, mod, p, lens=None):
+    def forward(ctx, qkv, mod, p, lens=None, doc_start=None):
         # qkv straight from an MfmaLinear with a bias (ops/linear.py tags its output): backward also
         # sums dqkv's columns -- that Linear's bias gradient -- and hands it over
         src = getattr(qkv, "_psd_src", None) if _feat("attn_bias") else None
         ctx.src = src if (src is not None and src[0].bias is not None and src[0].act in (None, "none")
                           and src[0]._psd_tok == src[1]) else None
         qkv = qkv.contiguous()
-        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens, 0, mod.causal)
-        ctx.mod, ctx.p, ctx.lens = mod, p, lens
+        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens, 0, mod.causal, doc_start)
+        ctx.mod, ctx.p, ctx.lens, ctx.doc = mod, p, lens, doc_start
         ctx.save_for_backward(qkv, o, lse)
         return o
 
@@ -64,15 +107,19 @@ class _AttnFn(torch.autograd.Function):
             db = sink(lin.bias) if sink is not None else None
             if db is None:
                 db = torch.empty_like(lin.bias)
-        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens, 0, mod.causal)
+        dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens, 0, mod.causal,
+                                 ctx.doc)
         if db is not None:
             ctx.src[0]._psd_bias_hand = (ctx.src[1], dqkv.data_ptr(), db)
-        return dqkv, None, None, None
+        return dqkv, None, None, None, None
 
 
 class FusedSelfAttention(nn.Module):
     """softmax(Q K^T / sqrt(d)) V with dropout on the probabilities, from the packed QKV tensor;
-    ``causal``: query q sees keys <= q only."""
+    ``causal``: query q sees keys <= q only. ``forward(qkv, lens=None, doc_start=None)``: with a
+    ``doc_start`` (packed documents, module docstring) a causal module runs the document copies of the
+    kernels at the kernel shapes; a bidirectional one has no kernel for it and takes SDPA with the
+    symmetric same-document mask."""
 
     def __init__(self, heads: int, p: float = 0.1, seed: int = 0, causal: bool = False):
         super().__init__()
@@ -97,20 +144,22 @@ class FusedSelfAttention(nn.Module):
         return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0
                 and self.long_kernel_shape_ok(S, E // (3 * self.heads)) and _feat("attn_long"))
 
-    def forward(self, qkv, lens=None):
+    def forward(self, qkv, lens=None, doc_start=None):
         p = self.p if self.training else 0.0
-        if self._kernel_ok(qkv) or self._long_kernel_ok(qkv):
-            return _AttnFn.apply(qkv, self, p, lens)
-        return self._sdpa(qkv, lens, p)
+        if (doc_start is None or self.causal) and (self._kernel_ok(qkv) or self._long_kernel_ok(qkv)):
+            return _AttnFn.apply(qkv, self, p, lens, doc_start)
+        return self._sdpa(qkv, lens, p, doc_start)
 
-    def _sdpa(self, qkv, lens, p):
+    def _sdpa(self, qkv, lens, p, doc_start=None):
         """``F.scaled_dot_product_attention`` on transposed views (what no kernel takes; tools/attn_bench.py --sdpa)."""
         B, S, E = qkv.shape
         H = self.heads
         q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)
-        if lens is None:
+        if lens is None and doc_start is None:
             a = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=self.causal)
             return a.transpose(1, 2).reshape(B, S, E // 3)
+        if lens is None:
+            lens = torch.full((B,), S, dtype=torch.int32, device=qkv.device)
         valid = torch.arange(S, device=qkv.device)[None, :] < lens.clamp(0, S)[:, None]  # [B, S]
         row = valid[:, None, :, None]
         # padded rows never enter a product (where, not a multiply: 0 * NaN = NaN)
@@ -120,5 +169,8 @@ class FusedSelfAttention(nn.Module):
         mask = valid[:, None, None, :] | ~row
         if self.causal:  # key <= q and key < L; a padded query keeps key 0, so its row stays finite
             mask = mask & torch.ones(S, S, dtype=torch.bool, device=qkv.device).tril()
+        if doc_start is not None:  # valid queries see their own document only; padded ones stay as they were
+            same = doc_start[:, None, :, None] == doc_start[:, None, None, :]
+            mask = mask & (same | ~row)
         a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p) * row.to(q.dtype)
         return a.transpose(1, 2).reshape(B, S, E // 3)

@@ -79,13 +79,15 @@ def _bert_emb_kernel_ok(mod, ids, types) -> bool:
 
 class _BertEmbLNFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, types, w, pt, tt, gamma, beta, mod, p):
+    def forward(ctx, ids, types, w, pt, tt, gamma, beta, mod, p, pos_ids=None):
         B, S = ids.shape
         ids_f, types_f = ids.reshape(-1).contiguous(), types.reshape(-1).contiguous()
+        if pos_ids is not None:
+            pos_ids = pos_ids.reshape(-1).contiguous()
         y, mean, rstd = native().emb_ln_fwd(ids_f, types_f, w, pt, tt, gamma, beta, S, mod.ln.eps, p, mod.seed,
-                                            mod.step)
+                                            mod.step, pos_ids)
         ctx.save_for_backward(ids_f, types_f, mean, rstd)
-        ctx.mod, ctx.p, ctx.S = mod, p, S
+        ctx.mod, ctx.p, ctx.S, ctx.pos_ids = mod, p, S, pos_ids
         return y.view(B, S, -1)
 
     @staticmethod
@@ -103,7 +105,7 @@ class _BertEmbLNFn(torch.autograd.Function):
         dT = out(tt) if tt.shape[0] <= 2 else None
         H = w.shape[1]
         dx, dg, db, dT = native().emb_ln_bwd(dy.reshape(-1, H), ids, types, w, pt, tt, mod.ln.weight, mean, rstd,
-                                             ctx.S, ctx.p, mod.seed, mod.step, dgo, dbo, dT)
+                                             ctx.S, ctx.p, mod.seed, mod.step, dgo, dbo, dT, ctx.pos_ids)
         if dT is None:  # > 2 token types: one-hot GEMM as FusedEmbedding's small-vocabulary path
             dT = out(tt)
             torch.mm(F.one_hot(types, tt.shape[0]).to(dx.dtype).t(), dx, out=dT)
@@ -112,13 +114,19 @@ class _BertEmbLNFn(torch.autograd.Function):
         s, perm = torch.sort(ids, stable=True)
         dW.zero_()
         native().embed_bwd_(s, perm, dx, dW)
-        # position table: rows [0, S) take the batch sum, the rest none
         dP = out(pt)
+        if ctx.pos_ids is not None:
+            # position ids: the word table's sorted scatter, over the ids the kernel read (clamped)
+            s, perm = torch.sort(ctx.pos_ids.clamp(0, pt.shape[0] - 1), stable=True)
+            dP.zero_()
+            native().embed_bwd_(s, perm, dx, dP)
+            return None, None, dW, dP, dT, dg, db, None, None, None
+        # position table: rows [0, S) take the batch sum, the rest none
         S = ctx.S
         dP[:S].copy_(torch.sum(dx.view(-1, S, H), 0, dtype=torch.float32))
         if S < dP.shape[0]:
             dP[S:].zero_()
-        return None, None, dW, dP, dT, dg, db, None, None
+        return None, None, dW, dP, dT, dg, db, None, None, None
 
 
 class FusedBertEmbeddings(nn.Module):
@@ -128,7 +136,10 @@ class FusedBertEmbeddings(nn.Module):
     embedding-sum gradient once for the word table's deterministic sorted scatter, the position
     table's batch sum and -- in the same pass -- the type rows' and LayerNorm's parameter gradients.
     Off-GPU / off-shape: the composite of nn.Embedding, nn.LayerNorm and F.dropout (the tests'
-    reference). ``step``: the owning model's device dropout counter (layernorm.bump_step)."""
+    reference). ``step``: the owning model's device dropout counter (layernorm.bump_step).
+    ``forward(ids, types, pos_ids=None)``: ``pos_ids`` (int64 ``[B, S]``) replaces the column index as
+    the position of each token (packed documents restart at 0); the kernels clamp it into the table and
+    the position table's gradient becomes the word table's deterministic sorted scatter."""
 
     def __init__(self, vocab: int, hidden: int, max_pos: int = 512, type_vocab: int = 2, eps: float = 1e-12,
                  p: float = 0.1, seed: int = 0):
@@ -144,13 +155,15 @@ class FusedBertEmbeddings(nn.Module):
     def psd_direct_grad_params(self):
         return [self.word.weight, self.pos.weight, self.tok_type.weight, self.ln.weight, self.ln.bias]
 
-    def forward(self, ids, types):
+    def forward(self, ids, types, pos_ids=None):
         p = self.p if self.training else 0.0
         if (torch.is_grad_enabled() and any(x.requires_grad for x in self.parameters())
-                and _bert_emb_kernel_ok(self, ids, types)):
+                and _bert_emb_kernel_ok(self, ids, types)
+                and (pos_ids is None or (pos_ids.dtype == torch.long and pos_ids.shape == ids.shape
+                                         and pos_ids.device == ids.device))):
             return _BertEmbLNFn.apply(ids, types, self.word.weight, self.pos.weight, self.tok_type.weight,
-                                      self.ln.weight, self.ln.bias, self, p)
-        S = ids.shape[1]
-        pos = torch.arange(S, device=ids.device)
-        x = self.word(ids) + self.pos(pos)[None] + self.tok_type(types)
+                                      self.ln.weight, self.ln.bias, self, p, pos_ids)
+        if pos_ids is None:
+            pos_ids = torch.arange(ids.shape[1], device=ids.device)[None]
+        x = self.word(ids) + self.pos(pos_ids) + self.tok_type(types)
         return F.dropout(self.ln(x), p, self.training)

@@ -7,10 +7,14 @@ default shape is BERT-base pre-training (B 256, S 128, 12 heads of 64).
   python tools/attn_bench.py --min-len 16   # padded batch: lengths uniform in [16, S], passed as lens
   python tools/attn_bench.py --seq 512 --batch 64 --sdpa   # the streaming kernels against the SDPA path
   python tools/attn_bench.py --seq 512 --batch 64 --causal # the causal instantiations (keys <= q)
+  python tools/attn_bench.py --seq 512 --batch 64 --docs 128 --sdpa  # packed documents of mean length 128
 
 With --min-len the bytes count the valid rows only (what the variable-length kernels have to move)
 and the FLOP rate counts the valid (query, key) pairs. With --causal the FLOP rate counts the visible
-pairs (key <= q, and both < the length); the bytes are unchanged.
+pairs (key <= q, and both < the length); the bytes are unchanged. --docs MEAN (causal only) packs every
+row with documents of length uniform in [MEAN/2, 3 MEAN/2] (seeded) and passes doc_start: the document
+copies of the kernels, and with --sdpa the SDPA path with the same boolean mask; the FLOP rate counts
+the visible pairs (same document, key <= q).
 
 --sdpa also times the module's SDPA path (F.scaled_dot_product_attention on transposed views, through
 autograd, with its layout copies and, with lengths, its mask) on the same data as a second pair of
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="batch size B")
     ap.add_argument("--sdpa", action="store_true", help="also time the module's SDPA path on the same data")
     ap.add_argument("--causal", action="store_true", help="causal mask (keys <= q), on both paths")
+    ap.add_argument("--docs", type=int, default=None,
+                    help="pack rows with documents of this mean length and pass doc_start (needs --causal)")
     ap.add_argument("--windows", type=int, default=None, help="timing windows per figure (default 1, with --sdpa 5)")
     args = ap.parse_args()
     C = native()
@@ -75,6 +81,26 @@ def main():
         el = int(lc.sum()) * H * D * 2  # the valid rows only
         flop_f = 4 * H * D * int((lc * (lc + 1) // 2 if causal else lc * lc).sum())
         print(f"lens uniform in [{args.min_len}, {S}]: mean {lc.float().mean():.1f}, valid rows {int(lc.sum())} of {B * S}")
+    extra = ()  # (doc_start,) with --docs: the last argument of attn_fwd / attn_bwd and of _sdpa
+    if args.docs is not None:
+        if not causal or args.docs < 2 or args.min_len is not None:
+            ap.error("--docs MEAN needs --causal, MEAN >= 2 and no --min-len")
+        from parameter_server_distributed_amd.ops.attention import doc_starts
+
+        g = torch.Generator(device="cpu").manual_seed(0)
+        rows = []
+        for _ in range(B):
+            row, t = [], 0
+            while t < S:
+                n = min(int(torch.randint(args.docs // 2, args.docs * 3 // 2 + 1, (1,), generator=g)), S - t)
+                row.append(n)
+                t += n
+            rows.append(row)
+        extra = (doc_starts(rows, S, dev),)
+        ndoc = sum(len(r) for r in rows)
+        flop_f = 4 * H * D * sum(n * (n + 1) // 2 for r in rows for n in r)
+        print(f"documents uniform in [{args.docs // 2}, {args.docs * 3 // 2}]: {ndoc / B:.1f} per row, "
+              f"mean length {B * S / ndoc:.1f}")
     it = args.iters
     print(f"B {B}, S {S}, H {H}, D {D}{', causal' if causal else ''}; {nwin} window(s) of {it} calls")
     head = "| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |"
@@ -87,15 +113,15 @@ def main():
     print(head)
     print("|" + "---:|" * (head.count("|") - 1))
     for p in (0.0, 0.1):
-        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal)
+        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra)
         tf, tb, sf, sb = [], [], [], []
         for _ in range(nwin):  # the paths alternate inside a window
-            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal), it))
+            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra), it))
             if args.sdpa:
-                sf.append(t_us(lambda: mod._sdpa(xg, lens, p), it))
-            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens, 0, causal), it))
+                sf.append(t_us(lambda: mod._sdpa(xg, lens, p, *extra), it))
+            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens, 0, causal, *extra), it))
             if args.sdpa:
-                so = mod._sdpa(xg, lens, p)
+                so = mod._sdpa(xg, lens, p, *extra)
                 sb.append(t_us(lambda: torch.autograd.grad(so, xg, do, retain_graph=True), it))
                 del so
         mf, mb = statistics.median(tf), statistics.median(tb)
