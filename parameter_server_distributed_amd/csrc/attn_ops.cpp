@@ -1,8 +1,9 @@
 // Tensor glue for the fused self-attention kernels: kernels/attention.hip (S <= 128, the whole head in
-// LDS) and kernels/attention_long.hip (128 < S <= 512, streaming); attn_fwd / attn_bwd dispatch on S.
+// LDS) and kernels/attention_long.hip (128 < S <= 4096, streaming); attn_fwd / attn_bwd dispatch on S.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -18,18 +19,26 @@ void check_docs(const c10::optional<at::Tensor>& doc_start, bool causal) {
   TORCH_CHECK(!given(doc_start) || causal,
               "psd attn: doc_start needs causal=True (the kernels do not serve bidirectional packing)");
 }
+// a sliding window (window = W >= 1 keys, the query's own included) is causal; 0 is off (also checked first)
+void check_window(int64_t window, bool causal) {
+  TORCH_CHECK(window >= 0, "psd attn: window must be >= 0 (0: off), got ", window);
+  TORCH_CHECK(window == 0 || causal, "psd attn: window needs causal=True (the kernels serve no symmetric window)");
+}
 void check_attn(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd attn: ", what,
               " must be a contiguous bf16 device tensor");
 }
 AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed, const c10::optional<at::Tensor>& step,
                    const c10::optional<at::Tensor>& lens, int64_t grid_cap, bool causal,
-                   const c10::optional<at::Tensor>& doc_start) {
+                   const c10::optional<at::Tensor>& doc_start, int64_t window) {
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
   const int64_t dh = qkv.size(2) / (3 * heads);
   TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh) || attn_long_supported((int)qkv.size(1), (int)dh),
-              "psd attn: needs head dim 64 and S in {32, 64, 96, 128} (whole-head kernels) or in "
-              "{192, 256, 320, 384, 448, 512} (streaming kernels)");
+              "psd attn: needs head dim 64 and S in {32, 64, 96, 128} (whole-head kernels) or a multiple of 64 in "
+              "192 .. 4096 (streaming kernels)");
+  TORCH_CHECK(window == 0 || attn_long_supported((int)qkv.size(1), (int)dh),
+              "psd attn: window is served by the streaming kernels only (S a multiple of 64 in 192 .. 4096), got S = ",
+              qkv.size(1));
   TORCH_CHECK(p >= 0.0 && p < 1.0, "psd attn: dropout p must be in [0, 1)");
   AttnArgs a{};
   a.qkv = reinterpret_cast<const uint16_t*>(qkv.data_ptr());
@@ -57,17 +66,20 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                 "psd attn: doc_start must be a contiguous int32 [B, S] tensor on qkv's device");
     a.doc = doc_start->data_ptr<int32_t>();
   }
+  // window > 0 always takes the WINDOW copies; W >= S is the plain causal / document mask, so S stands for more
+  a.window = (int32_t)std::min<int64_t>(window, qkv.size(1));
   return a;
 }
 }  // namespace
 
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal, c10::optional<at::Tensor> doc_start) {
+                                 bool causal, c10::optional<at::Tensor> doc_start, int64_t window) {
   check_docs(doc_start, causal);
+  check_window(window, causal);
   check_attn(qkv, "qkv");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window);
   at::Tensor o = at::empty({qkv.size(0), qkv.size(1), qkv.size(2) / 3}, qkv.options());
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
@@ -84,18 +96,19 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
 // sums hold).
 // lens (optional, int32 [B]): valid rows per sequence; grid_cap > 0 bounds the persistent grid (tests);
 // causal: the mask the forward used (keys <= q); doc_start (optional, int32 [B, S], causal only): the
-// document starts the forward used (keys doc_start[b, q] <= key <= q).
+// document starts the forward used (keys doc_start[b, q] <= key <= q); window: the forward's window.
 at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal, c10::optional<at::Tensor> doc_start) {
+                    bool causal, c10::optional<at::Tensor> doc_start, int64_t window) {
   check_docs(doc_start, causal);
+  check_window(window, causal);
   at::Tensor dout = dout_in.contiguous();
   check_attn(dout, "dout");
   check_attn(qkv, "qkv");
   check_attn(o, "o");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start);
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window);
   TORCH_CHECK(o.sizes() == dout.sizes() && o.size(0) == qkv.size(0) && o.size(1) == qkv.size(1) &&
                   o.size(2) * 3 == qkv.size(2),
               "psd attn bwd: o / dout must be [B, S, H*Dh]");

@@ -179,11 +179,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("stem_wgrad", &stem_wgrad);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
         py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
-        py::arg("doc_start") = py::none());
+        py::arg("doc_start") = py::none(), py::arg("window") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("heads"),
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
         py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
-        py::arg("doc_start") = py::none());
+        py::arg("doc_start") = py::none(), py::arg("window") = 0);
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
         py::arg("sc8_out") = py::none());

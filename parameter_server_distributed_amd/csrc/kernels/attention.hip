@@ -567,7 +567,7 @@ static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
               : fn<nw, false, false>(a, st))
 
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D) || (a.doc && !a.causal)) return hipErrorInvalidValue;
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window) return hipErrorInvalidValue;  // no window copies here
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_fwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_fwd_t, 2);
@@ -576,7 +576,7 @@ hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   }
 }
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D) || (a.doc && !a.causal)) return hipErrorInvalidValue;
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window) return hipErrorInvalidValue;  // no window copies here
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_bwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_bwd_t, 2);

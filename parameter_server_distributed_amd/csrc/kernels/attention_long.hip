@@ -1,10 +1,13 @@
-// Fused multi-head self-attention for sequences of 192 to 512 tokens (128 < S <= 512, S % 64 == 0,
+// Fused multi-head self-attention for sequences of 192 to 4096 tokens (128 < S <= 4096, S % 64 == 0,
 // head dim 64, bf16) on gfx950: streaming (flash-style) forward and backward with the contracts of the
 // whole-head kernels in attention.hip -- packed QKV [B, S, 3, H, 64] in, O [B, S, H, 64] and the
 // packed dQKV out, the row log-sum-exp, per-sequence lengths, the counter-hash dropout mask, the
 // QKV-bias partial sums and grid_cap.
 //
-// The whole head no longer fits LDS (K and V alone are 147 KB at S = 512), so every kernel here keeps
+// The whole head no longer fits LDS (K and V alone are 147 KB at S = 512), and nothing below is sized by
+// S: LDS holds two 64-row chunks whatever the length, every row, pair and partial index is 64-bit, and
+// the one S-bound structure is the 64-lane ballot over chunks in the dK/dV document walk (S <= 4096,
+// attn_long_supported). Every kernel here keeps
 // one operand set in registers, streams the other through LDS in 64-row chunks (register-staged,
 // double-buffered, one barrier per chunk) and holds all score-sized data in accumulators. Three
 // forward-shaped kernels, every product a v_mfma_f32_32x32x16_bf16:
@@ -56,6 +59,18 @@
 // monotone: so does every later chunk), skips the 32-query blocks whose first query starts past the
 // wave's last key and writes exact zeros where key < doc[query]; the chunk's starts ride in LDS beside
 // lse and D. With a.doc null the launchers pick the copies they picked before.
+// Windows (WINDOW instantiations, a.window = W >= 1; always causal, with or without a.doc -- they test
+// the pointer as the causal copies test a.lens): query q sees keys lb(q) <= key <= q (and < L) with
+// lb(q) = max(doc[q], q - W + 1, 0) (attn_frag.h lb_of). They are the document copies with lb read
+// wherever a document start is read: lb(q) <= q and lb is non-decreasing, which is all those walks and
+// skips rely on. It is not a fixed point (lb(lb(q)) < lb(q)), and nothing needs one: lane 0 of a wave
+// sees the key lb(q0) because lb(q0) <= q0, and any lane that sees no key of a chunk takes the selects.
+// Skips, per 32-row block by the block's first query: forward / dQ never multiply a 32-key block that
+// ends before lb(q0) (q0 the wave's first query), dK/dV never a 32-query block whose first query has
+// lb > the wave's last key; chunks outside [lb(128 qt) >> 6, 2 qt + 1] (forward / dQ) or past the first
+// query chunk with lb > 128 kt + 127 (dK/dV) are not even staged. W >= S is passed as S.
+// With a.window == 0 the launchers pick the copies they picked before; the other instantiations
+// contain no window code (if constexpr), and AttnArgs::window sits in former padding.
 // Bias hand-over: bpart[(b * ceil(S/128) + tile)][3*H*64] gets the fp32 column sums of the item's dQ
 // (dQ pass) and dK, dV (dK/dV pass), summed in a fixed order; launch_colsum_final reduces the rows.
 #include <algorithm>
@@ -147,10 +162,11 @@ __device__ __forceinline__ float wave_colsum(float* red, const af32x16 (&t)[2]) 
 }  // namespace
 
 // Forward. Persistent over items (bh, query tile); LDS: K and V chunk tiles, two buffers.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
 __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
+  static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
   const int S = a.S, HD = a.H * D;
@@ -177,12 +193,13 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
     // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
-    // (a padded query: doc is not read, start 0). (Loading the first chunk index one item ahead, so that
+    // (a padded query: doc is not read, start 0). WINDOW: the same with the lower bound lb_of for the
+    // start; all that is used of it is lb(t) <= t and that it does not decrease with t. (Loading the first chunk index one item ahead, so that
     // the first K / V fetch does not wait for it, measured 1 % slower forward + backward: not done.)
     int c0 = 0, dlo = 0, dhi = 0, dq = 0;
     if constexpr (DOCS) {
-      if (nck > 0) c0 = doc_of<DOCS>(a, b, S, 128 * qt) >> 6;
-      if (vq) dq = doc_of<DOCS>(a, b, S, q);
+      if (nck > 0) c0 = lb_of<DOCS, WINDOW>(a, b, S, 128 * qt) >> 6;
+      if (vq) dq = lb_of<DOCS, WINDOW>(a, b, S, q);
       if (live) {
         dlo = __builtin_amdgcn_readfirstlane(dq);
         dhi = __builtin_amdgcn_readlane(dq, __builtin_amdgcn_readfirstlane(min(31, L - 1 - q0)));
@@ -246,6 +263,8 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
         // and cm are both -inf and (m - mn), (s - m) would be NaN: by select, alpha = 1 and p = 0 while the
         // lane's running max is -inf (l and ot are still zero then). A lane with a finite max takes the
         // arithmetic above unchanged. A valid query sees itself, so no lane ends with m = -inf.
+        // Windows: the same lanes, and more of them (with W < 32 most lanes of a wave see no key of the
+        // first block it computes); the two selects below test every lane's own m, whatever its start is.
         const float mn = fmaxf(m, cm);
         float alpha = aexp2((m - mn) * sl);
         if constexpr (DOCS) {
@@ -308,10 +327,11 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
 }
 
 // Backward, dQ pass: the forward's item and orientation; also writes D = rowsum(dO . O) to dsum.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
 __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __restrict__ dsum) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
+  static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   float* red = reinterpret_cast<float*>(smem);
   float* cs_s = reinterpret_cast<float*>(smem + RED_B);  // [4][64]
@@ -340,12 +360,13 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
     // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
-    // (a padded query: doc is not read, start 0). (Loading the first chunk index one item ahead, so that
+    // (a padded query: doc is not read, start 0). WINDOW: the same with the lower bound lb_of for the
+    // start; all that is used of it is lb(t) <= t and that it does not decrease with t. (Loading the first chunk index one item ahead, so that
     // the first K / V fetch does not wait for it, measured 1 % slower forward + backward: not done.)
     int c0 = 0, dlo = 0, dhi = 0, dq = 0;
     if constexpr (DOCS) {
-      if (nck > 0) c0 = doc_of<DOCS>(a, b, S, 128 * qt) >> 6;
-      if (vq) dq = doc_of<DOCS>(a, b, S, q);
+      if (nck > 0) c0 = lb_of<DOCS, WINDOW>(a, b, S, 128 * qt) >> 6;
+      if (vq) dq = lb_of<DOCS, WINDOW>(a, b, S, q);
       if (live) {
         dlo = __builtin_amdgcn_readfirstlane(dq);
         dhi = __builtin_amdgcn_readlane(dq, __builtin_amdgcn_readfirstlane(min(31, L - 1 - q0)));
@@ -458,11 +479,12 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
 
 // Backward, dK/dV pass: item (bh, 128-key tile), the key on the lane. LDS: Q and dO chunk tiles, two
 // buffers, plus the chunk's lse and D.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void attn_long_dkv_kernel(AttnArgs a, const float* __restrict__ dsum) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
-  constexpr int NR = DOCS ? 3 : 2;  // per-row values of a chunk: lse, D and (DOCS) the document start
+  static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
+  constexpr int NR = DOCS ? 3 : 2;  // per-row values of a chunk: lse, D and (DOCS) the document start / lower bound
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B + 2 * NR * KC * 4];
   float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B);  // [buf][lse, D(, doc)][64]
   float* red = reinterpret_cast<float*>(smem);
@@ -506,7 +528,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
       if constexpr (DOCS) {  // the third wave: the chunk's document starts (as int bits; zeros past L)
         if (threadIdx.x >= 2 * KC && threadIdx.x < 3 * KC) {
           const int r = KC * c + (threadIdx.x & (KC - 1));
-          pr = __int_as_float(r < L ? doc_of<DOCS>(a, b, S, r) : 0);
+          pr = __int_as_float(r < L ? lb_of<DOCS, WINDOW>(a, b, S, r) : 0);
         }
       }
     };
@@ -517,10 +539,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
     };
     const int c0 = CAUSAL ? 2 * kt : 0;  // causal: queries before the key tile see none of it (c0 < nqc when nqc > 0)
     // DOCS: the walk stops at the first chunk whose first query's document starts past the tile's last
-    // key; monotone starts make every later chunk invisible too. Lane c tests chunk c (at most 8 chunks).
+    // key; monotone starts make every later chunk invisible too (WINDOW: its lower bound, monotone as
+    // well). Lane c tests chunk c: 64 lanes, so at most 64 chunks -- S <= 4096, which attn_long_supported
+    // guarantees and the launchers check.
     int cend = nqc;
     if constexpr (DOCS) {
-      const bool past = lane >= c0 && lane < nqc && doc_of<DOCS>(a, b, S, KC * lane) > 128 * kt + 127;  // 64 lane < L
+      const bool past = lane >= c0 && lane < nqc && lb_of<DOCS, WINDOW>(a, b, S, KC * lane) > 128 * kt + 127;  // 64 lane < L
       const uint64_t bal = __ballot(past);
       if (bal) cend = __ffsll((unsigned long long)bal) - 1;
     }
@@ -615,12 +639,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
   }
 }
 
-bool attn_long_supported(int S, int head_dim) { return head_dim == D && S > 128 && S <= 512 && S % 64 == 0; }
+// S <= 4096: 64 chunks of 64 rows, one per lane of the dK/dV pass's ballot over the chunks (the only
+// structure here with a size limit; every row, pair and partial index is 64-bit)
+bool attn_long_supported(int S, int head_dim) { return head_dim == D && S > 128 && S <= 4096 && S % 64 == 0; }
 int attn_long_bpart_rows(int B, int S) { return B * ((S + 127) / 128); }
 
 template <typename K, typename... Extra>
 static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra... extra) {
-  if (a.doc && !a.causal) return hipErrorInvalidValue;
+  if ((a.doc || a.window) && !a.causal) return hipErrorInvalidValue;
+  if (a.window < 0) return hipErrorInvalidValue;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items it, it + grid, ...
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), NT, 0) != hipSuccess || per_cu < 1)
@@ -633,10 +660,12 @@ static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra
   return hipGetLastError();
 }
 
-// (VARLEN, CAUSAL, DOCS): full length, lengths, causal (with or without lengths), causal with documents;
-// without a.doc the choice is the one made before the document copies existed
+// (VARLEN, CAUSAL, DOCS, WINDOW): full length, lengths, causal (with or without lengths), causal with
+// documents, causal with a window (with or without documents); with a.window == 0 the choice is the one
+// made before the window copies existed, without a.doc the one before the document copies
 #define PSD_ATTN_LONG_PICK(k, ...)                                               \
-  (a.doc ? launch_long(&k<true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
+  (a.window ? launch_long(&k<true, true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__) \
+   : a.doc ? launch_long(&k<true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
    : a.causal ? launch_long(&k<true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
             : a.lens ? launch_long(&k<true, false>, a, st __VA_OPT__(, ) __VA_ARGS__) \
                      : launch_long(&k<false, false>, a, st __VA_OPT__(, ) __VA_ARGS__))

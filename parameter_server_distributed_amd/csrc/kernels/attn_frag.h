@@ -1,6 +1,6 @@
 // MFMA fragment, dropout-hash and length helpers shared by the fused attention kernels: the
 // whole-head-in-LDS family (attention.hip, S <= 128) and the streaming one (attention_long.hip,
-// 128 < S <= 512). Device code only; include after common.h and launchers_attn.h.
+// 128 < S <= 4096). Device code only; include after common.h and launchers_attn.h.
 #pragma once
 
 #include "common.h"
@@ -103,6 +103,20 @@ __device__ __forceinline__ int doc_of(const AttnArgs& a, int b, int S, int t) {
     return min(max(a.doc[(int64_t)b * S + t], 0), t);
   } else {
     return 0;
+  }
+}
+
+// first key that token t of sequence b may see. DOCS copies: its document's start. WINDOW copies (a.window
+// = W >= 1, a.doc given or null -- only they test it): max(doc, t - W + 1, 0). Like a document start it is
+// <= t, non-decreasing in t, only compared, and asked for t < L only; unlike one it is not a fixed point
+// (lb(lb(t)) < lb(t) in general), so nothing may assume that the key lb(t) has itself as its lower bound.
+template <bool DOCS, bool WINDOW = false>
+__device__ __forceinline__ int lb_of(const AttnArgs& a, int b, int S, int t) {
+  if constexpr (WINDOW) {
+    const int d = a.doc ? min(max(a.doc[(int64_t)b * S + t], 0), t) : 0;
+    return max(d, t - a.window + 1);  // 1 <= W <= INT32_MAX, t >= 0: no overflow; d >= 0 holds the floor
+  } else {
+    return doc_of<DOCS>(a, b, S, t);
   }
 }
 

@@ -19,7 +19,10 @@ struct AttnArgs {
   uint32_t thresh;        // dropout: drop when hash < thresh (0: no dropout)
   float rescale;          // 1 / (1 - p)
   uint32_t seed;
-  const int32_t* lens;    // [B] device lengths or null (every sequence full): sequence b has valid rows
+  int32_t window;         // 0: off; W >= 1 (causal only): query q sees keys max(doc[b, q], q - W + 1, 0) <= key <= q,
+                          // W keys with itself; the WINDOW copies of the streaming kernels, with or without doc.
+                          // (Sits in what was padding before the pointer below: no other field moved.)
+  const int32_t* lens;   // [B] device lengths or null (every sequence full): sequence b has valid rows
                           // 0 .. clamp(lens[b], 0, S) - 1; read by the kernel only, never by the host
   int32_t grid_cap;       // 0: the launcher's own grid; > 0: at most this many (persistent) workgroups
   int32_t causal;         // != 0: query q sees keys <= q only (and < its length, with lens); the CAUSAL copies
@@ -31,9 +34,10 @@ bool attn_supported(int S, int head_dim);
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t stream);
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t stream);
 
-// Streaming kernels for 128 < S <= 512, S % 64 == 0 (kernels/attention_long.hip): the same AttnArgs and
+// Streaming kernels for 128 < S <= 4096, S % 64 == 0 (kernels/attention_long.hip): the same AttnArgs and
 // contracts, except that bpart has attn_long_bpart_rows(B, S) rows of [3*H*64] (one per 128-row tile
-// of a sequence) and backward takes an fp32 [B, H, S] scratch for D = rowsum(dO . O).
+// of a sequence) and backward takes an fp32 [B, H, S] scratch for D = rowsum(dO . O). Only they serve
+// a.window (the whole-head launchers refuse it).
 bool attn_long_supported(int S, int head_dim);
 int attn_long_bpart_rows(int B, int S);
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);

@@ -200,11 +200,11 @@ std::vector<at::Tensor> stem_fwd(const at::Tensor& x, const at::Tensor& w, const
 at::Tensor stem_wgrad(const at::Tensor& x, const at::Tensor& dy);
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt);
+                                 bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0);
 at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt);
+                    bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0);
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
                                double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
                                c10::optional<at::Tensor> q8_out = c10::nullopt,

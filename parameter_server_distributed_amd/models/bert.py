@@ -24,7 +24,7 @@ VOCAB = 30528
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False, fp8=False):
+    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False, fp8=False, window=None):
         super().__init__()
         self.heads = heads
         # fp8: the four Linears run the MX fp8 recipe of ops/linear.py (fp8 forward and bwd-data, bf16
@@ -34,7 +34,8 @@ class BertLayer(nn.Module):
         self.fp8 = bool(fp8)
         self.qkv = MfmaLinear(hidden, 3 * hidden, fp8=f8)
         # packed QKV in, [B, S, hidden] out: one fused kernel per direction (ops/attention.py)
-        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=causal)
+        # window (causal only): sliding-window attention over the last `window` keys (ops/attention.py)
+        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=causal, window=window)
         self.proj = MfmaLinear(hidden, hidden, fp8=f8)
         # LayerNorm(x + dropout(branch)) as one fused kernel family (ops/layernorm.py)
         self.ln1 = FusedAddLayerNorm(hidden, eps=1e-12, p=dropout, seed=2 * index + 1)

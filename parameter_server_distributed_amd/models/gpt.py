@@ -26,13 +26,15 @@ VOCAB = 40512
 
 
 class GPTForLM(nn.Module):
-    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False):
+    def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False,
+                 window=None):
         super().__init__()
         self.vocab = vocab
         self.emb = FusedBertEmbeddings(vocab, hidden, max_pos, 2, eps=1e-12, p=dropout, seed=4242)
         # fp8: MX fp8 qkv / proj / ffn1 / ffn2 in every block (models/bert.py); the LM head stays bf16
-        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8)
-                                     for i in range(layers)])
+        # window: every block attends to the last `window` keys only (sliding window, ops/attention.py)
+        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8,
+                                               window=window) for i in range(layers)])
         wire_fp8_handover(self.layers)
         self.head = MfmaLinear(hidden, vocab)
         self.p = dropout

@@ -113,6 +113,8 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "attn_bias": (True, "QKV bias gradient handed over by the attention backward"),
     "attn_long": (True, "streaming fused attention kernels for S = 192 .. 512 (multiples of 64); off: SDPA on "
                         "transposed views there, as for every other S > 128"),
+    "attn_xlong": (True, "the streaming fused attention kernels also at S = 576 .. 4096 (multiples of 64; needs "
+                         "attn_long); off: S > 512 goes back to SDPA on transposed views"),
 }
 
 _FEAT_ENV: str | None = None

@@ -8,13 +8,17 @@ default shape is BERT-base pre-training (B 256, S 128, 12 heads of 64).
   python tools/attn_bench.py --seq 512 --batch 64 --sdpa   # the streaming kernels against the SDPA path
   python tools/attn_bench.py --seq 512 --batch 64 --causal # the causal instantiations (keys <= q)
   python tools/attn_bench.py --seq 512 --batch 64 --docs 128 --sdpa  # packed documents of mean length 128
+  python tools/attn_bench.py --seq 2048 --batch 8 --causal --window 256 --sdpa  # sliding window of 256 keys
 
 With --min-len the bytes count the valid rows only (what the variable-length kernels have to move)
 and the FLOP rate counts the valid (query, key) pairs. With --causal the FLOP rate counts the visible
 pairs (key <= q, and both < the length); the bytes are unchanged. --docs MEAN (causal only) packs every
 row with documents of length uniform in [MEAN/2, 3 MEAN/2] (seeded) and passes doc_start: the document
 copies of the kernels, and with --sdpa the SDPA path with the same boolean mask; the FLOP rate counts
-the visible pairs (same document, key <= q).
+the visible pairs (same document, key <= q). --window W (causal only, with or without --docs / --min-len)
+passes window=W: the window copies of the streaming kernels (S >= 192), and with --sdpa the SDPA path with
+the band AND-ed into its boolean mask; the FLOP rate counts the visible pairs, q - max(doc, q - W + 1, 0) + 1
+per valid query.
 
 --sdpa also times the module's SDPA path (F.scaled_dot_product_attention on transposed views, through
 autograd, with its layout copies and, with lengths, its mask) on the same data as a second pair of
@@ -59,6 +63,8 @@ def main():
     ap.add_argument("--causal", action="store_true", help="causal mask (keys <= q), on both paths")
     ap.add_argument("--docs", type=int, default=None,
                     help="pack rows with documents of this mean length and pass doc_start (needs --causal)")
+    ap.add_argument("--window", type=int, default=None,
+                    help="sliding window: query q sees the W keys up to and including q (needs --causal)")
     ap.add_argument("--windows", type=int, default=None, help="timing windows per figure (default 1, with --sdpa 5)")
     args = ap.parse_args()
     C = native()
@@ -81,7 +87,9 @@ def main():
         el = int(lc.sum()) * H * D * 2  # the valid rows only
         flop_f = 4 * H * D * int((lc * (lc + 1) // 2 if causal else lc * lc).sum())
         print(f"lens uniform in [{args.min_len}, {S}]: mean {lc.float().mean():.1f}, valid rows {int(lc.sum())} of {B * S}")
-    extra = ()  # (doc_start,) with --docs: the last argument of attn_fwd / attn_bwd and of _sdpa
+    # (doc_start,) with --docs, (doc_start or None, W) with --window: the last arguments of attn_fwd /
+    # attn_bwd and of _sdpa
+    extra = ()
     if args.docs is not None:
         if not causal or args.docs < 2 or args.min_len is not None:
             ap.error("--docs MEAN needs --causal, MEAN >= 2 and no --min-len")
@@ -101,6 +109,16 @@ def main():
         flop_f = 4 * H * D * sum(n * (n + 1) // 2 for r in rows for n in r)
         print(f"documents uniform in [{args.docs // 2}, {args.docs * 3 // 2}]: {ndoc / B:.1f} per row, "
               f"mean length {B * S / ndoc:.1f}")
+    if args.window is not None:
+        if not causal or args.window < 1:
+            ap.error("--window W needs --causal and W >= 1")
+        idx = torch.arange(S)
+        lb = extra[0].cpu().long() if extra else torch.zeros(B, S, dtype=torch.long)
+        lb = torch.maximum(lb, (idx - args.window + 1).clamp(min=0)[None, :])
+        vq = idx[None, :] < (lc[:, None] if lens is not None else S)
+        flop_f = 4 * H * D * int(((idx[None, :] - lb + 1) * vq).sum())
+        extra = (extra[0] if extra else None, args.window)
+        print(f"window {args.window}: {flop_f / (4 * H * D) / (B * S):.1f} visible keys per query")
     it = args.iters
     print(f"B {B}, S {S}, H {H}, D {D}{', causal' if causal else ''}; {nwin} window(s) of {it} calls")
     head = "| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |"
