@@ -75,7 +75,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("hist"), py::arg("margin") = 1.0);
   m.def("embed_bwd_", &embed_bwd_, py::arg("sorted"), py::arg("perm"), py::arg("dy"), py::arg("out"));
   m.def("xent_fwd", &xent_fwd, py::arg("x"), py::arg("labels"));
-  m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("scale"));
+  m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("scale"),
+        py::arg("lse_lo") = py::none());
   m.def("bn_fwd", &bn_fwd, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("residual"), py::arg("relu"), py::arg("training"), py::arg("momentum"),
         py::arg("eps"), py::arg("counter"), py::arg("ss_eval"), py::arg("mask_out") = false,

@@ -238,6 +238,7 @@ void wprep_run(const at::Tensor& table, int64_t tiles);
 // fused softmax cross-entropy on bf16 logits (xent_ops.cpp)
 void embed_bwd_(const at::Tensor& sorted, const at::Tensor& perm, const at::Tensor& dy, at::Tensor out);
 std::vector<at::Tensor> xent_fwd(const at::Tensor& x, const at::Tensor& labels);
-at::Tensor xent_bwd(const at::Tensor& x, const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& scale);
+at::Tensor xent_bwd(const at::Tensor& x, const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& scale,
+                    c10::optional<at::Tensor> lse_lo);
 
 }  // namespace psd

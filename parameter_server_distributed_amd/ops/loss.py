@@ -1,6 +1,6 @@
 """Softmax cross-entropy on bf16 logits through the fused gfx950 kernels of ``csrc/kernels/xent.hip``.
 
-Forward reads the logits once (per-row log-sum-exp kept for backward); backward writes the bf16
+Forward reads the logits once (per-row log-sum-exp kept for backward, with its fp32 rounding error); backward writes the bf16
 gradient ``(softmax - onehot) * dloss / count`` in one pass -- no fp32 copy of the logits, no
 log-prob tensor (the MLM decoder's logits are 4864 x 30528 per BERT-base b256 step). Mean over the
 rows whose label is not negative (``ignore_index=-100`` semantics). Host tensors, other dtypes or
@@ -18,16 +18,16 @@ from .. import native
 class _XentFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):
-        loss_row, lse = native().xent_fwd(logits, labels)
+        loss_row, lse, lse_lo = native().xent_fwd(logits, labels)
         count = (labels >= 0).sum().clamp_min(1).to(torch.float32)
-        ctx.save_for_backward(logits, labels, lse, count)
+        ctx.save_for_backward(logits, labels, lse, lse_lo, count)
         return loss_row.sum() / count
 
     @staticmethod
     def backward(ctx, g):
-        logits, labels, lse, count = ctx.saved_tensors
+        logits, labels, lse, lse_lo, count = ctx.saved_tensors
         scale = (g.float() / count).reshape(1)
-        return native().xent_bwd(logits, labels, lse, scale), None
+        return native().xent_bwd(logits, labels, lse, scale, lse_lo), None
 
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
