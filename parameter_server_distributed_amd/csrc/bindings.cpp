@@ -185,6 +185,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
         py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
         py::arg("doc_start") = py::none(), py::arg("window") = 0);
+  m.def("rope_", &rope_, py::arg("qkv"), py::arg("heads"), py::arg("cos"), py::arg("sin"), py::arg("lens") = py::none(),
+        py::arg("doc_start") = py::none(), py::arg("inverse") = false, py::arg("blocks") = 0);
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
         py::arg("sc8_out") = py::none());

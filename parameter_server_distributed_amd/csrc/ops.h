@@ -205,6 +205,9 @@ at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Ten
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
                     bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0);
+// rotary position embedding of the Q and K heads of a packed qkv, in place (rope_ops.cpp)
+at::Tensor rope_(at::Tensor qkv, int64_t heads, const at::Tensor& cos, const at::Tensor& sin,
+                 c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks);
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
                                double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
                                c10::optional<at::Tensor> q8_out = c10::nullopt,

@@ -24,8 +24,16 @@ VOCAB = 30528
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False, fp8=False, window=None):
+    def __init__(self, hidden=768, heads=12, ffn=3072, dropout=0.1, index=0, causal=False, fp8=False, window=None,
+                 rope=None):
         super().__init__()
+        # rope: (max_pos, base) -- rotary position embedding of Q and K between the QKV Linear and the
+        # attention (ops/rope.py); None: no such module, the path below is untouched
+        self.rot = None
+        if rope is not None:
+            from ..ops.rope import RotaryQK
+
+            self.rot = RotaryQK(heads, int(rope[0]), float(rope[1]))
         self.heads = heads
         # fp8: the four Linears run the MX fp8 recipe of ops/linear.py (fp8 forward and bwd-data, bf16
         # weight gradient); each LayerNorm writes the MX input of the Linear that reads its output
@@ -53,7 +61,10 @@ class BertLayer(nn.Module):
         # each residual LayerNorm hands the gradient of its x input to the Linear that also reads x
         # (folded into that Linear's bwd-data GEMM, ops/layernorm.py)
         # doc_start: packed documents (ops/attention.py), passed on to the attention
-        x = self.ln1(x, self.proj(self.attn(self.qkv(x), lens, doc_start)), x_grad_to=self.qkv)
+        qkv = self.qkv(x)
+        if self.rot is not None:  # rotated in place on the GPU; the QKV Linear then sums its own bias gradient
+            qkv = self.rot(qkv, lens, doc_start)
+        x = self.ln1(x, self.proj(self.attn(qkv, lens, doc_start)), x_grad_to=self.qkv)
         return self.ln2(x, self.ffn2(self.ffn1(x)), x_grad_to=self.ffn1)
 
 

@@ -9,6 +9,13 @@ with all-zero token types, so the sum of the word and position rows (plus one co
 through an embedding LayerNorm and dropout where GPT-1 has dropout only; and the LM head is untied
 from the word embedding, for the reason ``models/bert.py`` gives (the PS data plane needs every weight
 consumed by exactly one autograd node).
+
+``pos="rope"`` replaces the learned absolute positions by rotary position embeddings: every block owns
+a ``RotaryQK(heads, max_pos, rope_base)`` (``ops/rope.py``) between its QKV Linear and its attention, the
+angle following the position inside the document (it restarts with ``doc_start``). One more deviation,
+stated here: the embedding block is kept, fed all-zero position ids and given a one-row position table,
+so the learned position signal becomes one constant row next to the constant type row. The rotary
+tables are no part of the state, so one ``state_dict`` serves every ``max_pos``.
 """
 from __future__ import annotations
 
@@ -27,14 +34,21 @@ VOCAB = 40512
 
 class GPTForLM(nn.Module):
     def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False,
-                 window=None):
+                 window=None, pos="learned", rope_base=10000.0):
         super().__init__()
+        if pos not in ("learned", "rope"):
+            raise ValueError(f"GPTForLM: pos must be 'learned' or 'rope', got {pos!r}")
         self.vocab = vocab
-        self.emb = FusedBertEmbeddings(vocab, hidden, max_pos, 2, eps=1e-12, p=dropout, seed=4242)
+        self.pos = pos
+        # pos="rope": the position table has one row, which every token reads (all-zero position ids)
+        self.emb = FusedBertEmbeddings(vocab, hidden, 1 if pos == "rope" else max_pos, 2, eps=1e-12, p=dropout,
+                                       seed=4242)
         # fp8: MX fp8 qkv / proj / ffn1 / ffn2 in every block (models/bert.py); the LM head stays bf16
         # window: every block attends to the last `window` keys only (sliding window, ops/attention.py)
+        # rope: every block rotates its Q and K by the position inside the document (ops/rope.py)
+        rope = (max_pos, rope_base) if pos == "rope" else None
         self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8,
-                                               window=window) for i in range(layers)])
+                                               window=window, rope=rope) for i in range(layers)])
         wire_fp8_handover(self.layers)
         self.head = MfmaLinear(hidden, vocab)
         self.p = dropout
@@ -57,7 +71,9 @@ class GPTForLM(nn.Module):
         doc_start = batch[2] if len(batch) > 2 else None
         bump_step(self)
         pos_ids = None
-        if doc_start is not None:
+        if self.pos == "rope":  # the blocks carry the position; the embedding adds its one constant row
+            pos_ids = torch.zeros_like(ids)
+        elif doc_start is not None:
             pos_ids = torch.arange(ids.shape[1], device=ids.device)[None, :] - doc_start.long()
         x = self.emb(ids, torch.zeros_like(ids), pos_ids)
         for layer in self.layers:

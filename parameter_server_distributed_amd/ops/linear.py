@@ -151,7 +151,10 @@ class _LinearFn(torch.autograd.Function):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous()
         M, N = x2.shape[0], weight.shape[0]
-        y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+        # the returned tensor owns the buffer and the GEMMs write its [M, N] view: autograd forbids a consumer's
+        # in-place update (ops/rope.py rotates the QKV output) on a view made inside a Function
+        out = torch.empty(*shp[:-1], N, dtype=x.dtype, device=x.device)
+        y = out.view(M, N)
         act = ACTS[mod.act]
         aux = torch.empty_like(y) if act == 2 else None
         use_mx = mod.fp8 == "mx" and mod.psd_mx_input_ok(x2.shape[1])
@@ -212,8 +215,9 @@ class _LinearFn(torch.autograd.Function):
         ctx.gelu_src = src if fuse else None
         ctx.gelu_tok = src._psd_tok if fuse else None
         pre_src = src._psd_gelu_pre if fuse else None
-        ctx.save_for_backward(x2, weight, y if act == 1 else aux, pre_src)
-        out = y.view(*shp[:-1], N)
+        # (ReLU keeps the output itself, not its [M, N] view: a saved view made under no_grad cannot be unpacked
+        # once an in-place op -- the library route's relu_ -- has touched it)
+        ctx.save_for_backward(x2, weight, out if act == 1 else aux, pre_src)
         out._psd_src = (mod, ctx.tok)  # a consumer that can hand this Linear its bias gradient
         if act == 2:
             mod._psd_gelu_pre = aux  # what a fused consumer's backward reads (also saved in this ctx)
@@ -240,7 +244,7 @@ class _LinearFn(torch.autograd.Function):
             # gradient (gemm_gelu_bwd_): dy IS the pre-activation gradient
             db = hand[1]
         elif ctx.act == 1:
-            dy2 = dy2 * (keep > 0)
+            dy2 = dy2 * (keep.view(dy2.shape) > 0)
         elif ctx.act == 2 and ctx.has_bias and ctx.needs_input_grad[2] and dy2.shape[1] % 8 == 0:
             # GELU backward and the bias gradient in one pass over dy / pre (kernels/gemm.hip)
             db = sink(ctx.mod.bias) if sink is not None else None

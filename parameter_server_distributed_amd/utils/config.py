@@ -115,6 +115,8 @@ FEATURES: dict[str, tuple[bool, str]] = {
                         "transposed views there, as for every other S > 128"),
     "attn_xlong": (True, "the streaming fused attention kernels also at S = 576 .. 4096 (multiples of 64; needs "
                          "attn_long); off: S > 512 goes back to SDPA on transposed views"),
+    "rope": (True, "in-place rotary position embedding kernel on the packed QKV (ops/rope.py RotaryQK); off: the "
+                   "out-of-place torch composite rope_ref"),
 }
 
 _FEAT_ENV: str | None = None
