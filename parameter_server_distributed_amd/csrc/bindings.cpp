@@ -187,6 +187,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("doc_start") = py::none(), py::arg("window") = 0);
   m.def("rope_", &rope_, py::arg("qkv"), py::arg("heads"), py::arg("cos"), py::arg("sin"), py::arg("lens") = py::none(),
         py::arg("doc_start") = py::none(), py::arg("inverse") = false, py::arg("blocks") = 0);
+  m.def("rms_fwd", &rms_fwd, py::arg("r"), py::arg("h") = py::none(), py::arg("gamma"), py::arg("eps"), py::arg("p"),
+        py::arg("seed"), py::arg("step") = py::none());
+  m.def("rms_bwd", &rms_bwd, py::arg("dy"), py::arg("dr_new") = py::none(), py::arg("r_new"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("had_h"),
+        py::arg("dgamma_out") = py::none());
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("blocks") = 0);
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("da"), py::arg("gu"), py::arg("blocks") = 0);
   m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("h"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
         py::arg("sc8_out") = py::none());

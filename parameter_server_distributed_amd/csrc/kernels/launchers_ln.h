@@ -67,6 +67,10 @@ int ln_bwd_blocks(int64_t rows);
 hipError_t launch_ln_fwd(const LnArgs& a, hipStream_t stream);
 hipError_t launch_ln_bwd(const LnArgs& a, hipStream_t stream);
 int emb_ln_bwd_blocks(int64_t rows);
+// part [nblk][NP][H] fp32 block partials -> bf16: row 0 into dgamma, row 1 into dbeta, rows 2.. into extra
+// [(NP - 2), H]; summed in a fixed order (deterministic). Pointers of rows NP does not reach are not used.
+hipError_t launch_ln_param_grad(const float* part, int nblk, int H, int NP, uint16_t* dgamma, uint16_t* dbeta,
+                                uint16_t* extra, hipStream_t stream);
 hipError_t launch_emb_ln_fwd(const EmbLnArgs& a, hipStream_t stream);
 hipError_t launch_emb_ln_bwd(const EmbLnArgs& a, hipStream_t stream);
 }  // namespace psd

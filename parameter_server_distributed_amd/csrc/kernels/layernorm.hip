@@ -19,55 +19,9 @@
 #include "common.h"
 #include "launchers_ln.h"
 #include "mx_common.h"
+#include "row_common.h"
 
 namespace psd {
-
-namespace {
-
-// the lane's E keep flags (common.h drop_keep's mask: 16 bits of one hash per element pair; off is
-// even -- a lane's E columns start at an even index -- so each pair's hash is computed once here)
-template <int E>
-__device__ __forceinline__ void keep_flags(uint32_t key, int64_t off, uint32_t thresh, bool (&kp)[E]) {
-  const uint32_t t16 = thresh >> 16;
-#pragma unroll
-  for (int j = 0; j < E / 2; ++j) {
-    const uint32_t hb = drop_pair_bits(key, (uint64_t)(off + 2 * j));
-    kp[2 * j] = (hb & 0xffffu) >= t16;
-    kp[2 * j + 1] = (hb >> 16) >= t16;
-  }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-template <int E>
-__device__ __forceinline__ void load_e(const uint16_t* p, float v[E]) {
-#pragma unroll
-  for (int i = 0; i < E / 4; ++i) {
-    const uint2 w = *reinterpret_cast<const uint2*>(p + 4 * i);
-    v[4 * i + 0] = __uint_as_float(w.x << 16);
-    v[4 * i + 1] = __uint_as_float(w.x & 0xffff0000u);
-    v[4 * i + 2] = __uint_as_float(w.y << 16);
-    v[4 * i + 3] = __uint_as_float(w.y & 0xffff0000u);
-  }
-}
-
-template <int E>
-__device__ __forceinline__ void store_e(uint16_t* p, const float v[E]) {
-#pragma unroll
-  for (int i = 0; i < E / 4; ++i)
-    *reinterpret_cast<uint2*>(p + 4 * i) = make_uint2(pack_bf16x2_rne(v[4 * i], v[4 * i + 1]),
-                                                      pack_bf16x2_rne(v[4 * i + 2], v[4 * i + 3]));
-}
-
-__device__ __forceinline__ uint32_t dropout_key(uint32_t seed, const int64_t* step) {
-  return drop_mix32(seed * 0x27d4eb2fu ^ (uint32_t)(step ? *step : 0) * 0x165667b1u);
-}
-
-}  // namespace
 
 // MX: also the MX e4m3 copy of y for the consumer Linear's fp8 GEMM (ops/linear.py fp8="mx"): payload
 // q8 [rows, H] and one E8M0 byte per 32 columns sc8 [rows, H/32], quantised from the bf16-rounded values
@@ -503,10 +457,12 @@ int ln_bwd_blocks(int64_t rows) {
 
 bool ln_supported(int H) { return H == 768 || H == 1024; }
 
-static uint32_t keep_thresh(float p) {
-  if (p <= 0.f) return 0u;
-  const double t = (double)p * 4294967296.0;
-  return t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
+// the fixed-order finalize of NP partial rows per block (also rmsnorm.hip's dgamma: NP = 1, dgamma only)
+hipError_t launch_ln_param_grad(const float* part, int nblk, int H, int NP, uint16_t* dgamma, uint16_t* dbeta,
+                                uint16_t* extra, hipStream_t st) {
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3((NP * H + 31) / 32), dim3(256), 0, st, part, nblk, H, NP, dgamma, dbeta,
+                     extra);
+  return hipGetLastError();
 }
 
 hipError_t launch_ln_fwd(const LnArgs& a, hipStream_t st) {
@@ -547,10 +503,7 @@ hipError_t launch_ln_bwd(const LnArgs& a, hipStream_t st) {
     else PSD_LNB(16, false);
   }
 #undef PSD_LNB
-  const int np = hs ? 3 : 2;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3((np * a.H + 31) / 32), dim3(256), 0, st, a.part, blocks, a.H, np,
-                     a.dgamma, a.dbeta, a.dhsum);
-  return hipGetLastError();
+  return launch_ln_param_grad(a.part, blocks, a.H, hs ? 3 : 2, a.dgamma, a.dbeta, a.dhsum, st);
 }
 
 hipError_t launch_emb_ln_fwd(const EmbLnArgs& a, hipStream_t st) {
@@ -577,10 +530,7 @@ hipError_t launch_emb_ln_bwd(const EmbLnArgs& a, hipStream_t st) {
   if (nt == 0) hipLaunchKernelGGL((emb_ln_bwd_kernel<12, 0>), dim3(blocks), dim3(256), 0, st, a, th, sc);
   else if (nt == 1) hipLaunchKernelGGL((emb_ln_bwd_kernel<12, 1>), dim3(blocks), dim3(256), 0, st, a, th, sc);
   else hipLaunchKernelGGL((emb_ln_bwd_kernel<12, 2>), dim3(blocks), dim3(256), 0, st, a, th, sc);
-  const int np = 2 + nt;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3((np * a.H + 31) / 32), dim3(256), 0, st, a.part, blocks, a.H, np,
-                     a.dgamma, a.dbeta, a.dT);
-  return hipGetLastError();
+  return launch_ln_param_grad(a.part, blocks, a.H, 2 + nt, a.dgamma, a.dbeta, a.dT, st);
 }
 
 }  // namespace psd

@@ -208,6 +208,15 @@ at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Ten
 // rotary position embedding of the Q and K heads of a packed qkv, in place (rope_ops.cpp)
 at::Tensor rope_(at::Tensor qkv, int64_t heads, const at::Tensor& cos, const at::Tensor& sin,
                  c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks);
+// pre-norm residual step r_new = r + dropout(h), y = RMSNorm(r_new) * gamma, and its backward (rmsnorm_ops.cpp)
+std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h, const at::Tensor& gamma, double eps,
+                                double p, int64_t seed, c10::optional<at::Tensor> step);
+std::vector<at::Tensor> rms_bwd(const at::Tensor& dy, c10::optional<at::Tensor> dr_new, const at::Tensor& r_new,
+                                const at::Tensor& rstd, const at::Tensor& gamma, double p, int64_t seed,
+                                c10::optional<at::Tensor> step, bool had_h, c10::optional<at::Tensor> dgamma_out);
+// gated SiLU on the packed gate/up tensor gu [T, 2F] and its backward (swiglu_ops.cpp)
+at::Tensor swiglu_fwd(const at::Tensor& gu, int64_t blocks);
+at::Tensor swiglu_bwd(const at::Tensor& da, const at::Tensor& gu, int64_t blocks);
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
                                double eps, double p, int64_t seed, c10::optional<at::Tensor> step,
                                c10::optional<at::Tensor> q8_out = c10::nullopt,

@@ -100,7 +100,8 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
         seq = kw.get("seq_len", 512)
         m = prepare(GPTForLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
                              max_pos=max(512, seq), fp8=bool(kw.get("fp8", False)), window=kw.get("window"),
-                             pos=kw.get("pos", "learned"), rope_base=kw.get("rope_base", 10000.0)),
+                             pos=kw.get("pos", "learned"), rope_base=kw.get("rope_base", 10000.0),
+                             arch=kw.get("arch", "gpt"), ffn=kw.get("ffn")),
                     device, dtype)
         min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
         pack = kw.get("pack_docs")  # (lo, hi): rows packed with documents of lengths in [lo, hi]

@@ -16,6 +16,16 @@ angle following the position inside the document (it restarts with ``doc_start``
 stated here: the embedding block is kept, fed all-zero position ids and given a one-row position table,
 so the learned position signal becomes one constant row next to the constant type row. The rotary
 tables are no part of the state, so one ``state_dict`` serves every ``max_pos``.
+
+``arch="llama"`` replaces the block by ``LlamaLayer`` (``models/llama_block.py``): a pre-norm residual
+stream, RMSNorm (eps 1e-6), a gated SiLU FFN of width ``ffn`` (default ``8/3 * hidden`` rounded up to a
+multiple of 256: 2048 at 768, the GELU FFN's parameter count) and bias-free Linears, the LM head included;
+the stack ends with a final ``norm_f``. The forward threads the residual stream and the last branch output
+``(r, h)`` through the blocks. ``pos``, ``window``, padded batches and packed documents compose with it
+unchanged. One more deviation, stated here: the embedding block is kept as it is -- ``FusedBertEmbeddings``
+with its embedding LayerNorm (with a bias) and dropout -- where Llama feeds the bare word embedding into
+the first block. ``fp8=True`` is not built for this block. ``arch="gpt"`` (the default) is the model above,
+module for module.
 """
 from __future__ import annotations
 
@@ -34,12 +44,19 @@ VOCAB = 40512
 
 class GPTForLM(nn.Module):
     def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False,
-                 window=None, pos="learned", rope_base=10000.0):
+                 window=None, pos="learned", rope_base=10000.0, arch="gpt", ffn=None):
         super().__init__()
         if pos not in ("learned", "rope"):
             raise ValueError(f"GPTForLM: pos must be 'learned' or 'rope', got {pos!r}")
+        if arch not in ("gpt", "llama"):
+            raise ValueError(f"GPTForLM: arch must be 'gpt' or 'llama', got {arch!r}")
+        if arch == "llama" and fp8:
+            raise ValueError("GPTForLM: fp8=True with arch='llama' is not built (the Llama block's Linears are bf16)")
+        if arch == "gpt" and ffn is not None and int(ffn) != 4 * hidden:
+            raise ValueError(f"GPTForLM: arch='gpt' has the fixed FFN width 4 * hidden = {4 * hidden}, got ffn={ffn}")
         self.vocab = vocab
         self.pos = pos
+        self.arch = arch
         # pos="rope": the position table has one row, which every token reads (all-zero position ids)
         self.emb = FusedBertEmbeddings(vocab, hidden, 1 if pos == "rope" else max_pos, 2, eps=1e-12, p=dropout,
                                        seed=4242)
@@ -47,17 +64,29 @@ class GPTForLM(nn.Module):
         # window: every block attends to the last `window` keys only (sliding window, ops/attention.py)
         # rope: every block rotates its Q and K by the position inside the document (ops/rope.py)
         rope = (max_pos, rope_base) if pos == "rope" else None
-        self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8,
-                                               window=window, rope=rope) for i in range(layers)])
-        wire_fp8_handover(self.layers)
-        self.head = MfmaLinear(hidden, vocab)
+        if arch == "llama":
+            from ..ops.rmsnorm import FusedAddRMSNorm
+            from .llama_block import LlamaLayer, default_ffn
+
+            ffn = default_ffn(hidden) if ffn is None else int(ffn)
+            self.layers = nn.ModuleList([LlamaLayer(hidden, heads, ffn, dropout, i, window=window, rope=rope)
+                                         for i in range(layers)])
+            # the last block's branch joins the stream here; seeds 2 * i + 1, 2 * i + 2 belong to block i
+            self.norm_f = FusedAddRMSNorm(hidden, eps=1e-6, p=dropout, seed=2 * layers + 1)
+            self.head = MfmaLinear(hidden, vocab, bias=False)
+        else:
+            self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8,
+                                                   window=window, rope=rope) for i in range(layers)])
+            wire_fp8_handover(self.layers)
+            self.head = MfmaLinear(hidden, vocab)
         self.p = dropout
         # device step counter for the fused dropout masks (ops/layernorm.py)
         self.register_buffer("_psd_rng_step", torch.zeros(1, dtype=torch.int64), persistent=False)
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.normal_(m.weight, std=0.02)
-                nn.init.zeros_(m.bias)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
             elif isinstance(m, nn.Embedding):
                 nn.init.normal_(m.weight, std=0.02)
 
@@ -76,8 +105,14 @@ class GPTForLM(nn.Module):
         elif doc_start is not None:
             pos_ids = torch.arange(ids.shape[1], device=ids.device)[None, :] - doc_start.long()
         x = self.emb(ids, torch.zeros_like(ids), pos_ids)
-        for layer in self.layers:
-            x = layer(x, lens, doc_start)
+        if self.arch == "llama":  # the residual stream r and the last branch output h, joined at each norm
+            r, h = x, None
+            for layer in self.layers:
+                r, h = layer(r, h, lens, doc_start)
+            x = self.norm_f(r, h)[1]
+        else:
+            for layer in self.layers:
+                x = layer(x, lens, doc_start)
         return self.head(x.reshape(-1, x.shape[-1]))
 
     @staticmethod

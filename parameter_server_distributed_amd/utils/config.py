@@ -117,6 +117,11 @@ FEATURES: dict[str, tuple[bool, str]] = {
                          "attn_long); off: S > 512 goes back to SDPA on transposed views"),
     "rope": (True, "in-place rotary position embedding kernel on the packed QKV (ops/rope.py RotaryQK); off: the "
                    "out-of-place torch composite rope_ref"),
+    # Llama-style block (ops/rmsnorm.py, ops/swiglu.py)
+    "rmsnorm": (True, "fused residual add + dropout + RMSNorm kernels (ops/rmsnorm.py FusedAddRMSNorm); off: the "
+                      "torch composite add_rmsnorm_ref"),
+    "swiglu": (True, "gated SiLU kernels on the packed gate/up tensor (ops/swiglu.py SwiGLU); off: the torch "
+                     "composite swiglu_ref"),
 }
 
 _FEAT_ENV: str | None = None
