@@ -116,7 +116,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("convn_", &convn_, py::arg("x"), py::arg("w2"), py::arg("out"), py::arg("R"), py::arg("S"), py::arg("stride"),
         py::arg("pad"), py::arg("part") = py::none(), py::arg("shift") = py::none(), py::arg("variant") = -1,
         py::arg("x2") = py::none(), py::arg("bias") = py::none(), py::arg("no_store") = false,
-        py::arg("apply_ss") = py::none(), py::arg("apply_res") = py::none(), py::arg("apply_mask") = py::none());
+        py::arg("apply_ss") = py::none(), py::arg("apply_res") = py::none(), py::arg("apply_mask") = py::none(),
+        py::arg("epi_prefetch") = true);
   m.def("convn_stats_rows", &convn_stats_rows_, py::arg("M"));
   m.def("convn_part_rows", &convn_part_rows_, py::arg("M"), py::arg("N"), py::arg("variant"), py::arg("Ho"),
         py::arg("Wo"), py::arg("R"));
@@ -131,7 +132,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stride"), py::arg("pad"), py::arg("part"), py::arg("variant"), py::arg("mode"), py::arg("bx"),
         py::arg("bmean"), py::arg("bss") = py::none(), py::arg("bdr") = py::none(), py::arg("bmbits") = py::none(),
         py::arg("x2") = py::none(), py::arg("bias") = py::none(), py::arg("bxd") = py::none(),
-        py::arg("bmean_d") = py::none(), py::arg("part_d") = py::none());
+        py::arg("bmean_d") = py::none(), py::arg("part_d") = py::none(), py::arg("epi_prefetch") = true);
   m.def("bn_bwd_pre", &bn_bwd_pre, py::arg("g"), py::arg("x"), py::arg("gamma"), py::arg("save_mean"),
         py::arg("save_invstd"), py::arg("part"), py::arg("rows"), py::arg("dgamma_out") = py::none(),
         py::arg("dbeta_out") = py::none(), py::arg("dq") = py::none(), py::arg("dqmx") = py::none());

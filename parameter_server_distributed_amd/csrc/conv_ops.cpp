@@ -253,7 +253,7 @@ int64_t convn_(const at::Tensor& x, const at::Tensor& w2, at::Tensor out, int64_
                int64_t pad, c10::optional<at::Tensor> part, c10::optional<at::Tensor> shift, int64_t variant,
                c10::optional<at::Tensor> x2, c10::optional<at::Tensor> bias, bool no_store,
                c10::optional<at::Tensor> apply_ss, c10::optional<at::Tensor> apply_res,
-               c10::optional<at::Tensor> apply_mask) {
+               c10::optional<at::Tensor> apply_mask, bool epi_prefetch) {
   TORCH_CHECK(is_nhwc_dev(x, at::kBFloat16), "psd convn: x must be a channels_last bf16 device tensor");
   TORCH_CHECK(w2.is_cuda() && w2.dim() == 2 && w2.scalar_type() == at::kBFloat16 && w2.is_contiguous(),
               "psd convn: w2 must be a contiguous bf16 [Cout, R*S*C] device tensor");
@@ -309,6 +309,7 @@ int64_t convn_(const at::Tensor& x, const at::Tensor& w2, at::Tensor out, int64_
     a.ares = opt_ptr<const uint16_t>(apply_res);
     a.amask = apply_mask->data_ptr<uint8_t>();
   }
+  a.epi_prefetch = epi_prefetch ? 1 : 0;
   set_geo(a, g, wbytes, Cout, K, no_store ? Cout : out.stride(0), variant);
   const hipError_t e = launch_convn(a, stream_of(x));
   if (e == hipErrorNotSupported) return 0;
@@ -401,7 +402,8 @@ int64_t convn_bwd_(const at::Tensor& dy, const at::Tensor& w2, at::Tensor out, i
                    int64_t pad, at::Tensor part, int64_t variant, int64_t mode, c10::optional<at::Tensor> bx,
                    const at::Tensor& bmean, c10::optional<at::Tensor> bss, c10::optional<at::Tensor> bdr,
                    c10::optional<at::Tensor> bmbits, c10::optional<at::Tensor> x2, c10::optional<at::Tensor> bias,
-                   c10::optional<at::Tensor> bxd, c10::optional<at::Tensor> bmean_d, c10::optional<at::Tensor> part_d) {
+                   c10::optional<at::Tensor> bxd, c10::optional<at::Tensor> bmean_d, c10::optional<at::Tensor> part_d,
+                   bool epi_prefetch) {
   TORCH_CHECK(is_nhwc_dev(dy, at::kBFloat16), "psd convn_bwd: dy must be a channels_last bf16 device tensor");
   TORCH_CHECK(w2.is_cuda() && w2.dim() == 2 && w2.scalar_type() == at::kBFloat16 && w2.is_contiguous(),
               "psd convn_bwd: w2 must be a contiguous bf16 [N, R*S*C] tensor");
@@ -462,6 +464,7 @@ int64_t convn_bwd_(const at::Tensor& dy, const at::Tensor& w2, at::Tensor out, i
   a.y = out.data_ptr();
   a.part = part.data_ptr<float>();
   set_geo(a, g, wbytes, N, K, N, variant);
+  a.epi_prefetch = epi_prefetch ? 1 : 0;
   a.bwd = (int)mode;
   a.bx = opt_ptr<const uint16_t>(bx);
   a.bmean = bmean.data_ptr<float>();

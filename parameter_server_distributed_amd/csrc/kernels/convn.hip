@@ -58,14 +58,15 @@ __device__ __forceinline__ bf16x8 frag(const uint8_t* lds, int rb, int ks, int l
   return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lds + kmaj_off(row, ks * 4 + (lane >> 4))));
 }
 
-// wait until at most `ahead` K-tiles (DPSK loads each) of this wave are still in flight
-template <int DPSK, int A>
+// wait until at most `ahead` K-tiles (DPSK loads each) of this wave are still in flight, plus OFF
+// further loads that were issued after the awaited K-tile (prefetched epilogue operands)
+template <int DPSK, int A, int OFF = 0>
 __device__ __forceinline__ void wait_ahead(int ahead) {
   if constexpr (A <= 0) {
-    wait_vm<0>();
+    wait_vm<OFF>();
   } else {
-    if (ahead >= A) wait_vm<A * DPSK>();
-    else wait_ahead<DPSK, A - 1>(ahead);
+    if (ahead >= A) wait_vm<A * DPSK + OFF>();
+    else wait_ahead<DPSK, A - 1, OFF>(ahead);
   }
 }
 
@@ -184,9 +185,10 @@ __device__ __forceinline__ void convn_flush(const ConvnArgs& a, EpiSums<WNT / 16
 
 // The epilogue's per-row operands of one wave's 64 rows (the pixel index of each row this lane
 // stores, and for the BN-backward modes the BN input x / residual gradient dr / ReLU bits / the dual
-// tail's xd; for the apply mode the residual). epi_load issues the loads; a persistent kernel can
-// issue them for its NEXT tile before that tile's MFMA loop (convh_kernel), so the loads' latency
-// hides behind the taps instead of stalling the epilogue -- at one wave per SIMD nothing else does.
+// tail's xd; for the apply mode the residual). epi_load issues the loads at the top of the epilogue;
+// the persistent 1x1 kernels issue them one tile ahead instead (epi_prefetch below, PRE in
+// convn_epilogue), so the loads' latency hides behind the previous tile instead of stalling the
+// epilogue -- at one workgroup per CU nothing else hides it.
 template <int WNT>
 struct EpiOps {
   static constexpr int CPR = WNT * 2 / 16;
@@ -194,6 +196,9 @@ struct EpiOps {
   int mm[4][PASSES];
   u32x4 exr[4][PASSES], rv4[4][PASSES], dv4[4][PASSES];
   uint32_t bt[4][PASSES];
+  // the prefetching kernels' mask byte, kept as loaded: widening it where it is loaded is an ALU
+  // instruction on the load's result, i.e. a wait for the load one tile before its use
+  uint8_t bt8[4][PASSES];
 };
 
 template <int WNT, int BWD, typename Pix>
@@ -248,23 +253,120 @@ __device__ __forceinline__ void epi_load(const ConvnArgs& a, int wr, int wc, int
     }
 }
 
+// ---- one-tile-ahead operand prefetch of the persistent 1x1 kernels (modes 2 / 3 / 5 / 8)
+// Buffer descriptors of the epilogue operands: a row that does not exist takes the offset kOOB, so
+// its load is still ISSUED (the counted waits of the ring depend on the exact number of loads in
+// flight, epi_prefetch below) but returns zeros without touching memory -- the zeros epi_load
+// writes for such a row.
+struct EpiSrc {
+  rsrc_t bx, dr, mb, xd;  // BN input | dr (mode 8: the residual) | mask bits | the dual tail's xd
+};
+__device__ __forceinline__ EpiSrc epi_src(const ConvnArgs& a) {
+  const uint32_t mn2 = (uint32_t)a.M * (uint32_t)a.N * 2u;  // (the launcher bounds M * N * 2 to 32 bits)
+  EpiSrc s;
+  s.bx = make_rsrc(a.bx ? (const void*)a.bx : a.x, a.bx ? mn2 : 0u);
+  if (a.bwd == 8) {
+    s.dr = make_rsrc(a.ares ? (const void*)a.ares : a.x, a.ares ? mn2 : 0u);
+  } else {
+    s.dr = make_rsrc(a.bdr, a.bwd == 5 ? mn2 >> 2 : mn2);
+  }
+  s.mb = make_rsrc(a.bmbits ? (const void*)a.bmbits : a.x, a.bmbits ? mn2 >> 4 : 0u);
+  s.xd = make_rsrc(a.bxd ? (const void*)a.bxd : a.x, a.bxd ? mn2 : 0u);
+  return s;
+}
+
+// the epilogue's per-channel constants, loaded once per workgroup by the prefetching kernels (the
+// plain epilogue re-loads them per tile, in front of their first use)
+template <int WNT>
+struct EpiK {
+  float bmu[8], bmd[8];
+  float sc[WNT / 16], sh[WNT / 16], bias[WNT / 16];
+};
+template <int WNT, int BWD>
+__device__ __forceinline__ void epi_consts(const ConvnArgs& a, int wc, int lane, int n0, EpiK<WNT>& k) {
+  constexpr int CPR = EpiOps<WNT>::CPR;
+  const int my_col = n0 + wc * WNT + (lane % CPR) * 8;
+  if constexpr (BWD == 3) load8_f32(a.bmean_d + my_col, k.bmd);
+  if constexpr (BWD >= 1 && BWD <= 5) load8_f32(a.bmean + my_col, k.bmu);
+#pragma unroll
+  for (int j = 0; j < WNT / 16; ++j) {
+    const int col = n0 + wc * WNT + j * 16 + (lane & 15);
+    k.bias[j] = a.bias ? a.bias[col] : 0.f;
+    if constexpr (BWD == 8) {
+      k.sc[j] = a.bss[col];
+      k.sh[j] = a.bss[a.N + col];
+    }
+  }
+}
+
+template <int WNT, int BWD, bool HASBX>
+struct EpiPf {
+  static constexpr int PER = BWD == 8 ? 1 : (HASBX ? 1 : 0) + 2 + (BWD == 3 ? 1 : 0);  // loads per row chunk
+  static constexpr int LOADS = 4 * EpiOps<WNT>::PASSES * PER;  // per wave per tile, ALWAYS issued
+};
+
+// Loads of row block i (16 rows) of the tile at row m0 into o: exactly EpiPf::LOADS / 4 vector
+// loads, unconditionally (no branch: rows at or past mlim take kOOB). mlim = a.M, or 0 for "no next
+// tile" (every load out of range).
+template <int WNT, int BWD, bool HASBX>
+__device__ __forceinline__ void epi_prefetch(const ConvnArgs& a, const EpiSrc& s, int i, int wr, int wc, int lane,
+                                             int m0, int mlim, int n0, EpiOps<WNT>& o) {
+  constexpr int CPR = EpiOps<WNT>::CPR, PASSES = EpiOps<WNT>::PASSES;
+  const int my_col = n0 + wc * WNT + (lane % CPR) * 8;
+#pragma unroll
+  for (int ps = 0; ps < PASSES; ++ps) {
+    const int rr = (ps * 64 + lane) / CPR;
+    const int row = m0 + wr * 64 + i * 16 + rr;
+    const bool ok = row < mlim;
+    o.mm[i][ps] = ok ? row : -1;
+    const uint32_t off = ok ? ((uint32_t)row * (uint32_t)a.N + (uint32_t)my_col) * 2u : kOOB;
+    if constexpr (BWD == 8) {
+      o.rv4[i][ps] = __builtin_amdgcn_raw_buffer_load_b128(s.dr, off, 0, 0);
+    } else {
+      if constexpr (HASBX) o.exr[i][ps] = __builtin_amdgcn_raw_buffer_load_b128(s.bx, off, 0, 0);
+      uint32_t roff = off;
+      if constexpr (BWD == 5) {  // dr on the quarter grid: even (h, w) only (M < 2^24: fdiv is exact)
+        const int hw = a.Ho * a.Wo;
+        const int n = fdiv(row, hw, 1.f / (float)hw), rem = row - n * hw;
+        const int h = fdiv(rem, a.Wo, 1.f / (float)a.Wo), w = rem - h * a.Wo;
+        const uint32_t q = (uint32_t)((n * (a.Ho >> 1) + (h >> 1)) * (a.Wo >> 1) + (w >> 1));
+        roff = (ok && ((h | w) & 1) == 0) ? (q * (uint32_t)a.N + (uint32_t)my_col) * 2u : kOOB;
+      }
+      o.rv4[i][ps] = __builtin_amdgcn_raw_buffer_load_b128(s.dr, roff, 0, 0);
+      o.bt8[i][ps] = __builtin_amdgcn_raw_buffer_load_b8(s.mb, ok ? off >> 4 : kOOB, 0, 0);
+      if constexpr (BWD == 3) o.dv4[i][ps] = __builtin_amdgcn_raw_buffer_load_b128(s.xd, off, 0, 0);
+    }
+  }
+}
+
+struct NoNext {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+
 // Epilogue of one wave's 64 x WNT accumulator block (shared by the gathered kernel, the persistent
 // HALO kernel and the persistent 1x1 kernel): per-wave, no barrier (``stg`` is this wave's own 2 KiB of LDS). C layout
 // of a 16x16 block: col = lane & 15, row = 4 * (lane >> 4) + r. ``pix(p)``: output pixel of tile row
 // p (-1: none). The reductions accumulate into ``es``; without DEFER they are flushed here to
 // partial row (tm * WM + wr).
-template <int BM, int BN, int WNT, bool STATS, int BWD, bool DEFER = false, bool PRE = false, typename Pix>
+// PRE (the prefetching persistent kernels): the operands come from ``pre`` (loaded one tile earlier;
+// HASBX: the BN input among them), the per-channel constants from ``kc``, and ``next(i)`` is called
+// once row block i's operands are consumed and its rows stored -- the caller re-fills them there.
+template <int BM, int BN, int WNT, bool STATS, int BWD, bool DEFER = false, bool PRE = false, bool HASBX = true,
+          typename Pix, typename Nxt = NoNext>
 __device__ __forceinline__ void convn_epilogue(const ConvnArgs& a, f32x4 (&acc)[4][WNT / 16],
                                                const float (&kshift)[WNT / 16], int tm, int wr, int wc, int lane,
                                                uint8_t* stg, Pix pix, int n0, EpiSums<WNT / 16>& es,
-                                               const EpiOps<WNT>* pre = nullptr) {
+                                               const EpiOps<WNT>* pre = nullptr, const EpiK<WNT>* kc = nullptr,
+                                               Nxt next = Nxt{}) {
   constexpr int JN = WNT / 16;
   constexpr int WM = BM / 64;
   const int cl = lane & 15, rq = (lane >> 4) * 4;
   if (a.bias) {  // per-output-channel bias (the BN-backward fold's constant term)
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
-      const float bv = a.bias[n0 + wc * WNT + j * 16 + cl];
+      float bv;
+      if constexpr (PRE) bv = kc->bias[j];
+      else bv = a.bias[n0 + wc * WNT + j * 16 + cl];
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i][j] += f32x4{bv, bv, bv, bv};
     }
@@ -326,7 +428,12 @@ __device__ __forceinline__ void convn_epilogue(const ConvnArgs& a, f32x4 (&acc)[
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
       const int col = n0 + wc * WNT + j * 16 + cl;
-      const float sc = a.bss[col], sh = a.bss[a.N + col];
+      float sc, sh;
+      if constexpr (PRE) {
+        sc = kc->sc[j], sh = kc->sh[j];
+      } else {
+        sc = a.bss[col], sh = a.bss[a.N + col];
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -342,8 +449,16 @@ __device__ __forceinline__ void convn_epilogue(const ConvnArgs& a, f32x4 (&acc)[
   const int my_c16 = lane % CPR;
   const int my_col = n0 + wc * WNT + my_c16 * 8;
   float bmu[8], bsc[8], bsh[8], bmd[8];
-  if constexpr (BWD == 3) load8_f32(a.bmean_d + my_col, bmd);
-  if constexpr (BRED) load8_f32(a.bmean + my_col, bmu);
+  if constexpr (PRE) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if constexpr (BRED) bmu[e] = kc->bmu[e];
+      if constexpr (BWD == 3) bmd[e] = kc->bmd[e];
+    }
+  } else {
+    if constexpr (BWD == 3) load8_f32(a.bmean_d + my_col, bmd);
+    if constexpr (BRED) load8_f32(a.bmean + my_col, bmu);
+  }
   if constexpr (BWD == 1) {
     load8_f32(a.bss + my_col, bsc);
     load8_f32(a.bss + a.N + my_col, bsh);
@@ -406,11 +521,18 @@ __device__ __forceinline__ void convn_epilogue(const ConvnArgs& a, f32x4 (&acc)[
         if constexpr (BRED) {
           float d[8], xv[8];
           load8_bf16(reinterpret_cast<const uint16_t*>(&v), d);
-          load8_bf16(reinterpret_cast<const uint16_t*>(&exr[i][ps]), xv);
+          if constexpr (HASBX) {
+            load8_bf16(reinterpret_cast<const uint16_t*>(&exr[i][ps]), xv);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xv[e] = 0.f;
+          }
           if constexpr (BWD >= 2) {
             float rv[8];
             load8_bf16(reinterpret_cast<const uint16_t*>(&rv4[i][ps]), rv);
-            const uint32_t bits = bt[i][ps];
+            uint32_t bits;
+            if constexpr (PRE) bits = ops.bt8[i][ps];
+            else bits = bt[i][ps];
 #pragma unroll
             for (int e = 0; e < 8; ++e) d[e] = ((bits >> e) & 1u) ? d[e] + rv[e] : 0.f;
           } else {
@@ -438,6 +560,7 @@ __device__ __forceinline__ void convn_epilogue(const ConvnArgs& a, f32x4 (&acc)[
         *reinterpret_cast<u32x4*>(y + go) = v;
       }
     }
+    if constexpr (PRE) next(i);
   }
   if constexpr (!DEFER) convn_flush<WNT, STATS, BWD>(a, es, (int64_t)tm * WM + wr, wc, lane, n0);
 }
@@ -614,7 +737,29 @@ __global__ __launch_bounds__(512) void convn_kernel(ConvnArgs a) {
 // the next tiles' A (and B) K-tiles land while this tile's MFMAs and epilogue run; the epilogue's
 // reductions accumulate over the run (one partial row per wave row per workgroup). A [M][C] with
 // row m the output pixel itself (and the K-concatenated x2 of the BN-backward fold).
-template <int BN, int WNT, int NSLOT, bool STATS, int BWD>
+//
+// PF (modes 2 / 3 / 5 / 8): the epilogue operands of a tile -- per 128 x 256 tile 64 KiB of dr or
+// residual, the mask bytes, the BN input(s): several times the A/B bytes of its K-tiles -- are loaded
+// one tile ahead. At one workgroup per CU, two waves per SIMD in barrier lock-step, loading them at
+// the top of the epilogue exposed their whole HBM latency once per tile. The wave keeps ONE operand
+// set (registers: two do not fit beside the accumulators): row block i of the next tile is loaded
+// right after row block i of this tile is consumed and stored (convn_epilogue's next(i)); the first
+// tile's set is issued behind the first D K-tiles. The next tile's rows are disjoint from the rows
+// this tile stores, so an output that aliases dr / the residual stays correct.
+//
+// vmcnt accounting. Loads return in issue order, so "at most n loads outstanding" means the n
+// youngest. The prefetching kernels issue everything unconditionally (a K-tile past the run and the
+// operand set of "no next tile" go out of range: kOOB, zeros, no traffic), so the loads younger than
+// K-tile T at its wait are exactly
+//   * the K-tiles T+1 .. T+D-1: (D - 1) * DPS (stage(T') is issued in iteration T' - D), and
+//   * the operand set issued in the epilogue of iteration E (E = -1: the prologue), i.e. between
+//     stage(E + D) and stage(E + D + 1): younger than K-tile T iff T <= E + D -- EpiPf::LOADS more.
+//     (For T > E + D the set is older than K-tile T and the plain allowance completes it; its
+//     consumer is the epilogue of iteration E + nt >= T.)
+// An allowance that is too small only drains the prefetch; one that is too large would read a
+// K-tile before it lands, hence no branch around any of these loads. The stores in between also
+// count in vmcnt and only lengthen a wait.
+template <int BN, int WNT, int NSLOT, bool STATS, int BWD, bool PF = false, bool HASBX = true>
 __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
   constexpr int BM = 128;
   using G = Geo<BM, BN, WNT, NSLOT>;
@@ -651,13 +796,14 @@ __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
     const bool second = k0 >= a.K1;
     const int c0 = second ? k0 - a.K1 : k0;
     const int lc = second ? a.logC2 : a.logC;
+    const bool live = !PF || T < total;  // PF: a K-tile past the run is issued out of range
 #pragma unroll
     for (int i = 0; i < G::APW; ++i) {
       const int piece = i * G::NW + wid;
       const int row = piece * 8 + (lane >> 3);
       const int kc = (lane & 7) ^ ((row >> 1) & 7);
       const int m = m0 + row;
-      const uint32_t off = m < a.M ? ((((uint32_t)m) << lc) + (uint32_t)(c0 + kc * 8)) * 2u : kOOB;
+      const uint32_t off = (live && m < a.M) ? ((((uint32_t)m) << lc) + (uint32_t)(c0 + kc * 8)) * 2u : kOOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(second ? x2r : xr,
                                                (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, off,
                                                0, 0, 0);
@@ -667,7 +813,7 @@ __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
       const int piece = i * G::NW + wid;
       const int row = piece * 8 + (lane >> 3);
       const int kc = (lane & 7) ^ ((row >> 1) & 7);
-      const uint32_t off = ((uint32_t)(n0 + row) * (uint32_t)a.K + (uint32_t)(k0 + kc * 8)) * 2u;
+      const uint32_t off = live ? ((uint32_t)(n0 + row) * (uint32_t)a.K + (uint32_t)(k0 + kc * 8)) * 2u : kOOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           wrs, (__attribute__((address_space(3))) void*)(slot + (SLOTB - BN * 128) + piece * 1024), 16, off, 0, 0, 0);
     }
@@ -681,12 +827,34 @@ __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
   es.zero();
   uint8_t* stg = smem + nslot * SLOTB + wid * G::STG;
   const int D = nslot - 1;  // K-tiles issued ahead (nslot >= 2)
-  for (int p = 0; p < D && p < total; ++p) stage(p);
+  constexpr int PFL = EpiPf<WNT, BWD, HASBX>::LOADS;
+  static_assert(!PF || G::DPS * (NSLOT - 2) + PFL < 64, "vmcnt is 6 bits");
+  EpiOps<WNT> ops;
+  EpiK<WNT> kc;
+  EpiSrc src;
+  int pf_at = -1;  // iteration whose epilogue issued the operand set now in `ops` (-1: the prologue)
+  if constexpr (PF) {
+    src = epi_src(a);
+    epi_consts<WNT, BWD>(a, wc, lane, n0, kc);
+    for (int p = 0; p < D; ++p) stage(p);
+    __builtin_amdgcn_sched_barrier(0);  // the first operand set is issued BEHIND these K-tiles
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      epi_prefetch<WNT, BWD, HASBX>(a, src, i, wr, wc, lane, t_begin * BM, total > 0 ? a.M : 0, n0, ops);
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    for (int p = 0; p < D && p < total; ++p) stage(p);
+  }
   for (int T = 0; T < total; ++T) {
-    wait_ahead<G::DPS, NSLOT - 2>(min(total - 1 - T, D - 1));
+    if constexpr (PF) {  // (the accounting above)
+      if (T - pf_at <= D) wait_ahead<G::DPS, NSLOT - 2, PFL>(D - 1);
+      else wait_ahead<G::DPS, NSLOT - 2>(D - 1);
+    } else {
+      wait_ahead<G::DPS, NSLOT - 2>(min(total - 1 - T, D - 1));
+    }
     __builtin_amdgcn_s_barrier();  // every wave: K-tile T published, K-tile T-1 no longer read
     __builtin_amdgcn_sched_barrier(0);
-    if (T + D < total) stage(T + D);
+    if (PF || T + D < total) stage(T + D);
     const uint8_t* As = smem + (T % nslot) * SLOTB;
     const uint8_t* Bs = As + (SLOTB - BN * 128);
     bf16x8 af[2][4], bf[2][G::JN];
@@ -709,7 +877,18 @@ __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
       const int tile = t_begin + T / nt;
       const int m0 = tile * BM;
       auto pix = [&](int p) -> int { return m0 + p < a.M ? m0 + p : -1; };
-      convn_epilogue<BM, BN, WNT, STATS, BWD, true>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0, es);
+      if constexpr (PF) {
+        const int nlim = tile + 1 < t_end ? a.M : 0;
+        auto next = [&](int i) {
+          epi_prefetch<WNT, BWD, HASBX>(a, src, i, wr, wc, lane, m0 + BM, nlim, n0, ops);
+        };
+        convn_epilogue<BM, BN, WNT, STATS, BWD, true, true, HASBX>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0,
+                                                                   es, &ops, &kc, next);
+        pf_at = T;
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        convn_epilogue<BM, BN, WNT, STATS, BWD, true>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0, es);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -729,7 +908,8 @@ __global__ __launch_bounds__(512) void convp_kernel(ConvnArgs a, int tiles_m) {
 // re-DMA'd the 32 KiB weight tile for every 16 KiB of input and kept 2 tiles in flight: the tail's
 // statistics-only pass over layer1 ran at 1.4 TB/s of input (288 us, profiles/tail_passes_r4.md).
 constexpr int kPrMaxSlots = 6;
-template <int BN, int WNT, bool STATS, int BWD>
+// PF: the operand prefetch of convp_kernel, same accounting with DPS = APW (the ring carries A only).
+template <int BN, int WNT, bool STATS, int BWD, bool PF = false, bool HASBX = true>
 __global__ __launch_bounds__(512) void convpr_kernel(ConvnArgs a, int tiles_m) {
   constexpr int BM = 128;
   using G = Geo<BM, BN, WNT, 3>;
@@ -778,13 +958,14 @@ __global__ __launch_bounds__(512) void convpr_kernel(ConvnArgs a, int tiles_m) {
     const bool second = k0 >= a.K1;
     const int c0 = second ? k0 - a.K1 : k0;
     const int lc = second ? a.logC2 : a.logC;
+    const bool live = !PF || T < total;  // PF: a K-tile past the run is issued out of range
 #pragma unroll
     for (int i = 0; i < G::APW; ++i) {
       const int piece = i * G::NW + wid;
       const int row = piece * 8 + (lane >> 3);
       const int kc = (lane & 7) ^ ((row >> 1) & 7);
       const int m = m0 + row;
-      const uint32_t off = m < a.M ? ((((uint32_t)m) << lc) + (uint32_t)(c0 + kc * 8)) * 2u : kOOB;
+      const uint32_t off = (live && m < a.M) ? ((((uint32_t)m) << lc) + (uint32_t)(c0 + kc * 8)) * 2u : kOOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(second ? x2r : xr,
                                                (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, off,
                                                0, 0, 0);
@@ -798,14 +979,36 @@ __global__ __launch_bounds__(512) void convpr_kernel(ConvnArgs a, int tiles_m) {
   EpiSums<G::JN> es;
   es.zero();
   const int D = nslot - 1;
-  for (int p = 0; p < D && p < total; ++p) stage(p);
+  constexpr int PFL = EpiPf<WNT, BWD, HASBX>::LOADS;
+  static_assert(!PF || G::APW * (kPrMaxSlots - 2) + PFL < 64, "vmcnt is 6 bits");
+  EpiOps<WNT> ops;
+  EpiK<WNT> kc;
+  EpiSrc src;
+  int pf_at = -1;  // iteration whose epilogue issued the operand set now in `ops` (-1: the prologue)
+  if constexpr (PF) {
+    src = epi_src(a);
+    epi_consts<WNT, BWD>(a, wc, lane, n0, kc);
+    for (int p = 0; p < D; ++p) stage(p);
+    __builtin_amdgcn_sched_barrier(0);  // the first operand set is issued BEHIND these K-tiles
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      epi_prefetch<WNT, BWD, HASBX>(a, src, i, wr, wc, lane, t_begin * BM, total > 0 ? a.M : 0, n0, ops);
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    for (int p = 0; p < D && p < total; ++p) stage(p);
+  }
   for (int T = 0; T < total; ++T) {
     // K-tile T landed: at most (D - 1) later K-tiles' A DMA in flight (loads return in issue order;
-    // the epilogue's stores in the count only lengthen the wait)
-    wait_ahead<G::APW, kPrMaxSlots - 2>(min(total - 1 - T, D - 1));
+    // the epilogue's stores in the count only lengthen the wait); PF: convp_kernel's accounting
+    if constexpr (PF) {
+      if (T - pf_at <= D) wait_ahead<G::APW, kPrMaxSlots - 2, PFL>(D - 1);
+      else wait_ahead<G::APW, kPrMaxSlots - 2>(D - 1);
+    } else {
+      wait_ahead<G::APW, kPrMaxSlots - 2>(min(total - 1 - T, D - 1));
+    }
     __builtin_amdgcn_s_barrier();  // every wave: K-tile T published, K-tile T-1 no longer read
     __builtin_amdgcn_sched_barrier(0);
-    if (T + D < total) stage(T + D);
+    if (PF || T + D < total) stage(T + D);
     const uint8_t* As = ring + (T % nslot) * AB;
     const uint8_t* Bs = bres + (T % nt) * BN * 128;
     bf16x8 af[2][4], bf[2][G::JN];
@@ -828,7 +1031,18 @@ __global__ __launch_bounds__(512) void convpr_kernel(ConvnArgs a, int tiles_m) {
       const int tile = t_begin + T / nt;
       const int m0 = tile * BM;
       auto pix = [&](int p) -> int { return m0 + p < a.M ? m0 + p : -1; };
-      convn_epilogue<BM, BN, WNT, STATS, BWD, true>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0, es);
+      if constexpr (PF) {
+        const int nlim = tile + 1 < t_end ? a.M : 0;
+        auto next = [&](int i) {
+          epi_prefetch<WNT, BWD, HASBX>(a, src, i, wr, wc, lane, m0 + BM, nlim, n0, ops);
+        };
+        convn_epilogue<BM, BN, WNT, STATS, BWD, true, true, HASBX>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0,
+                                                                   es, &ops, &kc, next);
+        pf_at = T;
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        convn_epilogue<BM, BN, WNT, STATS, BWD, true>(a, acc, kshift, tile, wr, wc, lane, stg, pix, n0, es);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1045,7 +1259,20 @@ static int convp_grid_x(int tiles_m, int tiles_n) {
   return g < tiles_m ? g : tiles_m;
 }
 
-template <int BN, bool STATS, int BWD>
+// The operand prefetch (ConvnArgs::epi_prefetch) is taken where it is built: the 256-wide column
+// tile (every wide bwd-data / apply output of the model), modes 2 / 5 / 8, operands that a 32-bit
+// buffer offset reaches (and M < 2^24: mode 5's reciprocal division). Mode 3 stays on the plain
+// kernels: its operand set (x, dr, xd, mask: 112 VGPRs) held across the K loop spills (17 / 28
+// VGPRs to scratch in convpr / convp at the 256-register budget of two waves per SIMD). Every other
+// launch runs the plain kernels, whatever the flag says; grid, partial rows and results do not
+// depend on it.
+template <int BN>
+static bool pf_ok(const ConvnArgs& a) {
+  return BN == 256 && a.epi_prefetch && (a.bwd == 2 || a.bwd == 5 || a.bwd == 8) && a.ldc == a.N &&
+         (int64_t)a.M * a.N * 2 <= 0xFFFFFF00ll && a.M < (1 << 24);
+}
+
+template <int BN, bool STATS, int BWD, bool PF = false, bool HASBX = true>
 static hipError_t convp_launch_t(const ConvnArgs& a0, hipStream_t st, int grid_mul = 1) {
   constexpr int WNT = P1Cfg<BN>::WNT;
   using G = Geo<128, BN, WNT, kP1Slots>;
@@ -1053,7 +1280,7 @@ static hipError_t convp_launch_t(const ConvnArgs& a0, hipStream_t st, int grid_m
   static_assert(LDS <= 160 * 1024, "LDS");
   static bool attr = false;
   if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)convp_kernel<BN, WNT, kP1Slots, STATS, BWD>,
+    const hipError_t e = hipFuncSetAttribute((const void*)convp_kernel<BN, WNT, kP1Slots, STATS, BWD, PF, HASBX>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) return e;
     attr = true;
@@ -1063,8 +1290,8 @@ static hipError_t convp_launch_t(const ConvnArgs& a0, hipStream_t st, int grid_m
   const int tiles_m = (a.M + 127) / 128, tiles_n = a.N / BN;
   int gx = convp_grid_x(tiles_m, tiles_n) * grid_mul;
   if (gx > tiles_m) gx = tiles_m;
-  hipLaunchKernelGGL((convp_kernel<BN, WNT, kP1Slots, STATS, BWD>), dim3(gx, tiles_n), dim3(G::NT), LDS, st, a,
-                     tiles_m);
+  hipLaunchKernelGGL((convp_kernel<BN, WNT, kP1Slots, STATS, BWD, PF, HASBX>), dim3(gx, tiles_n), dim3(G::NT), LDS, st,
+                     a, tiles_m);
   return hipGetLastError();
 }
 
@@ -1079,13 +1306,13 @@ static int pr_slots(int K) {
   return ns >= 3 ? ns : 0;
 }
 
-template <int BN, bool STATS, int BWD>
+template <int BN, bool STATS, int BWD, bool PF = false, bool HASBX = true>
 static hipError_t convpr_launch_t(const ConvnArgs& a0, int ns, hipStream_t st, int grid_mul = 1) {
   constexpr int WNT = P1Cfg<BN>::WNT;
   using G = Geo<128, BN, WNT, 3>;
   static bool attr = false;
   if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)convpr_kernel<BN, WNT, STATS, BWD>,
+    const hipError_t e = hipFuncSetAttribute((const void*)convpr_kernel<BN, WNT, STATS, BWD, PF, HASBX>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr = true;
@@ -1096,12 +1323,23 @@ static hipError_t convpr_launch_t(const ConvnArgs& a0, int ns, hipStream_t st, i
   const int tiles_m = (a.M + 127) / 128, tiles_n = a.N / BN;
   int gx = convp_grid_x(tiles_m, tiles_n) * grid_mul;
   if (gx > tiles_m) gx = tiles_m;
-  hipLaunchKernelGGL((convpr_kernel<BN, WNT, STATS, BWD>), dim3(gx, tiles_n), dim3(G::NT), lds, st, a, tiles_m);
+  hipLaunchKernelGGL((convpr_kernel<BN, WNT, STATS, BWD, PF, HASBX>), dim3(gx, tiles_n), dim3(G::NT), lds, st, a,
+                     tiles_m);
   return hipGetLastError();
 }
 
 template <int BN>
 static hipError_t convpr_launch_s(const ConvnArgs& a, int ns, hipStream_t st, int gm = 1) {
+  if constexpr (BN == 256) {
+    if (pf_ok<BN>(a)) {
+      const bool hb = a.bx != nullptr;
+      if (a.bwd == 2) return hb ? convpr_launch_t<BN, false, 2, true, true>(a, ns, st, gm)
+                                : convpr_launch_t<BN, false, 2, true, false>(a, ns, st, gm);
+      if (a.bwd == 5) return hb ? convpr_launch_t<BN, false, 5, true, true>(a, ns, st, gm)
+                                : convpr_launch_t<BN, false, 5, true, false>(a, ns, st, gm);
+      if (a.bwd == 8) return convpr_launch_t<BN, false, 8, true, true>(a, ns, st, gm);
+    }
+  }
   if (a.bwd == 1) return convpr_launch_t<BN, false, 1>(a, ns, st, gm);
   if (a.bwd == 2) return convpr_launch_t<BN, false, 2>(a, ns, st, gm);
   if (a.bwd == 3) return convpr_launch_t<BN, false, 3>(a, ns, st, gm);
@@ -1113,6 +1351,16 @@ static hipError_t convpr_launch_s(const ConvnArgs& a, int ns, hipStream_t st, in
 template <int BN>
 static hipError_t convp_launch_s(const ConvnArgs& a, hipStream_t st, int gm = 1) {
   if (const int ns = pr_slots<BN>(a.K)) return convpr_launch_s<BN>(a, ns, st, gm);
+  if constexpr (BN == 256) {
+    if (pf_ok<BN>(a)) {
+      const bool hb = a.bx != nullptr;
+      if (a.bwd == 2) return hb ? convp_launch_t<BN, false, 2, true, true>(a, st, gm)
+                                : convp_launch_t<BN, false, 2, true, false>(a, st, gm);
+      if (a.bwd == 5) return hb ? convp_launch_t<BN, false, 5, true, true>(a, st, gm)
+                                : convp_launch_t<BN, false, 5, true, false>(a, st, gm);
+      if (a.bwd == 8) return convp_launch_t<BN, false, 8, true, true>(a, st, gm);
+    }
+  }
   if (a.bwd == 1) return convp_launch_t<BN, false, 1>(a, st, gm);
   if (a.bwd == 2) return convp_launch_t<BN, false, 2>(a, st, gm);
   if (a.bwd == 3) return convp_launch_t<BN, false, 3>(a, st, gm);

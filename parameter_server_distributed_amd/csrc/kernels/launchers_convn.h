@@ -45,6 +45,9 @@ struct ConvnArgs {
   // stride-2 bwd-data phase launch (gathered variants): 0 = none, else 1 + (ph << 1 | pw); the M rows
   // of the Ho x Wo grid land at pixels (n, 2i + ph, 2j + pw) of a 2Ho x 2Wo output (convn.hip pix)
   int ophase;
+  // persistent 1x1 kernels, epilogue modes 2 / 3 / 5 / 8: load a tile's epilogue operands one tile
+  // ahead (feature convp_epi_prefetch; 0: the plain epilogue loads). Same grid, rows and results.
+  int epi_prefetch;
 };
 
 // output-channel tile of the kernel for N output channels (64, 128, 256 for N % 256 == 0), 0: unsupported

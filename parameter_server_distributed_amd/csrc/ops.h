@@ -148,7 +148,7 @@ int64_t convn_(const at::Tensor& x, const at::Tensor& w2, at::Tensor out, int64_
                int64_t pad, c10::optional<at::Tensor> part, c10::optional<at::Tensor> shift, int64_t variant,
                c10::optional<at::Tensor> x2, c10::optional<at::Tensor> bias, bool no_store,
                c10::optional<at::Tensor> apply_ss, c10::optional<at::Tensor> apply_res,
-               c10::optional<at::Tensor> apply_mask);
+               c10::optional<at::Tensor> apply_mask, bool epi_prefetch);
 int64_t convn_stats_rows_(int64_t M);
 int64_t convn_dgrad_s2_(const at::Tensor& dy, const std::vector<at::Tensor>& wph, at::Tensor out, int64_t variant,
                         c10::optional<at::Tensor> part, c10::optional<at::Tensor> bx, c10::optional<at::Tensor> bmean,
@@ -159,7 +159,7 @@ int64_t convn_bwd_(const at::Tensor& dy, const at::Tensor& w2, at::Tensor out, i
                    const at::Tensor& bmean, c10::optional<at::Tensor> bss, c10::optional<at::Tensor> bdr,
                    c10::optional<at::Tensor> bmbits, c10::optional<at::Tensor> x2,
                    c10::optional<at::Tensor> bias, c10::optional<at::Tensor> bxd, c10::optional<at::Tensor> bmean_d,
-                   c10::optional<at::Tensor> part_d);
+                   c10::optional<at::Tensor> part_d, bool epi_prefetch);
 std::vector<at::Tensor> bn_bwd_pre(const at::Tensor& g, const at::Tensor& x, c10::optional<at::Tensor> gamma,
                                    const at::Tensor& save_mean, const at::Tensor& save_invstd, const at::Tensor& part,
                                    int64_t rows, c10::optional<at::Tensor> dgamma_out,

@@ -321,7 +321,8 @@ def _convn_bwd_launch(dy, w2, cout: int, k: int, pad: int, v: int, fu: dict, pro
     part_d = torch.empty_like(part) if fu["mode"] == 3 else None
     rows = _native().convn_bwd_(dy, w2, out, k, k, 1, pad, part, v, fu["mode"], fu["bx"], fu["mean"],
                                 bss=fu.get("ss"), bdr=_dr_arg(fu.get("dr")), bmbits=fu.get("mbits"), x2=x2,
-                                bias=bias, bxd=fu.get("bxd"), bmean_d=fu.get("mean_d"), part_d=part_d)
+                                bias=bias, bxd=fu.get("bxd"), bmean_d=fu.get("mean_d"), part_d=part_d,
+                                epi_prefetch=_feat("convp_epi_prefetch"))
     if rows == 0:
         raise RuntimeError(declined)
     g = _from_2d(out, n, h, w)

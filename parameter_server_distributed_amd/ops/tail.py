@@ -104,7 +104,8 @@ def _variant(a2, w2, M: int, cin: int, cout: int, h: int, w: int, shift) -> int:
             res, ss = scratch
             out = torch.empty(M, cout, device=dev, dtype=torch.bfloat16)
             mb = torch.empty(M * cout // 8, device=dev, dtype=torch.uint8)
-            if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=v, apply_ss=ss, apply_res=res, apply_mask=mb) == 0:
+            if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=v, apply_ss=ss, apply_res=res, apply_mask=mb,
+                        epi_prefetch=_feat("convp_epi_prefetch")) == 0:
                 raise _at.Declined("convn apply pass")
             return out
         return fn
@@ -178,7 +179,8 @@ class _TailFn(torch.autograd.Function):
                                          bn_momentum(bn), bn.eps, bn.num_batches_tracked)
         out = torch.empty(M, cout, device=a2.device, dtype=torch.bfloat16)
         mbits = torch.empty(M * cout // 8, device=a2.device, dtype=torch.uint8)
-        if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=v, apply_ss=ss, apply_res=idt, apply_mask=mbits) == 0:
+        if C.convn_(a2, w2, out, 1, 1, 1, 0, variant=v, apply_ss=ss, apply_res=idt, apply_mask=mbits,
+                    epi_prefetch=_feat("convp_epi_prefetch")) == 0:
             raise RuntimeError("psd tail: convn declined the apply pass")
         y = _from_2d(out, n, h, w)
         # the consumer convolution's bwd-data epilogue runs this BN's backward reduction without its
@@ -374,14 +376,16 @@ class _DualTailFn(torch.autograd.Function):
             def fn():
                 o = torch.empty(M, cout, device=a2.device, dtype=torch.bfloat16)
                 mb = torch.empty(M * cout // 8, device=a2.device, dtype=torch.uint8)
-                if C.convn_(a2, wcat, o, 1, 1, 1, 0, variant=v, x2=xin, apply_ss=ssc, apply_mask=mb) == 0:
+                if C.convn_(a2, wcat, o, 1, 1, 1, 0, variant=v, x2=xin, apply_ss=ssc, apply_mask=mb,
+                            epi_prefetch=_feat("convp_epi_prefetch")) == 0:
                     raise _at.Declined("convn dual apply pass")
                 return o
             return fn
 
         cands = {f"psdn{v}": make(v) for v in _dual_variants(cout, w)}
         v = int(_at.choose(("tail", "dual_apply", M, c3, cd, cout), cands, next(iter(cands)))[4:])
-        if C.convn_(a2, wcat, out, 1, 1, 1, 0, variant=v, x2=xin, apply_ss=ssc, apply_mask=mbits) == 0:
+        if C.convn_(a2, wcat, out, 1, 1, 1, 0, variant=v, x2=xin, apply_ss=ssc, apply_mask=mbits,
+                    epi_prefetch=_feat("convp_epi_prefetch")) == 0:
             raise RuntimeError("psd dual tail: convn declined the apply pass")
         y = _from_2d(out, n, h, w)
         # the consumer convolution's bwd-data epilogue reduces bn3's backward without its input

@@ -62,6 +62,10 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "convn_persist": (True, "persistent layer-1 3x3 kernel (convh)"),
     "convn_p1": (True, "persistent 1x1 kernels (convp / convpr)"),
     "convn_p2": (True, "the persistent 1x1 kernel at two workgroups per CU (two-slot ring) as a candidate"),
+    "convp_epi_prefetch": (True, "persistent 1x1 kernels, 256-wide tiles, epilogue modes 2 / 5 / 8: the epilogue "
+                                 "operands (dr / residual, mask bytes, BN input) loaded one tile ahead; off: loaded "
+                                 "at the top of each tile's epilogue (same results bit for bit, "
+                                 "profiles/convp_epi_prefetch.md)"),
     "convn_bwd": (True, "producing BN's backward reduction in the bwd-data epilogue (modes 1/2)"),
     "convn_bwd3": (True, "the dual-BN tail's reduction in the bwd-data epilogue (mode 3)"),
     "convn_bwd5": (True, "stride-2 downsample gradient added on the quarter grid (mode 5)"),
