@@ -26,6 +26,9 @@ CSRC = PKG / "csrc"
 BUILD = PKG.parent / "build" / "native"
 OUT = PKG / "_C.so"
 ARCH = os.environ.get("PSD_OFFLOAD_ARCH", "gfx950")
+# Extra hipcc flags of single kernel files. lmhead_xent.hip: scalar fp32 VALU code only -- its epilogues are
+# long unrolled fp32 chains that the compiler would otherwise pair into packed fp32 operations.
+HIP_FILE_FLAGS = {"lmhead_xent.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _rocm() -> Path:
@@ -98,7 +101,8 @@ def build(verbose: bool = False, jobs: int | None = None, force: bool = False) -
     jobs_list = []
     for src in sorted(CSRC.rglob("*.hip")):
         obj = BUILD / (src.stem + ".hip.o")
-        jobs_list.append(([hipcc, *hip_flags, "-c", str(src), "-o", str(obj)], src, obj, hip_flags))
+        flags = hip_flags + HIP_FILE_FLAGS.get(src.name, [])
+        jobs_list.append(([hipcc, *flags, "-c", str(src), "-o", str(obj)], src, obj, flags))
     for src in sorted(CSRC.glob("*.cpp")):
         obj = BUILD / (src.stem + ".o")
         jobs_list.append(([cxx, *cxx_flags, "-c", str(src), "-o", str(obj)], src, obj, cxx_flags))

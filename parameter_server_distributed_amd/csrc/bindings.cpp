@@ -77,6 +77,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("xent_fwd", &xent_fwd, py::arg("x"), py::arg("labels"));
   m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("scale"),
         py::arg("lse_lo") = py::none());
+  m.def("lmhead_xent_fwd", &lmhead_xent_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("labels"),
+        py::arg("slices") = 0);
+  m.def("lmhead_xent_dz_", &lmhead_xent_dz_, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("labels"),
+        py::arg("lse"), py::arg("scale"), py::arg("dz_out"));
+  m.def("lmhead_xent_slices", &lmhead_xent_slices_, py::arg("M"), py::arg("V"));
   m.def("bn_fwd", &bn_fwd, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("residual"), py::arg("relu"), py::arg("training"), py::arg("momentum"),
         py::arg("eps"), py::arg("counter"), py::arg("ss_eval"), py::arg("mask_out") = false,
@@ -107,6 +112,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pre"), py::arg("out"), py::arg("db"), py::arg("accumulate") = false);
   m.def("gemm_splitk_", &gemm_splitk_, py::arg("A"), py::arg("B"), py::arg("a_kmajor"), py::arg("b_kmajor"),
         py::arg("out"), py::arg("accumulate") = false, py::arg("scale") = 1.0, py::arg("splits") = 0);
+  m.def("gemm_splits", &gemm_splits, py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("gemm_fp8_", &gemm_fp8_, py::arg("A"), py::arg("B"), py::arg("a_scale"), py::arg("b_scale"), py::arg("out"),
         py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("aux") = py::none(), py::arg("part") = py::none(),
         py::arg("shift") = py::none());

@@ -253,4 +253,11 @@ std::vector<at::Tensor> xent_fwd(const at::Tensor& x, const at::Tensor& labels);
 at::Tensor xent_bwd(const at::Tensor& x, const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& scale,
                     c10::optional<at::Tensor> lse_lo);
 
+// fused LM head + softmax cross-entropy: no logits in memory (lmhead_ops.cpp)
+int64_t lmhead_xent_slices_(int64_t M, int64_t V);
+std::vector<at::Tensor> lmhead_xent_fwd(const at::Tensor& x, const at::Tensor& w, c10::optional<at::Tensor> bias,
+                                        const at::Tensor& labels, int64_t slices);
+void lmhead_xent_dz_(const at::Tensor& x, const at::Tensor& w, c10::optional<at::Tensor> bias,
+                     const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& scale, at::Tensor dz_out);
+
 }  // namespace psd

@@ -26,6 +26,15 @@ unchanged. One more deviation, stated here: the embedding block is kept as it is
 with its embedding LayerNorm (with a bias) and dropout -- where Llama feeds the bare word embedding into
 the first block. ``fp8=True`` is not built for this block. ``arch="gpt"`` (the default) is the model above,
 module for module.
+
+``fused_head=True`` leaves the LM head out of ``forward``: it returns the final hidden states ``[B*S, hidden]``,
+and ``head_loss(h, labels)`` computes the next-token loss from them, the head weight and the labels through
+``ops/loss.linear_cross_entropy`` (``csrc/kernels/lmhead_xent.hip``) -- the ``[B*S, vocab]`` logits and their
+gradient, the two largest tensors of a step (2 x 2.65 GB at 8 x 4096 tokens), never exist; the backward holds
+4096 rows of logit gradient at a time. ``logits(h)`` applies the head for evaluation. The module tree and the
+``state_dict`` are the same either way (``head`` stays an ``MfmaLinear``, consumed by one autograd node), so one
+checkpoint serves both modes, and the mode composes with ``arch``, ``pos``, ``window``, padded and packed batches:
+it only replaces the last two calls. The default (False) is the model above, bit for bit.
 """
 from __future__ import annotations
 
@@ -36,7 +45,7 @@ import torch.nn as nn
 from ..ops.embedding import FusedBertEmbeddings
 from ..ops.layernorm import bump_step
 from ..ops.linear import MfmaLinear
-from ..ops.loss import cross_entropy
+from ..ops.loss import cross_entropy, linear_cross_entropy
 from .bert import BertLayer, wire_fp8_handover
 
 VOCAB = 40512
@@ -44,7 +53,7 @@ VOCAB = 40512
 
 class GPTForLM(nn.Module):
     def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False,
-                 window=None, pos="learned", rope_base=10000.0, arch="gpt", ffn=None):
+                 window=None, pos="learned", rope_base=10000.0, arch="gpt", ffn=None, fused_head=False):
         super().__init__()
         if pos not in ("learned", "rope"):
             raise ValueError(f"GPTForLM: pos must be 'learned' or 'rope', got {pos!r}")
@@ -57,6 +66,7 @@ class GPTForLM(nn.Module):
         self.vocab = vocab
         self.pos = pos
         self.arch = arch
+        self.fused_head = bool(fused_head)  # forward returns hidden states; head_loss / logits apply the head
         # pos="rope": the position table has one row, which every token reads (all-zero position ids)
         self.emb = FusedBertEmbeddings(vocab, hidden, 1 if pos == "rope" else max_pos, 2, eps=1e-12, p=dropout,
                                        seed=4242)
@@ -94,7 +104,8 @@ class GPTForLM(nn.Module):
         # (ids,) or, for a padded batch, (ids, lens): int32 [B] lengths, positions >= lens[b] are padding
         # that no attention key or query row reads. Packed documents: (ids, lens, doc_start), doc_start
         # int32 [B, S] (ops/attention.py): a token attends inside its own document only and its position
-        # id restarts there, t - doc_start[b, t]. Logits of every position: [B*S, vocab]
+        # id restarts there, t - doc_start[b, t]. Logits of every position: [B*S, vocab] (fused_head: the
+        # final hidden states [B*S, hidden] instead, for head_loss / logits)
         ids = batch[0]
         lens = batch[1] if len(batch) > 1 else None
         doc_start = batch[2] if len(batch) > 2 else None
@@ -113,11 +124,21 @@ class GPTForLM(nn.Module):
         else:
             for layer in self.layers:
                 x = layer(x, lens, doc_start)
-        return self.head(x.reshape(-1, x.shape[-1]))
+        x = x.reshape(-1, x.shape[-1])
+        return x if self.fused_head else self.head(x)
 
     @staticmethod
     def loss(logits, labels):
         return cross_entropy(logits, labels)  # fused bf16 softmax-CE kernels (ops/loss.py)
+
+    def head_loss(self, h, labels):
+        """Next-token loss from the final hidden states ``h [B*S, hidden]`` (``fused_head=True``): the head GEMM
+        and the softmax cross-entropy in one kernel, no logits in memory (ops/loss.py linear_cross_entropy)."""
+        return linear_cross_entropy(h, self.head.weight, self.head.bias, labels, mod=self.head)
+
+    def logits(self, h):
+        """The head applied to hidden states ``h`` (evaluation with ``fused_head=True``)."""
+        return self.head(h)
 
 
 def gpt_batch(batch: int, seq: int, vocab: int, device, seed: int = 0, min_len: int | None = None,

@@ -121,6 +121,9 @@ FEATURES: dict[str, tuple[bool, str]] = {
                          "attn_long); off: S > 512 goes back to SDPA on transposed views"),
     "rope": (True, "in-place rotary position embedding kernel on the packed QKV (ops/rope.py RotaryQK); off: the "
                    "out-of-place torch composite rope_ref"),
+    "head_xent": (True, "fused LM head + cross-entropy kernels where ops/loss.linear_cross_entropy is called "
+                        "(GPTForLM(fused_head=True)): no logits in memory; off: the composite "
+                        "cross_entropy(F.linear(...)) there"),
     # Llama-style block (ops/rmsnorm.py, ops/swiglu.py)
     "rmsnorm": (True, "fused residual add + dropout + RMSNorm kernels (ops/rmsnorm.py FusedAddRMSNorm); off: the "
                       "torch composite add_rmsnorm_ref"),
