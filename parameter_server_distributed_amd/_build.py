@@ -28,7 +28,10 @@ OUT = PKG / "_C.so"
 ARCH = os.environ.get("PSD_OFFLOAD_ARCH", "gfx950")
 # Extra hipcc flags of single kernel files. lmhead_xent.hip: scalar fp32 VALU code only -- its epilogues are
 # long unrolled fp32 chains that the compiler would otherwise pair into packed fp32 operations.
-HIP_FILE_FLAGS = {"lmhead_xent.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# rmsnorm.hip, swiglu.hip: the same for the MX side outputs' scaling chains (v * 2^-e per element before the fp8
+# conversion), so that a kernel's variants with and without the side output run the same scalar arithmetic.
+HIP_FILE_FLAGS = {"lmhead_xent.hip": _SCALAR_F32, "rmsnorm.hip": _SCALAR_F32, "swiglu.hip": _SCALAR_F32}
 
 
 def _rocm() -> Path:

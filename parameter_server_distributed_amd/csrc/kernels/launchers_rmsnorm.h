@@ -12,12 +12,16 @@ struct RmsArgs {
   uint16_t* r_new;         // fwd out [rows, H] (unused without h)
   uint16_t* y;             // fwd out [rows, H]
   float* rstd;             // fwd out [rows]
+  uint8_t* q8;             // fwd out or null: MX e4m3 copy of y [rows, H] (both or neither of q8 / sc8)
+  uint8_t* sc8;            // fwd out or null: its E8M0 scales [rows, H/32]
   const uint16_t* dy;      // bwd in [rows, H]
   const uint16_t* dr_new;  // bwd in or null (zero): the gradient arriving at the residual stream
   const uint16_t* rn;      // bwd in: r_new as stored
   const float* rstd_in;    // bwd in [rows]
   uint16_t* dr;            // bwd out [rows, H]
   uint16_t* dh;            // bwd out [rows, H] or null (no h, or p == 0: dh is dr)
+  uint8_t* dq8;            // bwd out or null: MX e5m2 copy of the returned dh (dh, or dr where dh is null)
+  uint8_t* dsc8;           // bwd out or null: its E8M0 scales [rows, H/32] (both or neither)
   uint16_t* dgamma;        // bwd out [H] bf16 (may be the PS gradient sink)
   float* part;             // bwd workspace [rms_bwd_blocks(rows)][H] fp32
   const int64_t* step;     // device step counter mixed into the dropout hash (may be null)

@@ -16,6 +16,9 @@ struct SwigluArgs {
   const uint16_t* da;  // bwd in [T, F] bf16
   uint16_t* a;         // fwd out [T, F] bf16
   uint16_t* dgu;       // bwd out [T, 2F] bf16
+  uint8_t* q8;         // out or null: MX copy of the launch's output, e4m3 of a [T, F] (fwd) or e5m2 of dgu
+                       // [T, 2F] (bwd); needs F % 32 == 0, 8-byte aligned (both or neither of q8 / sc8)
+  uint8_t* sc8;        // out or null: its E8M0 scales, [T, F/32] (fwd) or [T, 2F/32] (bwd)
   int64_t T;
   int64_t F;           // F % 8 == 0
   int32_t blocks;      // 0: the launcher's own grid; > 0: at most this many workgroups

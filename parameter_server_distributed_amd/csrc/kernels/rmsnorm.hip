@@ -13,20 +13,82 @@
 // [blk][H] (the four waves summed in a fixed order) -> layernorm.hip's fixed-order finalize with one partial
 // row. No atomics; nothing crosses workgroups but through that finalize; every other output element is a
 // function of its own row, so the bits do not depend on the grid. Row and element offsets are 64-bit.
+//
+// MX side outputs (the fp8 Llama block, ops/linear.py fp8="mx"): the forward can also write the MX e4m3 copy
+// of y -- the consumer Linear's forward operand -- and the backward the MX e5m2 copy of the tensor it returns
+// as dh -- the bwd-data operand of the Linear that produced h. Payload q8 [rows, H] and one E8M0 byte per 32
+// columns sc8 [rows, H/32], quantised from the bf16-rounded values the same launch stores: bitwise
+// quant_mx_kernel (fp8.hip) of that tensor, from registers, so the stand-alone pass's read of [rows, H] bf16
+// is saved. The bf16 outputs keep the bits of the variants without it (same arithmetic, stores added after).
 #include "common.h"
 #include "launchers_ln.h"
 #include "launchers_rmsnorm.h"
+#include "mx_common.h"
 #include "row_common.h"
 
 namespace psd {
 
-// ADD: with the branch h (r_new is written); without it r_new is r and only y / rstd are written
-template <int E, bool ADD>
+namespace {
+// The MX copy of one row held as v (fp32, about to be / just stored as bf16), on layernorm.hip's lane-group
+// block map (duplicated here, not shared: ln_fwd_kernel keeps its instructions). A lane's E columns are E/4
+// chunks of 4 that each lie in one 32-column block; GL lanes cover NB whole blocks (E = 12: 8 lanes, 3
+// blocks; E = 16: 2 lanes, 1 block), so a block's amax is log2(GL) xor-exchanges of NB per-lane partial
+// maxima. One 4-byte payload store per chunk; the lane holding a block's first chunk writes its scale
+// byte. qrow = q8 + r * H + c0 (4-byte aligned: E % 4 == 0), srow = sc8 + r * (H / 32). All 64 lanes call
+// it together (the row loop is wave-uniform). v is left bf16-rounded.
+template <int E, bool E5>
+__device__ __forceinline__ void mx_row_store(float (&v)[E], int lane, uint8_t* __restrict__ qrow,
+                                             uint8_t* __restrict__ srow) {
+  static_assert(E == 12 || E == 16, "MX block map written for H = 768 / 1024");
+  constexpr int NC = E / 4, GL = (E == 12) ? 8 : 2, NB = (E == 12) ? 3 : 1;
+  constexpr float fmax = E5 ? 57344.f : 448.f;
+  const int c0 = lane * E;
+  const int g0 = (lane & (GL - 1)) * E;  // first column of this lane inside its lane group's NB blocks
+  float bm[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) bm[k] = 0.f;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    float cm = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[4 * j + e] = bf16_to_f32(f32_to_bf16(v[4 * j + e]));  // as stored
+      cm = fmaxf(cm, fabsf(v[4 * j + e]));
+    }
+    const int kb = (g0 + 4 * j) >> 5;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) bm[k] = (kb == k) ? fmaxf(bm[k], cm) : bm[k];
+  }
+#pragma unroll
+  for (int o = 1; o < GL; o <<= 1)
+#pragma unroll
+    for (int k = 0; k < NB; ++k) bm[k] = fmaxf(bm[k], __shfl_xor(bm[k], o));
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const int kb = (g0 + 4 * j) >> 5;
+    float am = bm[0];
+#pragma unroll
+    for (int k = 1; k < NB; ++k) am = (kb == k) ? bm[k] : am;
+    const int eb = mx_exp_byte(am, fmax);
+    const float inv = __uint_as_float((uint32_t)(254 - eb) << 23);  // 2^(127 - eb), as mx_quant8
+    uint32_t w = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w |= (uint32_t)f32_to_f8<E5>(v[4 * j + e] * inv) << (8 * e);
+    *reinterpret_cast<uint32_t*>(qrow + 4 * j) = w;
+    if (((c0 + 4 * j) & 31) == 0) srow[(c0 + 4 * j) >> 5] = (uint8_t)eb;
+  }
+}
+}  // namespace
+
+// ADD: with the branch h (r_new is written); without it r_new is r and only y / rstd are written.
+// MX: also the MX e4m3 copy of y (q8, sc8)
+template <int E, bool ADD, bool MX>
 __global__ __launch_bounds__(256) void rms_fwd_kernel(const uint16_t* __restrict__ r_in, const uint16_t* __restrict__ h,
                                                       const uint16_t* __restrict__ gamma, uint16_t* __restrict__ r_new,
                                                       uint16_t* __restrict__ y, float* __restrict__ rstd_out,
                                                       int64_t rows, float eps, uint32_t seed,
-                                                      const int64_t* __restrict__ step, uint32_t thresh, float scale) {
+                                                      const int64_t* __restrict__ step, uint32_t thresh, float scale,
+                                                      uint8_t* __restrict__ q8, uint8_t* __restrict__ sc8) {
   constexpr int H = 64 * E;
   const int lane = threadIdx.x & 63;
   const int c0 = lane * E;
@@ -70,20 +132,23 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const uint16_t* __restrict
 #pragma unroll
     for (int i = 0; i < E; ++i) xv[i] = (xv[i] * rstd) * g[i];
     store_e<E>(y + off, xv);
+    if constexpr (MX) mx_row_store<E, false>(xv, lane, q8 + off, sc8 + r * (H / 32));
     if (lane == 0) rstd_out[r] = rstd;
   }
 }
 
 // DRN: the gradient dr_new arriving at the residual stream is added (else it counts as zero and is not
-// read). DH: the pre-dropout gradient dh is written too (p > 0 with a branch; at p == 0 dh is dr itself)
-template <int E, bool DRN, bool DH>
+// read). DH: the pre-dropout gradient dh is written too (p > 0 with a branch; at p == 0 dh is dr itself).
+// MXG: also the MX e5m2 copy (q8, sc8) of the tensor returned as dh: dh with DH, else dr
+template <int E, bool DRN, bool DH, bool MXG>
 __global__ __launch_bounds__(256) void rms_bwd_kernel(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ drn,
                                                       const uint16_t* __restrict__ rnew,
                                                       const float* __restrict__ rstd_in,
                                                       const uint16_t* __restrict__ gamma, uint16_t* __restrict__ dr,
                                                       uint16_t* __restrict__ dh, float* __restrict__ part, int64_t rows,
                                                       uint32_t seed, const int64_t* __restrict__ step, uint32_t thresh,
-                                                      float scale) {
+                                                      float scale, uint8_t* __restrict__ q8,
+                                                      uint8_t* __restrict__ sc8) {
   constexpr int H = 64 * E;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int c0 = lane * E;
@@ -140,6 +205,7 @@ __global__ __launch_bounds__(256) void rms_bwd_kernel(const uint16_t* __restrict
       for (int i = 0; i < E; ++i) dv[i] = kp[i] ? dv[i] * scale : 0.f;  // from the fp32 dr, before its rounding
       store_e<E>(dh + off, dv);
     }
+    if constexpr (MXG) mx_row_store<E, true>(dv, lane, q8 + off, sc8 + r * (H / 32));
   }
   // block partials of dgamma: [blk][H], waves summed in a fixed order
   __shared__ float red[4][H];
@@ -170,16 +236,21 @@ hipError_t launch_rms_fwd(const RmsArgs& a, hipStream_t st) {
   const bool add = a.h != nullptr;
   const uint32_t th = add ? keep_thresh(a.p) : 0u;
   const float sc = (add && a.p > 0.f) ? 1.f / (1.f - a.p) : 1.f;
-#define PSD_RMSF(E, ADD)                                                                                        \
-  hipLaunchKernelGGL((rms_fwd_kernel<E, ADD>), dim3(blocks), dim3(256), 0, st, a.r, a.h, a.gamma, a.r_new, a.y, \
-                     a.rstd, a.rows, a.eps, a.seed, a.step, th, sc)
-  if (a.H == 768) {
-    if (add) PSD_RMSF(12, true);
-    else PSD_RMSF(12, false);
-  } else {
-    if (add) PSD_RMSF(16, true);
-    else PSD_RMSF(16, false);
-  }
+  if ((a.q8 == nullptr) != (a.sc8 == nullptr)) return hipErrorInvalidValue;
+  const bool mx = a.q8 != nullptr;
+#define PSD_RMSF(E, ADD, MX)                                                                                        \
+  hipLaunchKernelGGL((rms_fwd_kernel<E, ADD, MX>), dim3(blocks), dim3(256), 0, st, a.r, a.h, a.gamma, a.r_new, a.y, \
+                     a.rstd, a.rows, a.eps, a.seed, a.step, th, sc, a.q8, a.sc8)
+#define PSD_RMSF_E(E)                         \
+  do {                                        \
+    if (add && mx) PSD_RMSF(E, true, true);   \
+    else if (add) PSD_RMSF(E, true, false);   \
+    else if (mx) PSD_RMSF(E, false, true);    \
+    else PSD_RMSF(E, false, false);           \
+  } while (0)
+  if (a.H == 768) PSD_RMSF_E(12);
+  else PSD_RMSF_E(16);
+#undef PSD_RMSF_E
 #undef PSD_RMSF
   return hipGetLastError();
 }
@@ -191,19 +262,27 @@ hipError_t launch_rms_bwd(const RmsArgs& a, hipStream_t st) {
   const bool drn = a.dr_new != nullptr;
   const bool dh = a.dh != nullptr;  // null at p == 0: dh is dr, written once
   const float sc = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
-#define PSD_RMSB(E, DRN, DH)                                                                                      \
-  hipLaunchKernelGGL((rms_bwd_kernel<E, DRN, DH>), dim3(blocks), dim3(256), 0, st, a.dy, a.dr_new, a.rn, a.rstd_in, \
-                     a.gamma, a.dr, a.dh, a.part, a.rows, a.seed, a.step, th, sc)
-#define PSD_RMSB_E(E)                      \
-  do {                                     \
-    if (drn && dh) PSD_RMSB(E, true, true); \
-    else if (drn) PSD_RMSB(E, true, false); \
-    else if (dh) PSD_RMSB(E, false, true);  \
-    else PSD_RMSB(E, false, false);         \
+  if ((a.dq8 == nullptr) != (a.dsc8 == nullptr)) return hipErrorInvalidValue;
+  const bool mx = a.dq8 != nullptr;
+#define PSD_RMSB(E, DRN, DH, MXG)                                                                                \
+  hipLaunchKernelGGL((rms_bwd_kernel<E, DRN, DH, MXG>), dim3(blocks), dim3(256), 0, st, a.dy, a.dr_new, a.rn,    \
+                     a.rstd_in, a.gamma, a.dr, a.dh, a.part, a.rows, a.seed, a.step, th, sc, a.dq8, a.dsc8)
+#define PSD_RMSB_M(E, MXG)                        \
+  do {                                            \
+    if (drn && dh) PSD_RMSB(E, true, true, MXG);  \
+    else if (drn) PSD_RMSB(E, true, false, MXG);  \
+    else if (dh) PSD_RMSB(E, false, true, MXG);   \
+    else PSD_RMSB(E, false, false, MXG);          \
+  } while (0)
+#define PSD_RMSB_E(E)            \
+  do {                           \
+    if (mx) PSD_RMSB_M(E, true); \
+    else PSD_RMSB_M(E, false);   \
   } while (0)
   if (a.H == 768) PSD_RMSB_E(12);
   else PSD_RMSB_E(16);
 #undef PSD_RMSB_E
+#undef PSD_RMSB_M
 #undef PSD_RMSB
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

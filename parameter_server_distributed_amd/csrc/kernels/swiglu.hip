@@ -18,8 +18,26 @@
 // stays below what the loads take. exp(-g) = inf for g < -88 gives sig = 0 and a = dg = du = 0, the limits.
 // No LDS, no atomics, nothing summed: each output is a function of its own inputs, so the bits do not
 // depend on the grid and two runs are equal.
+//
+// MX side outputs (template MX, SwigluArgs q8 / sc8; the fp8 Llama block): the forward also writes the MX
+// e4m3 copy of a [T, F] -- the down Linear's forward operand -- and the backward the MX e5m2 copy of dgu
+// [T, 2F] -- the gate/up Linear's bwd-data operand: fp8 payload plus one E8M0 byte per 32 columns, bitwise
+// quant_mx_kernel (fp8.hip) of the bf16 tensor the same launch stores, from the registers that hold it. A
+// lane's item is 8 consecutive columns, so a 32-column MX block is the 4 items of one aligned lane quad and
+// mx_quant8 (mx_common.h: two quad-permute DPPs for the amax) applies as in the stand-alone pass; one 8-byte
+// payload store per lane and half, the quad's first lane stores the scale byte.
+// Why the quad exchange is valid -- the variant requires F % 32 == 0 (checked by the launcher):
+//   * L = F / 8 is then a multiple of 4. Lanes 4q .. 4q+3 start at the consecutive item numbers idx0 =
+//     4k .. 4k+3; row0 = idx0 / L is the same for the four (a multiple of 4 divides their common base), and
+//     c = idx0 - row0 L = 4m .. 4m+3: one row, one block, in element order.
+//   * the grid-stride is gridDim * 256, a multiple of 4, so srem = stride % L is a multiple of 4 and
+//     srow is common: walk_next adds the same srem to the four c, the sums are again 4m' .. 4m'+3, and L % 4
+//     == 0 makes `c >= L` one decision for the quad. By induction the quad stays in one row and one block.
+//   * the loop condition row < T is therefore also one decision per quad: a quad is wholly inside the
+//     tensor or has wholly left the loop, so the DPP reads only lanes that hold this block's items.
 #include "common.h"
 #include "launchers_swiglu.h"
+#include "mx_common.h"
 
 namespace psd {
 
@@ -44,8 +62,28 @@ __device__ __forceinline__ void walk_next(ItemWalk& w, uint32_t L, int64_t srow,
   }
   w.row += srow;
 }
+
+// t -> the values its bf16 store keeps (what the MX copy is the quantisation of)
+__device__ __forceinline__ void round8_bf16(float (&t)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) t[e] = bf16_to_f32(f32_to_bf16(t[e]));
+}
+
+// The quad's MX block of 32 columns starting at element offset `off` (a multiple of 8; the quad's first lane
+// has off % 32 == 0) of a contiguous tensor whose rows are whole blocks: payload at q8 + off, scale byte at
+// sc8[off / 32]. All four lanes of the quad call it together.
+template <bool E5>
+__device__ __forceinline__ void mx_store8(float (&t)[8], uint8_t* __restrict__ q8, uint8_t* __restrict__ sc8,
+                                          int64_t off) {
+  round8_bf16(t);
+  uint2 qb;
+  const int eb = mx_quant8<E5>(t, qb);
+  *reinterpret_cast<uint2*>(q8 + off) = qb;
+  if ((off & 31) == 0) sc8[off >> 5] = (uint8_t)eb;
+}
 }  // namespace
 
+template <bool MX>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(SwigluArgs a, uint32_t L, int64_t srow, uint32_t srem) {
   const int64_t F = a.F;
   for (ItemWalk w = walk_start(L); w.row < a.T; walk_next(w, L, srow, srem)) {
@@ -55,10 +93,13 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(SwigluArgs a, uint32_t 
     load8_bf16(p + F, u);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (g[e] * sigmoid_f32(g[e])) * u[e];
-    store8_bf16(a.a + w.row * F + (int64_t)w.c * 8, o);
+    const int64_t off = w.row * F + (int64_t)w.c * 8;
+    store8_bf16(a.a + off, o);
+    if constexpr (MX) mx_store8<false>(o, a.q8, a.sc8, off);
   }
 }
 
+template <bool MX>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(SwigluArgs a, uint32_t L, int64_t srow, uint32_t srem) {
   const int64_t F = a.F;
   for (ItemWalk w = walk_start(L); w.row < a.T; walk_next(w, L, srow, srem)) {
@@ -76,6 +117,10 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(SwigluArgs a, uint32_t 
     }
     store8_bf16(a.dgu + off2, dg);
     store8_bf16(a.dgu + off2 + F, du);
+    if constexpr (MX) {  // F % 32 == 0: off2 + F is block-aligned where off2 is
+      mx_store8<true>(dg, a.q8, a.sc8, off2);
+      mx_store8<true>(du, a.q8, a.sc8, off2 + F);
+    }
   }
 }
 
@@ -84,6 +129,8 @@ template <typename K>
 hipError_t launch_swiglu(K kernel, const SwigluArgs& a, hipStream_t st) {
   // L < 2^28 keeps the 32-bit item-in-row arithmetic of the walk exact
   if (a.T < 0 || a.F < 0 || a.F % 8 != 0 || a.F / 8 >= (1 << 28) || a.blocks < 0) return hipErrorInvalidValue;
+  // the MX variants: both pointers, and rows of whole 32-column blocks (the quad argument in the header)
+  if ((a.q8 == nullptr) != (a.sc8 == nullptr) || (a.q8 != nullptr && a.F % 32 != 0)) return hipErrorInvalidValue;
   if (a.T == 0 || a.F == 0) return hipSuccess;
   const int64_t L = a.F / 8;
   if (a.T > INT64_MAX / L) return hipErrorInvalidValue;
@@ -97,12 +144,12 @@ hipError_t launch_swiglu(K kernel, const SwigluArgs& a, hipStream_t st) {
 
 hipError_t launch_swiglu_fwd(const SwigluArgs& a, hipStream_t st) {
   if (a.T > 0 && a.F > 0 && (!a.gu || !a.a)) return hipErrorInvalidValue;
-  return launch_swiglu(swiglu_fwd_kernel, a, st);
+  return a.q8 ? launch_swiglu(swiglu_fwd_kernel<true>, a, st) : launch_swiglu(swiglu_fwd_kernel<false>, a, st);
 }
 
 hipError_t launch_swiglu_bwd(const SwigluArgs& a, hipStream_t st) {
   if (a.T > 0 && a.F > 0 && (!a.gu || !a.da || !a.dgu)) return hipErrorInvalidValue;
-  return launch_swiglu(swiglu_bwd_kernel, a, st);
+  return a.q8 ? launch_swiglu(swiglu_bwd_kernel<true>, a, st) : launch_swiglu(swiglu_bwd_kernel<false>, a, st);
 }
 
 }  // namespace psd

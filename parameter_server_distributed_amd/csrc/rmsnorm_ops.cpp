@@ -42,13 +42,34 @@ int64_t check_hidden(const char* op, const at::Tensor& t, const char* name) {
   TORCH_CHECK(rms_supported((int)H), op, ": ", name, " must have a last dimension (H) of 768 or 1024, got ", H);
   return H;
 }
+// the MX side output of `like` [rows, H]: payload `q` (fp8 dtype `qt`, like's shape) and E8M0 scales `sc` (uint8,
+// one per 32 columns), both or neither; true when given
+bool check_mx(const char* op, const c10::optional<at::Tensor>& q, const c10::optional<at::Tensor>& sc,
+              const at::Tensor& like, at::ScalarType qt, const char* qname, const char* scname, const char* like_name) {
+  TORCH_CHECK(given(q) == given(sc), op, ": ", qname, " and ", scname, " come together");
+  if (!given(q)) return false;
+  TORCH_CHECK(q->is_cuda() && q->device() == like.device(), op, ": ", qname, " must be on ", like_name, "'s device");
+  TORCH_CHECK(q->scalar_type() == qt, op, ": ", qname, " must be ", qt, ", got ", q->scalar_type());
+  TORCH_CHECK(q->is_contiguous(), op, ": ", qname, " must be contiguous");
+  TORCH_CHECK(q->sizes() == like.sizes(), op, ": ", qname, " must have ", like_name, "'s shape ", like.sizes(), ", got ",
+              q->sizes());
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q->data_ptr()) & 3) == 0, op, ": ", qname, " must be 4-byte aligned");
+  TORCH_CHECK(sc->is_cuda() && sc->device() == like.device(), op, ": ", scname, " must be on ", like_name, "'s device");
+  TORCH_CHECK(sc->scalar_type() == at::kByte, op, ": ", scname, " must be uint8, got ", sc->scalar_type());
+  TORCH_CHECK(sc->is_contiguous(), op, ": ", scname, " must be contiguous");
+  TORCH_CHECK(sc->numel() == like.numel() / 32, op, ": ", scname, " must hold ", like.numel() / 32,
+              " bytes (one per 32 columns of ", like_name, "), got ", sc->sizes());
+  return true;
+}
 void check_p(const char* op, double p) { TORCH_CHECK(p >= 0.0 && p < 1.0, op, ": p must be in [0, 1), got ", p); }
 }  // namespace
 
 // r_new = bf16(r + dropout_p(h)), rstd = rsqrt(mean(r_new^2) + eps) [rows] fp32, y = bf16(r_new * rstd * gamma).
 // Without h, r_new is r itself (the same tensor is returned, nothing is written) and p / seed / step are ignored.
+// q8_out / sc8_out: also the MX e4m3 copy of y (bitwise quant_mx_ of y), float8_e4m3fn like r and uint8 [rows, H/32].
 std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h, const at::Tensor& gamma, double eps,
-                                double p, int64_t seed, c10::optional<at::Tensor> step) {
+                                double p, int64_t seed, c10::optional<at::Tensor> step,
+                                c10::optional<at::Tensor> q8_out, c10::optional<at::Tensor> sc8_out) {
   const char* op = "psd rms_fwd";
   check_act(op, r, "r");
   const int64_t H = check_hidden(op, r, "r");
@@ -60,6 +81,7 @@ std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h
     check_p(op, p);
     stp = check_step(op, step, r);
   }
+  const bool mx = check_mx(op, q8_out, sc8_out, r, at::kFloat8_e4m3fn, "q8_out", "sc8_out", "r");
   const c10::DeviceGuard g(r.device());
   const int64_t rows = r.numel() / H;
   at::Tensor r_new = add ? at::empty_like(r) : r;
@@ -72,6 +94,8 @@ std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h
   a.r_new = add ? bf16_mut(r_new) : nullptr;
   a.y = bf16_mut(y);
   a.rstd = rstd.data_ptr<float>();
+  a.q8 = mx ? reinterpret_cast<uint8_t*>(q8_out->data_ptr()) : nullptr;
+  a.sc8 = mx ? sc8_out->data_ptr<uint8_t>() : nullptr;
   a.step = stp;
   a.rows = rows;
   a.H = (int32_t)H;
@@ -84,10 +108,12 @@ std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h
 
 // dr = bf16(dr_new + rstd * (g - xh * mean(g * xh))) with xh = r_new * rstd, g = dy * gamma; dh = bf16 of the
 // fp32 dr * keep / (1 - p) (p == 0: the tensor dr itself; had_h false: none); dgamma = column sums of dy * xh
-// into dgamma_out when given.
+// into dgamma_out when given. dq8_out / dsc8_out (with had_h only): also the MX e5m2 copy of the returned dh
+// (bitwise quant_mx_ of it, e5m2), float8_e5m2 like r_new and uint8 [rows, H/32].
 std::vector<at::Tensor> rms_bwd(const at::Tensor& dy, c10::optional<at::Tensor> dr_new, const at::Tensor& r_new,
                                 const at::Tensor& rstd, const at::Tensor& gamma, double p, int64_t seed,
-                                c10::optional<at::Tensor> step, bool had_h, c10::optional<at::Tensor> dgamma_out) {
+                                c10::optional<at::Tensor> step, bool had_h, c10::optional<at::Tensor> dgamma_out,
+                                c10::optional<at::Tensor> dq8_out, c10::optional<at::Tensor> dsc8_out) {
   const char* op = "psd rms_bwd";
   check_act(op, r_new, "r_new");
   const int64_t H = check_hidden(op, r_new, "r_new");
@@ -102,6 +128,8 @@ std::vector<at::Tensor> rms_bwd(const at::Tensor& dy, c10::optional<at::Tensor> 
   check_p(op, p);
   const int64_t* stp = check_step(op, step, r_new);
   if (given(dgamma_out)) check_gamma(op, *dgamma_out, r_new, H, "dgamma_out");
+  const bool mx = check_mx(op, dq8_out, dsc8_out, r_new, at::kFloat8_e5m2, "dq8_out", "dsc8_out", "r_new");
+  TORCH_CHECK(!mx || had_h, op, ": dq8_out is the MX copy of dh and needs had_h");
   const c10::DeviceGuard g(r_new.device());
   at::Tensor dr = at::empty_like(r_new);
   at::Tensor dh;
@@ -116,6 +144,8 @@ std::vector<at::Tensor> rms_bwd(const at::Tensor& dy, c10::optional<at::Tensor> 
   a.gamma = bf16(gamma);
   a.dr = bf16_mut(dr);
   a.dh = (had_h && p > 0.0) ? bf16_mut(dh) : nullptr;
+  a.dq8 = mx ? reinterpret_cast<uint8_t*>(dq8_out->data_ptr()) : nullptr;
+  a.dsc8 = mx ? dsc8_out->data_ptr<uint8_t>() : nullptr;
   a.dgamma = bf16_mut(dgamma);
   a.part = part.data_ptr<float>();
   a.step = stp;

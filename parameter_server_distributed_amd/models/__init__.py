@@ -98,8 +98,10 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
         from .gpt import GPTForLM, gpt_batch
 
         seq = kw.get("seq_len", 512)
+        fp8 = kw.get("fp8", False)  # "mx" passes through (the spelling the Llama block takes); else a flag
         m = prepare(GPTForLM(**{k: v for k, v in kw.items() if k in ("layers", "hidden", "heads", "vocab")},
-                             max_pos=max(512, seq), fp8=bool(kw.get("fp8", False)), window=kw.get("window"),
+                             max_pos=max(512, seq), fp8=fp8 if isinstance(fp8, str) else bool(fp8),
+                             window=kw.get("window"),
                              pos=kw.get("pos", "learned"), rope_base=kw.get("rope_base", 10000.0),
                              arch=kw.get("arch", "gpt"), ffn=kw.get("ffn"),
                              fused_head=bool(kw.get("fused_head", False))),

@@ -24,8 +24,11 @@ the stack ends with a final ``norm_f``. The forward threads the residual stream 
 ``(r, h)`` through the blocks. ``pos``, ``window``, padded batches and packed documents compose with it
 unchanged. One more deviation, stated here: the embedding block is kept as it is -- ``FusedBertEmbeddings``
 with its embedding LayerNorm (with a bias) and dropout -- where Llama feeds the bare word embedding into
-the first block. ``fp8=True`` is not built for this block. ``arch="gpt"`` (the default) is the model above,
-module for module.
+the first block. ``fp8="mx"`` puts the block's four Linears (qkv, proj, gate_up, down) on the MX fp8 GEMMs, their
+operands written by the fused RMSNorm / SwiGLU kernels where those produce them (``models/llama_block.py``); the
+head, the embeddings and the attention stay bf16. (``fp8=True`` is not built for this block and raises: the Llama
+block takes ``fp8="mx"``; for ``arch="gpt"`` ``"mx"`` means what ``True`` means.) ``arch="gpt"`` (the default) is
+the model above, module for module.
 
 ``fused_head=True`` leaves the LM head out of ``forward``: it returns the final hidden states ``[B*S, hidden]``,
 and ``head_loss(h, labels)`` computes the next-token loss from them, the head weight and the labels through
@@ -59,8 +62,11 @@ class GPTForLM(nn.Module):
             raise ValueError(f"GPTForLM: pos must be 'learned' or 'rope', got {pos!r}")
         if arch not in ("gpt", "llama"):
             raise ValueError(f"GPTForLM: arch must be 'gpt' or 'llama', got {arch!r}")
-        if arch == "llama" and fp8:
-            raise ValueError("GPTForLM: fp8=True with arch='llama' is not built (the Llama block's Linears are bf16)")
+        if not (fp8 is False or fp8 is True or (isinstance(fp8, str) and fp8 == "mx")):
+            raise ValueError(f"GPTForLM: fp8 must be False, True or 'mx', got {fp8!r}")
+        if arch == "llama" and fp8 is True:
+            raise ValueError("GPTForLM: fp8=True with arch='llama' is not built: the Llama block takes fp8='mx' "
+                             "(MX fp8 Linears)")
         if arch == "gpt" and ffn is not None and int(ffn) != 4 * hidden:
             raise ValueError(f"GPTForLM: arch='gpt' has the fixed FFN width 4 * hidden = {4 * hidden}, got ffn={ffn}")
         self.vocab = vocab
@@ -79,13 +85,19 @@ class GPTForLM(nn.Module):
             from .llama_block import LlamaLayer, default_ffn
 
             ffn = default_ffn(hidden) if ffn is None else int(ffn)
-            self.layers = nn.ModuleList([LlamaLayer(hidden, heads, ffn, dropout, i, window=window, rope=rope)
+            self.layers = nn.ModuleList([LlamaLayer(hidden, heads, ffn, dropout, i, window=window, rope=rope, fp8=fp8)
                                          for i in range(layers)])
             # the last block's branch joins the stream here; seeds 2 * i + 1, 2 * i + 2 belong to block i
             self.norm_f = FusedAddRMSNorm(hidden, eps=1e-6, p=dropout, seed=2 * layers + 1)
+            if fp8:
+                # the norm that takes a block's branch h = down(..) writes down's MX e5m2 output gradient: the
+                # next block's norm1, and norm_f for the last block (the in-block hand-overs: LlamaLayer)
+                for i, layer in enumerate(self.layers):
+                    nxt = self.layers[i + 1].norm1 if i + 1 < layers else self.norm_f
+                    nxt.psd_mx_grad_to(layer.down)
             self.head = MfmaLinear(hidden, vocab, bias=False)
         else:
-            self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=fp8,
+            self.layers = nn.ModuleList([BertLayer(hidden, heads, 4 * hidden, dropout, i, causal=True, fp8=bool(fp8),
                                                    window=window, rope=rope) for i in range(layers)])
             wire_fp8_handover(self.layers)
             self.head = MfmaLinear(hidden, vocab)

@@ -13,6 +13,17 @@ stream is never read by an add of its own::
 
 and returns ``(r, h)``; the owner closes the stack with one more norm, ``norm_f(r, h)``. The first block
 gets ``h=None``.
+
+``fp8="mx"``: the four Linears run the MX fp8 recipe of ``ops/linear.py`` (forward and bwd-data on the block-scaled
+MFMA; the attention stays bf16), and the fused kernels around them write their MX operands as side outputs of the
+passes they already make (feature ``fp8_llama_handover``), instead of one ``quantize_mx`` pass each::
+
+    forward   norm1 -> qkv,  norm2 -> gate_up,  act -> down        (e4m3 inputs)
+    backward  act -> gate_up,  norm2 -> proj,  the next norm1 / norm_f -> down   (e5m2 output gradients)
+
+The last one crosses blocks and is wired by the owner (``models/gpt.py``). ``proj``'s input (the attention output)
+and ``qkv``'s output gradient (the attention's ``dqkv``) come from kernels that do not write MX copies: those two
+operands stay ``quantize_mx`` passes.
 """
 from __future__ import annotations
 
@@ -31,8 +42,11 @@ def default_ffn(hidden: int) -> int:
 
 
 class LlamaLayer(nn.Module):
-    def __init__(self, hidden=768, heads=12, ffn=2048, dropout=0.1, index=0, window=None, rope=None, eps=1e-6):
+    def __init__(self, hidden=768, heads=12, ffn=2048, dropout=0.1, index=0, window=None, rope=None, eps=1e-6,
+                 fp8=False):
         super().__init__()
+        if not (fp8 is False or (isinstance(fp8, str) and fp8 == "mx")):
+            raise ValueError(f"LlamaLayer: fp8 must be False or 'mx', got {fp8!r}")
         # rope: (max_pos, base) -- rotary position embedding of Q and K between the QKV Linear and the
         # attention (ops/rope.py); None: no such module
         self.rot = None
@@ -43,15 +57,21 @@ class LlamaLayer(nn.Module):
         self.heads = heads
         # seeds as BertLayer's: attention 1000 + index, the two norm sites 2 * index + 1 and 2 * index + 2
         self.norm1 = FusedAddRMSNorm(hidden, eps=eps, p=dropout, seed=2 * index + 1)
-        self.qkv = MfmaLinear(hidden, 3 * hidden, bias=False)
+        self.qkv = MfmaLinear(hidden, 3 * hidden, bias=False, fp8=fp8)
         self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=True, window=window)
-        self.proj = MfmaLinear(hidden, hidden, bias=False)
+        self.proj = MfmaLinear(hidden, hidden, bias=False, fp8=fp8)
         self.norm2 = FusedAddRMSNorm(hidden, eps=eps, p=dropout, seed=2 * index + 2)
         # gate_proj and up_proj as one Linear: its output is the packed [.., 2 ffn] the activation reads in place
-        self.gate_up = MfmaLinear(hidden, 2 * ffn, bias=False)
+        self.gate_up = MfmaLinear(hidden, 2 * ffn, bias=False, fp8=fp8)
         self.act = SwiGLU()
-        self.down = MfmaLinear(ffn, hidden, bias=False)
+        self.down = MfmaLinear(ffn, hidden, bias=False, fp8=fp8)
         self.p = dropout
+        if fp8:  # the MX operands the fused kernels write for the Linears next to them (module docstring)
+            self.norm1.psd_mx_output_to(self.qkv)
+            self.norm2.psd_mx_output_to(self.gate_up)
+            self.act.psd_mx_output_to(self.down)
+            self.act.psd_mx_grad_to(self.gate_up)
+            self.norm2.psd_mx_grad_to(self.proj)
 
     def forward(self, r, h=None, lens=None, doc_start=None):
         # doc_start: packed documents (ops/attention.py), passed on to the rotation and the attention

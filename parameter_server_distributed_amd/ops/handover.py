@@ -86,6 +86,26 @@ def take(mod, attr: str, t: torch.Tensor, strides: bool, mismatch: str | None = 
     return None
 
 
+def mx_grad_token(lin, out):
+    """The forward token of the fp8 Linear ``lin`` if ``out`` is the output of its latest forward and that forward
+    ran the MX recipe -- then a fused backward that computes ``out``'s gradient may leave its MX e5m2 copy on
+    ``lin._psd_dq8_pending`` as ``(token, Q8Pending)`` (ops/rmsnorm.py, ops/swiglu.py) -- else None."""
+    src = getattr(out, "_psd_src", None) if (lin is not None and out is not None) else None
+    if src is None or src[0] is not lin or src[1] != lin._psd_tok or not lin._psd_ran_mx:
+        return None
+    return src[1]
+
+
+def take_dq8(mod, tok: int, dy2: torch.Tensor):
+    """Consume ``mod._psd_dq8_pending`` (cleared): the Q8Pending if it carries the forward token ``tok`` and was
+    made for exactly ``dy2`` (data_ptr and shape), else None."""
+    pend = getattr(mod, "_psd_dq8_pending", None)
+    mod._psd_dq8_pending = None
+    if pend is None or pend[0] != tok or not same(pend[1].t, dy2, strides=False):
+        return None
+    return pend[1]
+
+
 class StridedDr:
     """A residual-branch gradient handed to a BN (``_psd_pending_dr``) by a stride-2 1x1 (downsample)
     convolution, kept on its quarter grid: ``t4`` = dY . W of the strided positions, [N, C, H/2, W/2]

@@ -18,11 +18,14 @@ the split-K form of the same MFMA kernel (``gemm_fp8_splitk_``: fp32 slabs, dete
 where the bf16 route writes (the grad sink's bf16 / fp32 view, else a fresh bf16 tensor). The bias gradient
 stays as it is.
   q(x)     the MX e4m3 copy the producing fused LayerNorm wrote (ops/layernorm.py psd_mx_output_to,
-           feature ``fp8_ln_handover``), else one ``quantize_mx`` pass
+           feature ``fp8_ln_handover``) or the Llama block's fused RMSNorm / SwiGLU wrote (ops/rmsnorm.py,
+           ops/swiglu.py, feature ``fp8_llama_handover``), else one ``quantize_mx`` pass
   q(W)     the MX e4m3 copy the PS data plane published (``pull_dtype="fp8"``, the ``_psd_w8`` hook of
            parallel/flat.py), else one ``quantize_mx`` pass
   q_t(W)   ``quantize_mx_t``: W^T [in, out] with blocks along ``out`` in one pass over the bf16 W
-           (kernels/fp8_t.hip); q_e5m2(dy') one ``quantize_mx`` pass (feature ``fp8_dgrad``; off: bf16 dgrad)
+           (kernels/fp8_t.hip); q_e5m2(dy') the MX e5m2 copy the fused RMSNorm / SwiGLU backward that produced
+           dy' wrote (``psd_mx_grad_to``; not with ``fp8_wgrad``), else one ``quantize_mx`` pass (feature
+           ``fp8_dgrad``; off: bf16 dgrad)
   q_t(dy') with ``fp8_wgrad``: the transposed e4m3 half of one ``quantize_mx_dual`` pass over dy' whose e5m2
            row half (bitwise ``quantize_mx``'s) feeds bwd-data, else ``quantize_mx_t(dy')``; q_t(x) one
            ``quantize_mx_t`` pass over the saved bf16 x
@@ -54,7 +57,7 @@ from ..utils.config import feature as _feat
 from .. import native
 from . import autotune as _at
 from .fp8_common import FP8_CALLS, mx_weight
-from .handover import take
+from .handover import take, take_dq8
 
 ACTS = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 
@@ -202,6 +205,7 @@ class _LinearFn(torch.autograd.Function):
         # stopped between the two -- an exception, autograd.grad on a partial graph -- can never
         # leave a stale gradient for the next step)
         ctx.tok = mod._psd_tok = getattr(mod, "_psd_tok", 0) + 1
+        mod._psd_ran_mx = use_mx  # of this forward: what a producer of dy's MX copy asks (handover.mx_grad_token)
         ctx.has_bias = bias is not None
         ctx.in_shape = shp
         # GELU hand-over (MfmaLinear.psd_gelu_input_from): this Linear's bwd-data GEMM applies the
@@ -230,6 +234,9 @@ class _LinearFn(torch.autograd.Function):
         x2, w, keep, pre_src = ctx.saved_tensors
         dy2 = dy.reshape(-1, w.shape[0]).contiguous()
         sink = getattr(ctx.mod, "_psd_grad_sink", None)
+        # the MX e5m2 copy of dy from the fused backward that produced it (ops/rmsnorm.py / ops/swiglu.py
+        # psd_mx_grad_to): taken -- and cleared -- here, used below only for exactly dy2
+        dq8 = take_dq8(ctx.mod, ctx.tok, dy2)
         db = None
         hands = ctx.mod._psd_gelu_hands
         hand = hands.pop(ctx.tok, None)
@@ -274,6 +281,9 @@ class _LinearFn(torch.autograd.Function):
             # dx = q_e5m2(dy') . q_t(W): A = dy' [M, out] e5m2, B = W^T [in, out] e4m3, MX blocks along out
             if wgrad8:  # one read of dy' for both of its MX copies; the row half is bitwise quantize_mx's
                 dyq, sdy, dyT, sdyT = quantize_mx_dual(dy2, e5m2_row=True, e5m2_t=False)
+            elif dq8 is not None:
+                dyq, sdy = dq8.q.view(dy2.shape), dq8.scales
+                ctx.mod.psd_mx_grad_handovers += 1
             else:
                 dyq, sdy = quantize_mx(dy2, e5m2=True)
             wtq, swt = quantize_mx_t(w)
@@ -337,6 +347,9 @@ class MfmaLinear(nn.Linear):
         self.fp8 = fp8
         self._psd_q8_pending = None  # ops.handover.Q8Pending of the input, left by the producing LayerNorm
         self.psd_mx_handovers = 0  # forwards that took it (tests / logs)
+        self._psd_dq8_pending = None  # (forward token, Q8Pending of dy) left by the fused backward that produced dy
+        self.psd_mx_grad_handovers = 0  # backwards that took it
+        self._psd_ran_mx = False  # whether the latest forward ran the MX recipe
         self._psd_pending_dx: list = []  # gradients of the input handed over by a residual LayerNorm
         self._psd_gelu_from = None  # psd_gelu_input_from: the GELU Linear whose output is this one's input
         self._psd_gelu_hands: dict = {}  # forward token -> (pre-activation gradient, bias gradient) from the consumer

@@ -11,6 +11,12 @@ Dropout masks come from LayerNorm's counter-based hash of (per-site seed, device
 graph. The weight gradient goes straight into the PS flat-gradient buffer when the data plane installed a
 grad sink.
 
+MX hand-overs of the fp8 Llama block (feature ``fp8_llama_handover``, ``ops/linear.py`` ``fp8="mx"``): the
+forward also writes the MX e4m3 copy of ``y`` for the Linear declared with ``psd_mx_output_to`` (its forward
+operand), and the backward the MX e5m2 copy of ``dh`` for the Linear declared with ``psd_mx_grad_to`` (the one
+that produced ``h``: its bwd-data operand). Both are side outputs of the same launches, bitwise ``quantize_mx``
+of the bf16 tensors they store, so the consumers skip their quantise passes.
+
 CPU tensors, other dtypes or hidden sizes, and feature ``rmsnorm`` off use the composite
 ``add_rmsnorm_ref`` -- the reference the tests compare against.
 """
@@ -22,6 +28,7 @@ import torch.nn.functional as F
 
 from .. import native
 from ..utils.config import feature as _feat
+from .handover import Q8Pending, mx_grad_token
 
 
 def add_rmsnorm_ref(r, h, weight, eps: float = 1e-6, p: float = 0.0, training: bool = False):
@@ -43,9 +50,20 @@ class _AddRMSFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, h, weight, mod, p):
         shp = r.shape
+        # MX hand-over (psd_mx_output_to): the forward also writes the MX e4m3 copy of y for the fp8 Linear that
+        # reads it, which then skips its quantise pass (bitwise quantize_mx(y))
+        cons = mod._psd_mx_to
+        q8 = sc8 = None
+        if cons is not None and _feat("fp8_llama_handover") and cons.psd_mx_input_ok(shp[-1]):
+            q8 = torch.empty(shp, dtype=torch.float8_e4m3fn, device=r.device)
+            sc8 = torch.empty(r.numel() // 32, dtype=torch.uint8, device=r.device)
         r_new, y, rstd = native().rms_fwd(r.contiguous(), None if h is None else h.contiguous(), weight, mod.eps, p,
-                                          mod.seed, mod.step)
+                                          mod.seed, mod.step, q8, sc8)
+        if q8 is not None:
+            cons._psd_q8_pending = Q8Pending(y.view(shp), q8, sc8)
         ctx.mod, ctx.p, ctx.had_h = mod, p, h is not None
+        # backward hand-over (psd_mx_grad_to): the forward token of the fp8 Linear that produced exactly this h
+        ctx.gtok = mx_grad_token(mod._psd_mxg_to, h)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(r_new, rstd, weight)
         if h is None:
@@ -61,9 +79,17 @@ class _AddRMSFn(torch.autograd.Function):
             dy = torch.zeros_like(r_new)
         sink = getattr(mod, "_psd_grad_sink", None)
         dgo = sink(mod.weight) if sink is not None else None
+        # the e5m2 copy of dh for the bwd-data GEMM of the Linear that produced h (it ran MX, fp8_dgrad is on)
+        lin = mod._psd_mxg_to
+        dq8 = dsc8 = None
+        if ctx.gtok is not None and _feat("fp8_llama_handover") and _feat("fp8_dgrad") and not _feat("fp8_wgrad"):
+            dq8 = torch.empty(r_new.shape, dtype=torch.float8_e5m2, device=r_new.device)
+            dsc8 = torch.empty(r_new.numel() // 32, dtype=torch.uint8, device=r_new.device)
         dr, dh, dg = native().rms_bwd(dy.contiguous().view(r_new.shape),
                                       None if dr_new is None else dr_new.contiguous().view(r_new.shape), r_new, rstd,
-                                      w, ctx.p, mod.seed, mod.step, ctx.had_h, dgo)
+                                      w, ctx.p, mod.seed, mod.step, ctx.had_h, dgo, dq8, dsc8)
+        if dq8 is not None:
+            lin._psd_dq8_pending = (ctx.gtok, Q8Pending(dh.view(-1, dh.shape[-1]), dq8, dsc8))
         return dr, dh, dg, None, None
 
 
@@ -80,6 +106,22 @@ class FusedAddRMSNorm(nn.Module):
         self.seed = int(seed) & 0x7FFFFFFF
         self.step = None  # device int64 counter, set by the owning model (ops.layernorm.bump_step)
         self.weight = nn.Parameter(torch.ones(self.hidden))
+        self._psd_mx_to = None  # psd_mx_output_to: the fp8 MfmaLinear that reads this norm's output y
+        self._psd_mxg_to = None  # psd_mx_grad_to: the fp8 MfmaLinear that produced the branch h
+
+    def psd_mx_output_to(self, lin) -> None:
+        """Declare that ``lin`` (an ``MfmaLinear``) reads this norm's output ``y``: when it runs the MX fp8 recipe,
+        the fused forward also writes its MX e4m3 input operand and leaves it on ``lin`` as an
+        ``ops.handover.Q8Pending`` (feature ``fp8_llama_handover``). ``lin`` uses it only for exactly the tensor
+        returned here. (Kept out of the module tree: ``lin`` is registered where the model owns it.)"""
+        object.__setattr__(self, "_psd_mx_to", lin)
+
+    def psd_mx_grad_to(self, lin) -> None:
+        """Declare that ``lin`` (an ``MfmaLinear``) produces this norm's branch input ``h``, so that ``lin``'s
+        output gradient is this norm's ``dh``: when that forward of ``lin`` ran the MX fp8 recipe and ``fp8_dgrad``
+        is on, the fused backward also writes the MX e5m2 copy of ``dh`` and leaves it on ``lin``
+        (``_psd_dq8_pending``, with ``lin``'s forward token) for its bwd-data GEMM."""
+        object.__setattr__(self, "_psd_mxg_to", lin)
 
     def extra_repr(self) -> str:
         return f"{self.hidden}, eps={self.eps}, p={self.p}"

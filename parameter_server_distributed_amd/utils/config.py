@@ -100,6 +100,9 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "fp8_dgrad": (True, "fp8 e5m2-dY bwd-data of the fp8 convolutions and fp8 Linear layers"),
     "fp8_wgrad": (False, "fp8 e4m3 x e4m3 split-K weight gradient of the fp8 Linear layers (tokens % 128 == 0); off: bf16"),
     "fp8_ln_handover": (True, "the fused LayerNorm writes the MX e4m3 input of the fp8 Linear that consumes it"),
+    "fp8_llama_handover": (True, "the Llama block's fused RMSNorm / SwiGLU kernels write the MX operands of the fp8 "
+                                 "Linears around them (e4m3 inputs forward, e5m2 output gradients backward); "
+                                 "off: stand-alone quantize_mx passes, bitwise the same results"),
     "async_cached_local": (True, "async PS at world 1: inbox / publish buffers in plain (cached) device memory "
                                  "instead of uncached IPC memory (AsyncPS hands it to the native engine)"),
     "async_apply_background": (True, "async PS with SSP bound >= 1: the owner's apply on a normal-priority stream "

@@ -5,6 +5,8 @@ T = 16,384 tokens, H = 768, F = 2048. us per call, bytes moved and achieved GB/s
 
   python tools/llama_block_bench.py            # the four kernels
   python tools/llama_block_bench.py --ref      # also the torch composites add_rmsnorm_ref / swiglu_ref
+  python tools/llama_block_bench.py --mx       # the MX side-output variants against plain + quantize_mx
+  python tools/llama_block_bench.py --layer    # one layer forward + backward: fp8 hand-overs on / off, bf16
 
 The bytes counted are what each pass has to move (bf16 tensors read or written once; the fp32 rstd, gamma and
 the dgamma partials are not counted):
@@ -15,6 +17,13 @@ the dgamma partials are not counted):
 The composites' columns are charged the same bytes, so their GB/s is the rate at which they do the same job
 (they move more: every intermediate goes through memory). A composite backward is the autograd backward of
 its forward, whose graph is built once outside the timed window.
+
+--mx: each variant that also writes the MX fp8 copy of its output (q8 + E8M0 scales: 33/32 bytes per element on
+top of the plain pass) against what it replaces, the plain kernel followed by the stand-alone quantize_mx pass
+over the stored bf16 output (2 bytes per element read again, 33/32 written); the three alternate inside a window.
+--layer: forward + backward of one LlamaLayer plus the norm that closes it (it takes the layer's branch, so the
+down Linear's backward hand-over is in the figure), T tokens as [T / 512, 512], dropout 0.1, rope: the fp8 layer
+with feature fp8_llama_handover on and off and the bf16 layer, alternating inside a window, ms per step.
 
 Every figure comes from --repeats timed windows of --iters calls between two device events; with --ref the
 two paths alternate inside a window. Printed: median (min - max) us and the rate at the median."""
@@ -49,12 +58,104 @@ def _fmt(ts):
     return f"{statistics.median(ts):.1f} ({min(ts):.1f} - {max(ts):.1f})"
 
 
+def mx_cases(C, T, r, h, dy, drn, gamma, gu, da, step):
+    """(name, plain bytes, MX copy elements, plain call -> the tensor that is quantised, e5m2, fused call)."""
+    p = 0.1
+    r_new, _, rstd = C.rms_fwd(r, h, gamma, EPS, p, SEED, step)
+
+    def out8(n, cols, e5m2):
+        return (torch.empty(n, cols, device=r.device, dtype=torch.float8_e5m2 if e5m2 else torch.float8_e4m3fn),
+                torch.empty(n * cols // 32, device=r.device, dtype=torch.uint8))
+
+    qy, qdh, qa, qdgu = out8(T, H, False), out8(T, H, True), out8(T, F, False), out8(T, 2 * F, True)
+    return [
+        ("rms_fwd p=0.1 + e4m3(y)", 4 * T * H * 2, T * H, lambda: C.rms_fwd(r, h, gamma, EPS, p, SEED, step)[1], False,
+         lambda: C.rms_fwd(r, h, gamma, EPS, p, SEED, step, *qy)),
+        ("rms_bwd p=0.1 + e5m2(dh)", 5 * T * H * 2, T * H,
+         lambda: C.rms_bwd(dy, drn, r_new, rstd, gamma, p, SEED, step, True)[1], True,
+         lambda: C.rms_bwd(dy, drn, r_new, rstd, gamma, p, SEED, step, True, None, *qdh)),
+        ("swiglu_fwd + e4m3(a)", 3 * T * F * 2, T * F, lambda: C.swiglu_fwd(gu, 0), False,
+         lambda: C.swiglu_fwd(gu, 0, *qa)),
+        ("swiglu_bwd + e5m2(dgu)", 5 * T * F * 2, 2 * T * F, lambda: C.swiglu_bwd(da, gu, 0), True,
+         lambda: C.swiglu_bwd(da, gu, 0, *qdgu)),
+    ]
+
+
+def bench_mx(C, args, tensors):
+    from parameter_server_distributed_amd.ops import quantize_mx
+
+    print("| variant | plain MB | plain us | plain + quantize_mx MB | plain + quantize_mx us | fused MB | fused us "
+          "| fused / (plain + quantize_mx) |")
+    print("|" + "---:|" * 8)
+    for name, nbytes, nq, plain, e5m2, fused in mx_cases(C, args.tokens, *tensors):
+        two = (lambda: quantize_mx(plain(), e5m2))
+        tp, t2, tf = [], [], []
+        for _ in range(args.repeats):
+            tp.append(t_us(plain, args.iters))
+            t2.append(t_us(two, args.iters))
+            tf.append(t_us(fused, args.iters))
+        copy = nq * 33 / 32
+        ratio = statistics.median(tf) / statistics.median(t2)
+        print(f"| {name} | {nbytes / 1e6:.1f} | {_fmt(tp)} | {(nbytes + 2 * nq + copy) / 1e6:.1f} | {_fmt(t2)} | "
+              f"{(nbytes + copy) / 1e6:.1f} | {_fmt(tf)} | {ratio:.3f} |", flush=True)
+
+
+def bench_layer(args, dev):
+    from parameter_server_distributed_amd.models.llama_block import LlamaLayer
+    from parameter_server_distributed_amd.ops.rmsnorm import FusedAddRMSNorm
+
+    S = 512
+    if args.tokens % S:
+        sys.exit("llama_block_bench --layer: --tokens must be a multiple of 512")
+    B = args.tokens // S
+    g = torch.Generator(device=dev).manual_seed(1)
+    r0 = torch.randn(B, S, H, device=dev, generator=g).to(torch.bfloat16).requires_grad_(True)
+    h0 = torch.randn(B, S, H, device=dev, generator=g).to(torch.bfloat16).requires_grad_(True)
+    dr, dy = (torch.randn(B, S, H, device=dev, generator=g).to(torch.bfloat16) for _ in range(2))
+    step = torch.tensor([3], device=dev, dtype=torch.int64)
+
+    def make(fp8):
+        torch.manual_seed(0)
+        layer = LlamaLayer(H, 12, F, 0.1, 0, rope=(S, 10000.0), fp8=fp8).to(dev).to(torch.bfloat16).train()
+        close = FusedAddRMSNorm(H, p=0.1, seed=3).to(dev).to(torch.bfloat16).train()
+        if fp8:
+            close.psd_mx_grad_to(layer.down)
+        for m in (layer.norm1, layer.norm2, close):
+            m.step = step
+        params = [r0, h0] + list(layer.parameters()) + list(close.parameters())
+
+        def run():
+            r, h = layer(r0, h0)
+            torch.autograd.grad(close(r, h), params, (dr, dy))
+
+        return run
+
+    runs = [("fp8, fp8_llama_handover on", make("mx"), ""), ("fp8, fp8_llama_handover off", make("mx"),
+                                                             "fp8_llama_handover=0"), ("bf16", make(False), "")]
+    env0 = os.environ.get("PSD_FEATURES", "")
+    ts = {name: [] for name, _, _ in runs}
+    for _ in range(args.repeats):
+        for name, run, feat in runs:
+            os.environ["PSD_FEATURES"] = ",".join(filter(None, (env0, feat)))
+            ts[name].append(t_us(run, args.layer_iters) / 1e3)
+    os.environ["PSD_FEATURES"] = env0
+    print(f"one LlamaLayer + closing norm, forward + backward, [{B}, {S}, {H}], F {F}: ms, median (min - max)")
+    print("| layer | ms |")
+    print("|---|---:|")
+    for name, _, _ in runs:
+        v = ts[name]
+        print(f"| {name} | {statistics.median(v):.3f} ({min(v):.3f} - {max(v):.3f}) |", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=TOKENS, help="rows T")
     ap.add_argument("--iters", type=int, default=200, help="timed calls per window")
     ap.add_argument("--repeats", type=int, default=10, help="timed windows per figure")
     ap.add_argument("--ref", action="store_true", help="also time the torch composites on the same buffers")
+    ap.add_argument("--mx", action="store_true", help="time the MX side-output variants against plain + quantize_mx")
+    ap.add_argument("--layer", action="store_true", help="time one layer: fp8 hand-overs on / off and bf16")
+    ap.add_argument("--layer-iters", type=int, default=20, help="timed steps per window of --layer")
     args = ap.parse_args()
     if args.tokens < 1:
         ap.error("--tokens must be >= 1")
@@ -72,6 +173,13 @@ def main():
     gamma = (torch.rand(H, device=dev, generator=g) + 0.5).to(torch.bfloat16)
     gu, da = rnd(T, 2 * F), rnd(T, F)
     step = torch.tensor([3], device=dev, dtype=torch.int64)
+    if args.mx or args.layer:
+        print(f"T {T} tokens, H {H}, F {F}; {args.repeats} windows: median (min - max)")
+        if args.mx:
+            bench_mx(C, args, (r, h, dy, drn, gamma, gu, da, step))
+        if args.layer:
+            bench_layer(args, dev)
+        return
     cases = []  # (name, bytes, kernel call, composite call or None)
     for p in (0.0, 0.1):
         r_new, _, rstd = C.rms_fwd(r, h, gamma, EPS, p, SEED, step)
