@@ -4,7 +4,7 @@
 
 namespace psd {
 // The pre-norm residual step r_new = r + dropout_p(h), y = RMSNorm(r_new) * gamma over rows of H
-// (kernels/rmsnorm.hip) and its backward.
+// (kernels/rmsnorm.hip at H = 768 / 1024, kernels/rmsnorm_wide.hip at H = 512 n, n = 3 .. 16) and its backward.
 struct RmsArgs {
   const uint16_t* r;       // fwd: residual stream in [rows, H] bf16
   const uint16_t* h;       // fwd: branch output or null (then r_new is r: nothing added, nothing written)
@@ -23,7 +23,7 @@ struct RmsArgs {
   uint8_t* dq8;            // bwd out or null: MX e5m2 copy of the returned dh (dh, or dr where dh is null)
   uint8_t* dsc8;           // bwd out or null: its E8M0 scales [rows, H/32] (both or neither)
   uint16_t* dgamma;        // bwd out [H] bf16 (may be the PS gradient sink)
-  float* part;             // bwd workspace [rms_bwd_blocks(rows)][H] fp32
+  float* part;             // bwd workspace [rms_bwd_blocks(rows, H)][H] fp32
   const int64_t* step;     // device step counter mixed into the dropout hash (may be null)
   int64_t rows;
   int32_t H;
@@ -31,9 +31,15 @@ struct RmsArgs {
   float p;                 // dropout probability (0: identity)
   uint32_t seed;           // per call site
 };
-bool rms_supported(int H);
-int rms_fwd_blocks(int64_t rows);
-int rms_bwd_blocks(int64_t rows);
+bool rms_supported(int H);  // 768, 1024 or rms_wide(H)
+bool rms_wide(int H);       // a multiple of 512 from 1536 to 8192: the wide kernels, 16-byte accesses
+int rms_fwd_blocks(int64_t rows, int H);
+int rms_bwd_blocks(int64_t rows, int H);
 hipError_t launch_rms_fwd(const RmsArgs& a, hipStream_t stream);
 hipError_t launch_rms_bwd(const RmsArgs& a, hipStream_t stream);
+// kernels/rmsnorm_wide.hip, reached through the four functions above
+int rms_wide_fwd_blocks(int64_t rows);
+int rms_wide_bwd_blocks(int64_t rows);
+hipError_t launch_rms_wide_fwd(const RmsArgs& a, hipStream_t stream);
+hipError_t launch_rms_wide_bwd(const RmsArgs& a, hipStream_t stream);
 }  // namespace psd

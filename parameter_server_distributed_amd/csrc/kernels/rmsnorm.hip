@@ -216,23 +216,27 @@ __global__ __launch_bounds__(256) void rms_bwd_kernel(const uint16_t* __restrict
     part[(int64_t)blockIdx.x * H + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
 
-bool rms_supported(int H) { return H == 768 || H == 1024; }
+bool rms_supported(int H) { return H == 768 || H == 1024 || rms_wide(H); }
 
 // one row per wave, four waves per workgroup, <= 2048 workgroups: past 8192 rows the waves take further rows
-int rms_fwd_blocks(int64_t rows) {
+// (the wide sizes: rmsnorm_wide.hip's own grids)
+int rms_fwd_blocks(int64_t rows, int H) {
+  if (rms_wide(H)) return rms_wide_fwd_blocks(rows);
   const int64_t want = (rows + 3) / 4;
   return (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
 }
 
 // >= 8 rows per wave, <= 512 workgroups (two per CU): at most 512 dgamma partial rows for the finalize
-int rms_bwd_blocks(int64_t rows) {
+int rms_bwd_blocks(int64_t rows, int H) {
+  if (rms_wide(H)) return rms_wide_bwd_blocks(rows);
   const int64_t want = (rows + 4 * 8 - 1) / (4 * 8);
   return (int)(want < 1 ? 1 : (want > 512 ? 512 : want));
 }
 
 hipError_t launch_rms_fwd(const RmsArgs& a, hipStream_t st) {
   if (!rms_supported(a.H) || a.rows < 0) return hipErrorInvalidValue;
-  const int blocks = rms_fwd_blocks(a.rows);
+  if (rms_wide(a.H)) return launch_rms_wide_fwd(a, st);
+  const int blocks = rms_fwd_blocks(a.rows, a.H);
   const bool add = a.h != nullptr;
   const uint32_t th = add ? keep_thresh(a.p) : 0u;
   const float sc = (add && a.p > 0.f) ? 1.f / (1.f - a.p) : 1.f;
@@ -257,7 +261,8 @@ hipError_t launch_rms_fwd(const RmsArgs& a, hipStream_t st) {
 
 hipError_t launch_rms_bwd(const RmsArgs& a, hipStream_t st) {
   if (!rms_supported(a.H) || a.rows < 0) return hipErrorInvalidValue;
-  const int blocks = rms_bwd_blocks(a.rows);
+  if (rms_wide(a.H)) return launch_rms_wide_bwd(a, st);
+  const int blocks = rms_bwd_blocks(a.rows, a.H);
   const uint32_t th = keep_thresh(a.p);
   const bool drn = a.dr_new != nullptr;
   const bool dh = a.dh != nullptr;  // null at p == 0: dh is dr, written once

@@ -1,4 +1,4 @@
-// Tensor glue for the fused residual add + dropout + RMSNorm kernels (kernels/rmsnorm.hip). Every check
+// Tensor glue for the fused residual add + dropout + RMSNorm kernels (kernels/rmsnorm.hip, rmsnorm_wide.hip). Every check
 // runs before any allocation or launch and names the argument it rejects.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
@@ -39,8 +39,14 @@ const int64_t* check_step(const char* op, const c10::optional<at::Tensor>& step,
 int64_t check_hidden(const char* op, const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() >= 1, op, ": ", name, " must have at least one dimension");
   const int64_t H = t.size(-1);
-  TORCH_CHECK(rms_supported((int)H), op, ": ", name, " must have a last dimension (H) of 768 or 1024, got ", H);
+  TORCH_CHECK(H <= 8192 && rms_supported((int)H), op, ": ", name,
+              " must have a last dimension (H) of 768, 1024 or a multiple of 512 from 1536 to 8192, got ", H);
   return H;
+}
+// the wide kernels (rms_wide(H)) move 16 bytes per access: activations, gamma and MX payloads
+void check_align16(const char* op, int64_t H, const at::Tensor& t, const char* name) {
+  TORCH_CHECK(!rms_wide((int)H) || (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, op, ": ", name,
+              " must be 16-byte aligned at H = ", H);
 }
 // the MX side output of `like` [rows, H]: payload `q` (fp8 dtype `qt`, like's shape) and E8M0 scales `sc` (uint8,
 // one per 32 columns), both or neither; true when given
@@ -73,15 +79,21 @@ std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h
   const char* op = "psd rms_fwd";
   check_act(op, r, "r");
   const int64_t H = check_hidden(op, r, "r");
+  check_align16(op, H, r, "r");
   const bool add = given(h);
-  if (add) check_like(op, *h, r, "h", "r");
+  if (add) {
+    check_like(op, *h, r, "h", "r");
+    check_align16(op, H, *h, "h");
+  }
   check_gamma(op, gamma, r, H, "gamma");
+  check_align16(op, H, gamma, "gamma");
   const int64_t* stp = nullptr;
   if (add) {
     check_p(op, p);
     stp = check_step(op, step, r);
   }
   const bool mx = check_mx(op, q8_out, sc8_out, r, at::kFloat8_e4m3fn, "q8_out", "sc8_out", "r");
+  if (mx) check_align16(op, H, *q8_out, "q8_out");
   const c10::DeviceGuard g(r.device());
   const int64_t rows = r.numel() / H;
   at::Tensor r_new = add ? at::empty_like(r) : r;
@@ -117,25 +129,32 @@ std::vector<at::Tensor> rms_bwd(const at::Tensor& dy, c10::optional<at::Tensor> 
   const char* op = "psd rms_bwd";
   check_act(op, r_new, "r_new");
   const int64_t H = check_hidden(op, r_new, "r_new");
+  check_align16(op, H, r_new, "r_new");
   check_like(op, dy, r_new, "dy", "r_new");
+  check_align16(op, H, dy, "dy");
   const bool drn = given(dr_new);
-  if (drn) check_like(op, *dr_new, r_new, "dr_new", "r_new");
+  if (drn) {
+    check_like(op, *dr_new, r_new, "dr_new", "r_new");
+    check_align16(op, H, *dr_new, "dr_new");
+  }
   const int64_t rows = r_new.numel() / H;
   TORCH_CHECK(rstd.defined() && rstd.is_cuda() && rstd.device() == r_new.device() && rstd.scalar_type() == at::kFloat &&
                   rstd.is_contiguous() && rstd.numel() == rows,
               op, ": rstd must be a contiguous fp32 [", rows, "] tensor on r_new's device");
   check_gamma(op, gamma, r_new, H, "gamma");
+  check_align16(op, H, gamma, "gamma");
   check_p(op, p);
   const int64_t* stp = check_step(op, step, r_new);
   if (given(dgamma_out)) check_gamma(op, *dgamma_out, r_new, H, "dgamma_out");
   const bool mx = check_mx(op, dq8_out, dsc8_out, r_new, at::kFloat8_e5m2, "dq8_out", "dsc8_out", "r_new");
   TORCH_CHECK(!mx || had_h, op, ": dq8_out is the MX copy of dh and needs had_h");
+  if (mx) check_align16(op, H, *dq8_out, "dq8_out");
   const c10::DeviceGuard g(r_new.device());
   at::Tensor dr = at::empty_like(r_new);
   at::Tensor dh;
   if (had_h) dh = p > 0.0 ? at::empty_like(r_new) : dr;
   at::Tensor dgamma = given(dgamma_out) ? *dgamma_out : at::empty({H}, r_new.options());
-  at::Tensor part = at::empty({(int64_t)rms_bwd_blocks(rows) * H}, r_new.options().dtype(at::kFloat));
+  at::Tensor part = at::empty({(int64_t)rms_bwd_blocks(rows, (int)H) * H}, r_new.options().dtype(at::kFloat));
   RmsArgs a{};
   a.dy = bf16(dy);
   a.dr_new = drn ? bf16(*dr_new) : nullptr;

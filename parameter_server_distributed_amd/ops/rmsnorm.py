@@ -1,6 +1,7 @@
 """The pre-norm residual step of a Llama-style block, ``r_new = r + dropout(h)``, ``y = RMSNorm(r_new)``,
-on the fused gfx950 kernels of ``csrc/kernels/rmsnorm.hip`` (one pass forward, one pass backward + the
-tiny fixed-order ``dgamma`` finalize).
+on the fused gfx950 kernels of ``csrc/kernels/rmsnorm.hip`` (hidden 768 / 1024: one wave per row) and
+``rmsnorm_wide.hip`` (hidden 512 n, n = 3 .. 16: one workgroup per row; feature ``rmsnorm_wide``): one pass
+forward, one pass backward + the tiny fixed-order ``dgamma`` finalize.
 
 ``rstd = rsqrt(mean(r_new^2) + eps)`` is taken from the bf16-rounded ``r_new`` -- the value that is stored
 and carried on as the residual stream -- and ``y = r_new * rstd * weight``; there is no bias and no mean.
@@ -82,7 +83,10 @@ class _AddRMSFn(torch.autograd.Function):
         # the e5m2 copy of dh for the bwd-data GEMM of the Linear that produced h (it ran MX, fp8_dgrad is on)
         lin = mod._psd_mxg_to
         dq8 = dsc8 = None
-        if ctx.gtok is not None and _feat("fp8_llama_handover") and _feat("fp8_dgrad") and not _feat("fp8_wgrad"):
+        # (not at hidden 1536 / 2048: the wide kernels' one-slab backward with the side output only ties the plain
+        # launch + quantize_mx, measured at 2048, profiles/rmsnorm_wide.md, so the Linear keeps its own pass there)
+        if (ctx.gtok is not None and _feat("fp8_llama_handover") and _feat("fp8_dgrad") and not _feat("fp8_wgrad")
+                and not 1536 <= r_new.shape[-1] <= 2048):
             dq8 = torch.empty(r_new.shape, dtype=torch.float8_e5m2, device=r_new.device)
             dsc8 = torch.empty(r_new.numel() // 32, dtype=torch.uint8, device=r_new.device)
         dr, dh, dg = native().rms_bwd(dy.contiguous().view(r_new.shape),
@@ -130,7 +134,9 @@ class FusedAddRMSNorm(nn.Module):
         return [self.weight]
 
     def _kernel_ok(self, r, h) -> bool:
-        return (r.is_cuda and r.dtype == torch.bfloat16 and r.shape[-1] == self.hidden and self.hidden in (768, 1024)
+        hid = self.hidden
+        wide = hid % 512 == 0 and 1536 <= hid <= 8192 and _feat("rmsnorm_wide")  # rmsnorm_wide.hip
+        return (r.is_cuda and r.dtype == torch.bfloat16 and r.shape[-1] == hid and (hid in (768, 1024) or wide)
                 and self.weight.dtype == torch.bfloat16 and self.weight.device == r.device
                 and (h is None or (h.dtype == torch.bfloat16 and h.shape == r.shape and h.device == r.device)))
 

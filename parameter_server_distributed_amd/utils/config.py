@@ -130,6 +130,8 @@ FEATURES: dict[str, tuple[bool, str]] = {
     # Llama-style block (ops/rmsnorm.py, ops/swiglu.py)
     "rmsnorm": (True, "fused residual add + dropout + RMSNorm kernels (ops/rmsnorm.py FusedAddRMSNorm); off: the "
                       "torch composite add_rmsnorm_ref"),
+    "rmsnorm_wide": (True, "the fused RMSNorm kernels also at hidden sizes 512 n, n = 3 .. 16 (1536 .. 8192: "
+                           "kernels/rmsnorm_wide.hip; needs rmsnorm); off: those sizes take add_rmsnorm_ref"),
     "swiglu": (True, "gated SiLU kernels on the packed gate/up tensor (ops/swiglu.py SwiGLU); off: the torch "
                      "composite swiglu_ref"),
 }

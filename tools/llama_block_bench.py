@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the four kernels of the Llama-style block (csrc/kernels/rmsnorm.hip, swiglu.hip): the fused residual
 add + dropout + RMSNorm forward and backward at p = 0 and 0.1, and the gated SiLU forward and backward, at
-T = 16,384 tokens, H = 768, F = 2048. us per call, bytes moved and achieved GB/s.
+T = 16,384 tokens, H = 768, F = 2048 (--tokens, --hidden, --ffn; a hidden size of 512 n from 1536 to 8192 times
+the wide kernels of rmsnorm_wide.hip). us per call, bytes moved and achieved GB/s.
 
   python tools/llama_block_bench.py            # the four kernels
   python tools/llama_block_bench.py --ref      # also the torch composites add_rmsnorm_ref / swiglu_ref
@@ -116,7 +117,7 @@ def bench_layer(args, dev):
 
     def make(fp8):
         torch.manual_seed(0)
-        layer = LlamaLayer(H, 12, F, 0.1, 0, rope=(S, 10000.0), fp8=fp8).to(dev).to(torch.bfloat16).train()
+        layer = LlamaLayer(H, H // 64, F, 0.1, 0, rope=(S, 10000.0), fp8=fp8).to(dev).to(torch.bfloat16).train()
         close = FusedAddRMSNorm(H, p=0.1, seed=3).to(dev).to(torch.bfloat16).train()
         if fp8:
             close.psd_mx_grad_to(layer.down)
@@ -148,8 +149,11 @@ def bench_layer(args, dev):
 
 
 def main():
+    global H, F
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=TOKENS, help="rows T")
+    ap.add_argument("--hidden", type=int, default=H, help="hidden size H of the RMSNorm cases (and of --layer)")
+    ap.add_argument("--ffn", type=int, default=F, help="FFN size F of the SwiGLU cases (and of --layer)")
     ap.add_argument("--iters", type=int, default=200, help="timed calls per window")
     ap.add_argument("--repeats", type=int, default=10, help="timed windows per figure")
     ap.add_argument("--ref", action="store_true", help="also time the torch composites on the same buffers")
@@ -159,6 +163,9 @@ def main():
     args = ap.parse_args()
     if args.tokens < 1:
         ap.error("--tokens must be >= 1")
+    if args.hidden % 64 or args.hidden < 64 or args.ffn % 32 or args.ffn < 32:
+        ap.error("--hidden must be a multiple of 64 and --ffn a multiple of 32")
+    H, F = args.hidden, args.ffn
     if not torch.cuda.is_available():
         sys.exit("llama_block_bench: no GPU visible; timings are taken on the device only")
     C = native()
