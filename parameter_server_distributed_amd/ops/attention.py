@@ -55,6 +55,7 @@ import torch.nn.functional as F
 
 from ..utils.config import feature as _feat
 from .. import native
+from .handover import bias_src, grad_out, hand_bias
 
 
 def doc_starts(doc_lens, S: int, device=None) -> torch.Tensor:
@@ -93,11 +94,9 @@ def check_doc_start(t: torch.Tensor) -> None:
 class _AttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, mod, p, lens=None, doc_start=None, window=None):
-        # qkv straight from an MfmaLinear with a bias (ops/linear.py tags its output): backward also
+        # qkv straight from the latest forward of an MfmaLinear with a bias and no activation: backward also
         # sums dqkv's columns -- that Linear's bias gradient -- and hands it over
-        src = getattr(qkv, "_psd_src", None) if _feat("attn_bias") else None
-        ctx.src = src if (src is not None and src[0].bias is not None and src[0].act in (None, "none")
-                          and src[0]._psd_tok == src[1]) else None
+        ctx.src = bias_src(qkv) if _feat("attn_bias") else None
         qkv = qkv.contiguous()
         # window: None on every path that existed before it (no argument passed), else the W of the window copies
         ctx.win = () if window is None else (int(window),)
@@ -109,18 +108,12 @@ class _AttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
-        mod = ctx.mod
-        db = None
-        if ctx.src is not None:
-            lin = ctx.src[0]
-            sink = getattr(lin, "_psd_grad_sink", None)
-            db = sink(lin.bias) if sink is not None else None
-            if db is None:
-                db = torch.empty_like(lin.bias)
+        mod, src = ctx.mod, ctx.src
+        db = grad_out(src.lin, src.lin.bias, like=src.lin.bias) if src is not None else None
         dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens, 0, mod.causal,
                                  ctx.doc, *ctx.win)
-        if db is not None:
-            ctx.src[0]._psd_bias_hand = (ctx.src[1], dqkv.data_ptr(), db)
+        if src is not None:
+            hand_bias(src, dqkv, db)
         return dqkv, None, None, None, None, None
 
 

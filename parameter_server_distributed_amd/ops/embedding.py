@@ -18,8 +18,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import native
+from .handover import grad_out
 
 SMALL_VOCAB = 16
+
+
+def _grad_dest(mod, param):
+    """Where a table's (or the LayerNorm's) gradient is written: the PS flat-gradient view where the data plane
+    installed a sink and the view is contiguous, else a fresh tensor."""
+    v = grad_out(mod, param)
+    return v if v is not None and v.is_contiguous() else torch.empty_like(param)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -38,10 +46,7 @@ class _EmbedFn(torch.autograd.Function):
         flat = ids.reshape(-1)
         # straight into the PS flat-gradient buffer when the data plane installed a sink (the table
         # gradient is then neither zeroed by the data plane nor accumulated into it)
-        sink = getattr(ctx.mod, "_psd_grad_sink", None)
-        dw = sink(ctx.mod.weight) if sink is not None else None
-        if dw is None or not dw.is_contiguous():
-            dw = torch.empty(V, Hd, dtype=g2.dtype, device=g2.device)
+        dw = _grad_dest(ctx.mod, ctx.mod.weight)
         if V <= SMALL_VOCAB:
             torch.mm(F.one_hot(flat, V).to(g2.dtype).t(), g2, out=dw)
             return None, dw, None
@@ -95,26 +100,20 @@ class _BertEmbLNFn(torch.autograd.Function):
         ids, types, mean, rstd = ctx.saved_tensors
         mod = ctx.mod
         w, pt, tt = mod.word.weight, mod.pos.weight, mod.tok_type.weight
-        sink = getattr(mod, "_psd_grad_sink", None)
-
-        def out(param):  # the PS flat-gradient view (direct), else a fresh tensor
-            v = sink(param) if sink is not None else None
-            return v if v is not None and v.is_contiguous() else torch.empty_like(param)
-
-        dgo, dbo = out(mod.ln.weight), out(mod.ln.bias)
-        dT = out(tt) if tt.shape[0] <= 2 else None
+        dgo, dbo = _grad_dest(mod, mod.ln.weight), _grad_dest(mod, mod.ln.bias)
+        dT = _grad_dest(mod, tt) if tt.shape[0] <= 2 else None
         H = w.shape[1]
         dx, dg, db, dT = native().emb_ln_bwd(dy.reshape(-1, H), ids, types, w, pt, tt, mod.ln.weight, mean, rstd,
                                              ctx.S, ctx.p, mod.seed, mod.step, dgo, dbo, dT, ctx.pos_ids)
         if dT is None:  # > 2 token types: one-hot GEMM as FusedEmbedding's small-vocabulary path
-            dT = out(tt)
+            dT = _grad_dest(mod, tt)
             torch.mm(F.one_hot(types, tt.shape[0]).to(dx.dtype).t(), dx, out=dT)
         # word table: the deterministic sorted scatter of dx (kernels/embed.hip, as _EmbedFn)
-        dW = out(w)
+        dW = _grad_dest(mod, w)
         s, perm = torch.sort(ids, stable=True)
         dW.zero_()
         native().embed_bwd_(s, perm, dx, dW)
-        dP = out(pt)
+        dP = _grad_dest(mod, pt)
         if ctx.pos_ids is not None:
             # position ids: the word table's sorted scatter, over the ids the kernel read (clamped)
             s, perm = torch.sort(ctx.pos_ids.clamp(0, pt.shape[0] - 1), stable=True)

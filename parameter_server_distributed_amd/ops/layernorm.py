@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from .. import native
 from ..utils.config import feature as _feat
-from .handover import Q8Pending
+from .handover import bias_src, forward_token, grad_out, hand_bias, leave_q8, mx_pair, queue_dx
 
 
 class _AddLNFn(torch.autograd.Function):
@@ -29,48 +29,35 @@ class _AddLNFn(torch.autograd.Function):
         # MX hand-over (psd_mx_output_to): the forward also writes the MX e4m3 copy of y for the fp8
         # Linear that reads it, which then skips its quantise pass (bitwise quantize_mx(y))
         cons = getattr(mod, "_psd_mx_to", None)
-        q8 = sc8 = None
-        if (cons is not None and _feat("fp8_ln_handover")
-                and getattr(cons, "psd_mx_input_ok", lambda _h: False)(shp[-1])):
-            q8 = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-            sc8 = torch.empty(x.numel() // 32, dtype=torch.uint8, device=x.device)
+        make = (cons is not None and _feat("fp8_ln_handover")
+                and getattr(cons, "psd_mx_input_ok", lambda _h: False)(shp[-1]))
+        q8, sc8 = mx_pair(shp, x.device) if make else (None, None)
         y, s, mean, rstd = C.ln_fwd(x.contiguous(), h.contiguous(), weight, bias, mod.eps, p, mod.seed, mod.step,
                                     q8, sc8)
         if q8 is not None:
-            cons._psd_q8_pending = Q8Pending(y.view(shp), q8, sc8)
+            leave_q8(cons, y.view(shp), q8, sc8)
         ctx.mod, ctx.p, ctx.x_grad_to = mod, p, x_grad_to
-        ctx.tok = getattr(x_grad_to, "_psd_tok", None) if x_grad_to is not None else None
-        # h straight from an MfmaLinear with a bias and no activation (ops/linear.py tags its
-        # output): the backward sums dh's columns in its own pass -- that Linear's bias gradient --
-        # and hands it over, so the Linear skips its column-sum kernels
-        src = getattr(h, "_psd_src", None)
-        ctx.h_src = src if (src is not None and src[0].bias is not None and src[0].act in (None, "none")
-                            and src[0]._psd_tok == src[1]) else None
+        ctx.tok = forward_token(x_grad_to)
+        # h straight from the latest forward of an MfmaLinear with a bias and no activation: the backward sums
+        # dh's columns in its own pass -- that Linear's bias gradient -- and hands it over, so the Linear
+        # skips its column-sum kernels
+        ctx.h_src = bias_src(h)
         ctx.save_for_backward(s, mean, rstd, weight)
         return y.view(shp)
 
     @staticmethod
     def backward(ctx, dy):
         s, mean, rstd, w = ctx.saved_tensors
-        mod = ctx.mod
-        sink = getattr(mod, "_psd_grad_sink", None)
-        dgo = dbo = None
-        if sink is not None:
-            dgo, dbo = sink(mod.weight), sink(mod.bias)
-        dhs = None
-        if ctx.h_src is not None:
-            lin = ctx.h_src[0]
-            lsink = getattr(lin, "_psd_grad_sink", None)
-            dhs = lsink(lin.bias) if lsink is not None else None
-            if dhs is None:
-                dhs = torch.empty_like(lin.bias)
+        mod, src = ctx.mod, ctx.h_src
+        dgo, dbo = grad_out(mod, mod.weight), grad_out(mod, mod.bias)
+        dhs = grad_out(src.lin, src.lin.bias, like=src.lin.bias) if src is not None else None
         dx, dh, dg, db = native().ln_bwd(dy, s, mean, rstd, w, ctx.p, mod.seed, mod.step, dgo, dbo, dhs)
-        if dhs is not None:
-            ctx.h_src[0]._psd_bias_hand = (ctx.h_src[1], dh.data_ptr(), dhs)
+        if src is not None:
+            hand_bias(src, dh, dhs)
         if ctx.x_grad_to is not None:
             # residual-branch gradient handed to the Linear that also consumes x: its dgrad GEMM
             # accumulates onto it (beta = 1) instead of autograd adding the two [M, H] gradients
-            ctx.x_grad_to._psd_pending_dx.append((ctx.tok, dx))
+            queue_dx(ctx.x_grad_to, ctx.tok, dx)
             return None, dh.view(dy.shape), dg, db, None, None, None
         return dx.view(dy.shape), dh.view(dy.shape), dg, db, None, None, None
 

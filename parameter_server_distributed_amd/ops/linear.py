@@ -44,6 +44,12 @@ faster path is kept. Measured on BERT-base (M = 8192 tokens) hipBLASLt wins most
 shapes, the split-K MFMA wgrad writing straight into the PS gradient buffer stays competitive.
 Feature ``linear_tune`` off pins everything to the MFMA kernels.
 
+Hand-overs (ops/handover.py holds the records, the tag on the output and every validity test; its docstring
+has the table): the forward takes the MX copy of x its producer left; the backward takes the MX copy of dy,
+the bias gradient a consumer LayerNorm / attention summed, a residual LayerNorm's gradient of x and the GELU
+hand-over of the consumer Linear (private to this file), then runs four steps -- activation backward, bwd-data,
+weight gradient, bias gradient (``_act_backward``, ``_bwd_data``, ``_weight_grad``, ``_bias_grad``).
+
 CPU tensors (and non-bf16 / unaligned shapes) use ``F.linear`` -- the reference the tests compare
 against.
 """
@@ -57,7 +63,7 @@ from ..utils.config import feature as _feat
 from .. import native
 from . import autotune as _at
 from .fp8_common import FP8_CALLS, mx_weight
-from .handover import take, take_dq8
+from .handover import grad_out, linear_src, tag_output, take, take_bias, take_dq8, take_dx
 
 ACTS = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 
@@ -115,17 +121,16 @@ def _dgrad_route(key: tuple, dy2: torch.Tensor, w: torch.Tensor, dx: torch.Tenso
     return cands[_at.choose(("linear",) + key, cands, "mfma", lambda: dx)]
 
 
-def _gelu_dgrad(ctx, dy2, w, pre, M: int, K: int, N: int) -> bool:
+def _gelu_dgrad(ctx, dy2, w, pre, M: int, K: int, N: int):
     """Bwd-data GEMM with the producing GELU Linear's backward in its epilogue: g = dY W * gelu'(pre)
     and that Linear's bias gradient (into its grad sink when the data plane installed one), handed
-    over with the producer's forward token; False when the kernel declines the shape (nothing ran)."""
+    over with the producer's forward token. Returns g, or None when the kernel declines the shape
+    (nothing ran)."""
     C = native()
     src = ctx.gelu_src
     g = torch.empty(M, K, dtype=dy2.dtype, device=dy2.device)
-    sink = getattr(src, "_psd_grad_sink", None)
-    db = sink(src.bias) if (sink is not None and src.bias is not None) else None
-    if db is None:
-        db = torch.empty(K, dtype=w.dtype, device=w.device)
+    db = (grad_out(src, src.bias, like=src.bias) if src.bias is not None
+          else torch.empty(K, dtype=w.dtype, device=w.device))
 
     def nn_():
         if not C.gemm_gelu_bwd_(dy2, w, True, False, pre, g, db):
@@ -140,11 +145,109 @@ def _gelu_dgrad(ctx, dy2, w, pre, M: int, K: int, N: int) -> bool:
                                               lambda: g)]
         fn()
     except _at.Declined:
-        return False
+        return None
     # keyed by the producer's forward token: its backward must find exactly this hand-over (a
     # fused gradient consumed as an ordinary one would apply GELU' twice)
     src._psd_gelu_hands[ctx.gelu_tok] = (g, db if src.bias is not None else None)
-    return True
+    return g
+
+
+def _take_gelu(mod, tok: int):
+    """Consume ``mod``'s GELU hand-over of the forward token ``tok`` -- (pre-activation gradient, bias gradient)
+    from the consumer Linear's bwd-data epilogue (``_gelu_dgrad``) -- or None; older ones, left by a backward that
+    never ran, are dropped."""
+    hands = mod._psd_gelu_hands
+    hand = hands.pop(tok, None)
+    for t in [t for t in hands if t < tok]:
+        del hands[t]
+    return hand
+
+
+def _act_backward(ctx, dy2, keep, hand):
+    """dy' = the gradient before the activation, and the bias gradient where the same pass sums it (else None)."""
+    if hand is not None:
+        if ctx.act != 2 or hand[0].data_ptr() != dy2.data_ptr():
+            raise RuntimeError(
+                "psd MfmaLinear: the consumer fused this GELU's backward (psd_gelu_input_from) but the "
+                "gradient reaching it is not the handed-over one -- the GELU output has another consumer")
+        # the consumer's bwd-data GEMM already applied this GELU's backward and summed the bias
+        # gradient (gemm_gelu_bwd_): dy IS the pre-activation gradient
+        return dy2, hand[1]
+    if ctx.act == 1:
+        return dy2 * (keep.view(dy2.shape) > 0), None
+    if ctx.act == 2 and ctx.has_bias and ctx.needs_input_grad[2] and dy2.shape[1] % 8 == 0:
+        # GELU backward and the bias gradient in one pass over dy / pre (kernels/gemm.hip)
+        db = grad_out(ctx.mod, ctx.mod.bias, like=ctx.mod.bias)
+        g = torch.empty_like(dy2)
+        native().gelu_bwd_colsum_(dy2, keep, g, db, False)
+        return g, db
+    if ctx.act == 2:
+        return torch.ops.aten.gelu_backward(dy2, keep, approximate="tanh"), None
+    return dy2, None
+
+
+def _bwd_data(ctx, dy2, x2, w, pre_src, got, dq8, wgrad8: bool):
+    """dx = dy' W, and [q_t(dy') [out, tokens] e4m3, its scales] where the dual quantiser made them for the fp8
+    weight gradient (else None). ``got``: x's other gradient (a residual LayerNorm's, ops/layernorm.py); ``dq8``:
+    the MX e5m2 copy of dy' its producer left."""
+    (M, K), N = x2.shape, w.shape[0]
+    dyT8 = None
+    if ctx.mx and _feat("fp8_dgrad"):
+        from . import quantize_mx, quantize_mx_dual, quantize_mx_t
+
+        # dx = q_e5m2(dy') . q_t(W): A = dy' [M, out] e5m2, B = W^T [in, out] e4m3, MX blocks along out
+        if wgrad8:  # one read of dy' for both of its MX copies; the row half is bitwise quantize_mx's
+            dyq, sdy, *dyT8 = quantize_mx_dual(dy2, e5m2_row=True, e5m2_t=False)
+        elif dq8 is not None:
+            dyq, sdy = dq8.q.view(dy2.shape), dq8.scales
+            ctx.mod.psd_mx_grad_handovers += 1
+        else:
+            dyq, sdy = quantize_mx(dy2, e5m2=True)
+        wtq, swt = quantize_mx_t(w)
+        dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
+        native().gemm_fp8_(dyq, wtq, sdy, swt, dx)
+        FP8_CALLS["lin_dgrad"] += 1
+        if got is not None:  # added after the GEMM (no beta = 1 fp8 epilogue)
+            dx = got.view(M, K).add_(dx)
+    elif got is not None:  # accumulated by the GEMM
+        dx = got.view(M, K)
+        dx.addmm_(dy2, w)
+    else:
+        dx = _gelu_dgrad(ctx, dy2, w, pre_src, M, K, N) if ctx.gelu_src is not None else None
+        if dx is None:
+            dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
+            _dgrad_route(("dgrad", M, K, N), dy2, w, dx)()
+    return dx.view(ctx.in_shape), dyT8
+
+
+def _weight_grad(ctx, dy2, x2, w, wgrad8: bool, dyT8):
+    """dW = dy'^T x into the grad sink's view of the weight, else a fresh tensor. ``dyT8``: q_t(dy') and its scales
+    from the bwd-data step, where it made them."""
+    C = native()
+    dw = grad_out(ctx.mod, ctx.mod.weight, like=w)
+    if wgrad8:
+        from . import quantize_mx_t
+
+        # dW = q_t(dy') . q_t(x)^T: A = dy'^T [out, tokens], B = x^T [in, tokens], both e4m3, K = tokens
+        dyT, sdyT = dyT8 or quantize_mx_t(dy2)
+        xT, sxT = quantize_mx_t(x2)
+        C.gemm_fp8_splitk_(dyT, xT, sdyT, sxT, dw, False, 1.0, 0)
+        FP8_CALLS["lin_wgrad"] += 1
+    else:
+        _route(("wgrad", *x2.shape, w.shape[0]), lambda: C.gemm_splitk_(dy2, x2, False, False, dw, False, 1.0, 0),
+               lambda: torch.mm(dy2.t(), x2, out=dw), dw)()
+    return dw
+
+
+def _bias_grad(ctx, dy2, db, hand):
+    """db = colsum(dy'): ``db`` where the activation backward summed it, else the consumer's ``hand`` (summed by a
+    LayerNorm's or the attention's backward, ops/layernorm.py, ops/attention.py), else the column-sum kernel."""
+    if db is None and hand is not None:
+        db = hand.db
+    if db is None and ctx.has_bias and ctx.needs_input_grad[2]:
+        db = grad_out(ctx.mod, ctx.mod.bias, like=ctx.mod.bias)
+        native().colsum_(dy2, db, False)
+    return db
 
 
 class _LinearFn(torch.autograd.Function):
@@ -214,126 +317,36 @@ class _LinearFn(torch.autograd.Function):
         src = getattr(mod, "_psd_gelu_from", None)
         # (not on the MX fp8 path: the e5m2-A GEMM has no activation epilogue, so no hand-over is made and
         # the producer runs gelu_bwd_colsum_ itself)
-        fuse = (src is not None and not use_mx and _feat("gelu_fuse") and getattr(x, "_psd_gelu_tok", None) is not None
-                and x._psd_gelu_tok == (id(src), src._psd_tok) and getattr(src, "_psd_gelu_pre", None) is not None)
+        fuse = (src is not None and not use_mx and _feat("gelu_fuse") and linear_src(x, src) is not None
+                and getattr(src, "_psd_gelu_pre", None) is not None)
         ctx.gelu_src = src if fuse else None
         ctx.gelu_tok = src._psd_tok if fuse else None
         pre_src = src._psd_gelu_pre if fuse else None
         # (ReLU keeps the output itself, not its [M, N] view: a saved view made under no_grad cannot be unpacked
         # once an in-place op -- the library route's relu_ -- has touched it)
         ctx.save_for_backward(x2, weight, out if act == 1 else aux, pre_src)
-        out._psd_src = (mod, ctx.tok)  # a consumer that can hand this Linear its bias gradient
+        tag_output(mod, out, ctx.tok)  # for the consumers that hand this Linear's backward something (ops/handover.py)
         if act == 2:
             mod._psd_gelu_pre = aux  # what a fused consumer's backward reads (also saved in this ctx)
-            out._psd_gelu_tok = (id(mod), ctx.tok)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        C = native()
         x2, w, keep, pre_src = ctx.saved_tensors
+        mod, tok = ctx.mod, ctx.tok
         dy2 = dy.reshape(-1, w.shape[0]).contiguous()
-        sink = getattr(ctx.mod, "_psd_grad_sink", None)
-        # the MX e5m2 copy of dy from the fused backward that produced it (ops/rmsnorm.py / ops/swiglu.py
-        # psd_mx_grad_to): taken -- and cleared -- here, used below only for exactly dy2
-        dq8 = take_dq8(ctx.mod, ctx.tok, dy2)
-        db = None
-        hands = ctx.mod._psd_gelu_hands
-        hand = hands.pop(ctx.tok, None)
-        for t in [t for t in hands if t < ctx.tok]:  # left by an aborted backward
-            del hands[t]
-        if hand is not None:
-            if ctx.act != 2 or hand[0].data_ptr() != dy2.data_ptr():
-                raise RuntimeError(
-                    "psd MfmaLinear: the consumer fused this GELU's backward (psd_gelu_input_from) but the "
-                    "gradient reaching it is not the handed-over one -- the GELU output has another consumer")
-            # the consumer's bwd-data GEMM already applied this GELU's backward and summed the bias
-            # gradient (gemm_gelu_bwd_): dy IS the pre-activation gradient
-            db = hand[1]
-        elif ctx.act == 1:
-            dy2 = dy2 * (keep.view(dy2.shape) > 0)
-        elif ctx.act == 2 and ctx.has_bias and ctx.needs_input_grad[2] and dy2.shape[1] % 8 == 0:
-            # GELU backward and the bias gradient in one pass over dy / pre (kernels/gemm.hip)
-            db = sink(ctx.mod.bias) if sink is not None else None
-            if db is None:
-                db = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
-            g = torch.empty_like(dy2)
-            C.gelu_bwd_colsum_(dy2, keep, g, db, False)
-            dy2 = g
-        elif ctx.act == 2:
-            dy2 = torch.ops.aten.gelu_backward(dy2, keep, approximate="tanh")
-        M, K, N = x2.shape[0], x2.shape[1], w.shape[0]
-        dx = None
-        pend = ctx.mod._psd_pending_dx
-        got = None
-        while pend:  # older hand-overs (of an aborted backward) are dropped
-            tok, g = pend.pop()
-            if tok == ctx.tok:
-                got = g
-                break
-        pend.clear()
+        # what the consumers of this forward's output left for this backward (ops/handover.py): each is taken --
+        # and cleared -- once, and used only for this forward's token and exactly this dy
+        dq8 = take_dq8(mod, tok, dy2)
+        dy2, db = _act_backward(ctx, dy2, keep, _take_gelu(mod, tok))
+        got, bias_hand = take_dx(mod, tok), take_bias(mod, tok, dy2)  # (the bias hand-over is of dy')
         # fp8 weight gradient (feature fp8_wgrad): MX blocks run along the tokens, whole 128-wide K-tiles
-        wgrad8 = ctx.mx and ctx.needs_input_grad[1] and M % 128 == 0 and _feat("fp8_wgrad")
-        dyT = sdyT = None  # q_t(dy') [out, tokens] e4m3, when the dual quantiser below made it
-        if ctx.needs_input_grad[0] and ctx.mx and _feat("fp8_dgrad"):
-            from . import quantize_mx, quantize_mx_dual, quantize_mx_t
-
-            # dx = q_e5m2(dy') . q_t(W): A = dy' [M, out] e5m2, B = W^T [in, out] e4m3, MX blocks along out
-            if wgrad8:  # one read of dy' for both of its MX copies; the row half is bitwise quantize_mx's
-                dyq, sdy, dyT, sdyT = quantize_mx_dual(dy2, e5m2_row=True, e5m2_t=False)
-            elif dq8 is not None:
-                dyq, sdy = dq8.q.view(dy2.shape), dq8.scales
-                ctx.mod.psd_mx_grad_handovers += 1
-            else:
-                dyq, sdy = quantize_mx(dy2, e5m2=True)
-            wtq, swt = quantize_mx_t(w)
-            dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
-            C.gemm_fp8_(dyq, wtq, sdy, swt, dx)
-            FP8_CALLS["lin_dgrad"] += 1
-            if got is not None:
-                # x's other gradient (a residual LayerNorm's): added after the GEMM (no beta = 1 fp8 epilogue)
-                dx = got.view(M, K).add_(dx)
-            dx = dx.view(ctx.in_shape)
-        elif ctx.needs_input_grad[0] and got is not None:
-            # x's other gradient (a residual LayerNorm's, ops/layernorm.py): accumulated by the GEMM
-            dx = got.view(M, K)
-            dx.addmm_(dy2, w)
-            dx = dx.view(ctx.in_shape)
-        elif ctx.needs_input_grad[0] and ctx.gelu_src is not None and _gelu_dgrad(ctx, dy2, w, pre_src, M, K, N):
-            dx = ctx.gelu_src._psd_gelu_hands[ctx.gelu_tok][0].view(ctx.in_shape)
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty(x2.shape, dtype=dy2.dtype, device=dy2.device)
-            _dgrad_route(("dgrad", M, K, N), dy2, w, dx)()
-            dx = dx.view(ctx.in_shape)
+        wgrad8 = ctx.mx and ctx.needs_input_grad[1] and x2.shape[0] % 128 == 0 and _feat("fp8_wgrad")
+        dx, dyT8 = _bwd_data(ctx, dy2, x2, w, pre_src, got, dq8, wgrad8) if ctx.needs_input_grad[0] else (None, None)
         if ctx.gelu_src is not None and ctx.gelu_src._psd_gelu_pre is pre_src:
             ctx.gelu_src._psd_gelu_pre = None  # not kept alive between steps
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = sink(ctx.mod.weight) if sink is not None else None
-            if dw is None:
-                dw = torch.empty(w.shape, dtype=w.dtype, device=w.device)
-            if wgrad8:
-                from . import quantize_mx_t
-
-                # dW = q_t(dy') . q_t(x)^T: A = dy'^T [out, tokens], B = x^T [in, tokens], both e4m3, K = tokens
-                if dyT is None:
-                    dyT, sdyT = quantize_mx_t(dy2)
-                xT, sxT = quantize_mx_t(x2)
-                C.gemm_fp8_splitk_(dyT, xT, sdyT, sxT, dw, False, 1.0, 0)
-                FP8_CALLS["lin_wgrad"] += 1
-            else:
-                _route(("wgrad", M, K, N), lambda: C.gemm_splitk_(dy2, x2, False, False, dw, False, 1.0, 0),
-                       lambda: torch.mm(dy2.t(), x2, out=dw), dw)()
-        bh = getattr(ctx.mod, "_psd_bias_hand", None)
-        ctx.mod._psd_bias_hand = None
-        if db is None and bh is not None and bh[0] == ctx.tok and bh[1] == dy2.data_ptr():
-            db = bh[2]  # summed by the consumer LayerNorm's backward (ops/layernorm.py)
-        if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
-            db = sink(ctx.mod.bias) if sink is not None else None
-            if db is None:
-                db = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
-            C.colsum_(dy2, db, False)
-        return dx, dw, db, None
+        dw = _weight_grad(ctx, dy2, x2, w, wgrad8, dyT8) if ctx.needs_input_grad[1] else None
+        return dx, dw, _bias_grad(ctx, dy2, db, bias_hand), None
 
 
 class MfmaLinear(nn.Linear):
@@ -347,14 +360,14 @@ class MfmaLinear(nn.Linear):
         self.fp8 = fp8
         self._psd_q8_pending = None  # ops.handover.Q8Pending of the input, left by the producing LayerNorm
         self.psd_mx_handovers = 0  # forwards that took it (tests / logs)
-        self._psd_dq8_pending = None  # (forward token, Q8Pending of dy) left by the fused backward that produced dy
+        self._psd_dq8_pending = None  # Q8Pending of dy with this forward's token, from the fused backward that made dy
         self.psd_mx_grad_handovers = 0  # backwards that took it
         self._psd_ran_mx = False  # whether the latest forward ran the MX recipe
-        self._psd_pending_dx: list = []  # gradients of the input handed over by a residual LayerNorm
+        self._psd_pending_dx: list = []  # ops.handover.PendingDx: gradients of the input from a residual LayerNorm
         self._psd_gelu_from = None  # psd_gelu_input_from: the GELU Linear whose output is this one's input
         self._psd_gelu_hands: dict = {}  # forward token -> (pre-activation gradient, bias gradient) from the consumer
         self._psd_gelu_pre = None
-        self._psd_bias_hand = None  # (forward token, dy data pointer, bias gradient) from a consumer LayerNorm
+        self._psd_bias_hand = None  # ops.handover.BiasHand from a consumer LayerNorm / attention
 
     def psd_gelu_input_from(self, src: "MfmaLinear") -> None:
         """Declare that this Linear's input is ``src``'s GELU output and nothing else reads it: the

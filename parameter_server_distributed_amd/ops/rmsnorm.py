@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from .. import native
 from ..utils.config import feature as _feat
-from .handover import Q8Pending, mx_grad_token
+from .handover import grad_out, leave_dq8, leave_q8, mx_grad_gate, mx_grad_token, mx_pair
 
 
 def add_rmsnorm_ref(r, h, weight, eps: float = 1e-6, p: float = 0.0, training: bool = False):
@@ -54,14 +54,12 @@ class _AddRMSFn(torch.autograd.Function):
         # MX hand-over (psd_mx_output_to): the forward also writes the MX e4m3 copy of y for the fp8 Linear that
         # reads it, which then skips its quantise pass (bitwise quantize_mx(y))
         cons = mod._psd_mx_to
-        q8 = sc8 = None
-        if cons is not None and _feat("fp8_llama_handover") and cons.psd_mx_input_ok(shp[-1]):
-            q8 = torch.empty(shp, dtype=torch.float8_e4m3fn, device=r.device)
-            sc8 = torch.empty(r.numel() // 32, dtype=torch.uint8, device=r.device)
+        make = cons is not None and _feat("fp8_llama_handover") and cons.psd_mx_input_ok(shp[-1])
+        q8, sc8 = mx_pair(shp, r.device) if make else (None, None)
         r_new, y, rstd = native().rms_fwd(r.contiguous(), None if h is None else h.contiguous(), weight, mod.eps, p,
                                           mod.seed, mod.step, q8, sc8)
         if q8 is not None:
-            cons._psd_q8_pending = Q8Pending(y.view(shp), q8, sc8)
+            leave_q8(cons, y.view(shp), q8, sc8)
         ctx.mod, ctx.p, ctx.had_h = mod, p, h is not None
         # backward hand-over (psd_mx_grad_to): the forward token of the fp8 Linear that produced exactly this h
         ctx.gtok = mx_grad_token(mod._psd_mxg_to, h)
@@ -78,22 +76,17 @@ class _AddRMSFn(torch.autograd.Function):
         dr_new, dy = grads if ctx.had_h else (None, grads[0])
         if dy is None:  # y unused: only the residual stream's gradient passes through
             dy = torch.zeros_like(r_new)
-        sink = getattr(mod, "_psd_grad_sink", None)
-        dgo = sink(mod.weight) if sink is not None else None
+        dgo = grad_out(mod, mod.weight)
         # the e5m2 copy of dh for the bwd-data GEMM of the Linear that produced h (it ran MX, fp8_dgrad is on)
-        lin = mod._psd_mxg_to
-        dq8 = dsc8 = None
         # (not at hidden 1536 / 2048: the wide kernels' one-slab backward with the side output only ties the plain
         # launch + quantize_mx, measured at 2048, profiles/rmsnorm_wide.md, so the Linear keeps its own pass there)
-        if (ctx.gtok is not None and _feat("fp8_llama_handover") and _feat("fp8_dgrad") and not _feat("fp8_wgrad")
-                and not 1536 <= r_new.shape[-1] <= 2048):
-            dq8 = torch.empty(r_new.shape, dtype=torch.float8_e5m2, device=r_new.device)
-            dsc8 = torch.empty(r_new.numel() // 32, dtype=torch.uint8, device=r_new.device)
+        gate = mx_grad_gate(ctx.gtok) and not 1536 <= r_new.shape[-1] <= 2048
+        dq8, dsc8 = mx_pair(r_new.shape, r_new.device, e5m2=True) if gate else (None, None)
         dr, dh, dg = native().rms_bwd(dy.contiguous().view(r_new.shape),
                                       None if dr_new is None else dr_new.contiguous().view(r_new.shape), r_new, rstd,
                                       w, ctx.p, mod.seed, mod.step, ctx.had_h, dgo, dq8, dsc8)
         if dq8 is not None:
-            lin._psd_dq8_pending = (ctx.gtok, Q8Pending(dh.view(-1, dh.shape[-1]), dq8, dsc8))
+            leave_dq8(mod._psd_mxg_to, ctx.gtok, dh, dq8, dsc8)
         return dr, dh, dg, None, None
 
 
@@ -124,7 +117,7 @@ class FusedAddRMSNorm(nn.Module):
         """Declare that ``lin`` (an ``MfmaLinear``) produces this norm's branch input ``h``, so that ``lin``'s
         output gradient is this norm's ``dh``: when that forward of ``lin`` ran the MX fp8 recipe and ``fp8_dgrad``
         is on, the fused backward also writes the MX e5m2 copy of ``dh`` and leaves it on ``lin``
-        (``_psd_dq8_pending``, with ``lin``'s forward token) for its bwd-data GEMM."""
+        (``ops.handover.leave_dq8``, with ``lin``'s forward token) for its bwd-data GEMM."""
         object.__setattr__(self, "_psd_mxg_to", lin)
 
     def extra_repr(self) -> str:

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from ..utils.config import feature as _feat
 from .. import native
+from .handover import drop_tag
 
 HEAD_DIM = 64
 
@@ -116,7 +117,8 @@ class RotaryQK(nn.Module):
     returns the same tensor object, the backward rotates the incoming gradient by the inverse angle.
     Everything else takes ``rope_ref`` through ordinary autograd, out of place.
 
-    The bias hand-over: the tensor returned carries no ``_psd_src`` tag. The attention backward would
+    The bias hand-over: the tensor returned no longer carries the producing Linear's tag
+    (``ops.handover.drop_tag``). The attention backward would
     otherwise hand the QKV Linear the column sums of the ``dQKV`` it wrote (ops/attention.py), which the
     Linear accepts by the gradient's data pointer (ops/linear.py) -- and the in-place inverse rotation keeps
     that pointer while changing the values. Without the tag the attention makes no hand-over and the
@@ -163,7 +165,6 @@ class RotaryQK(nn.Module):
             if qkv.is_leaf and qkv.requires_grad:  # autograd allows no in-place update of such a leaf
                 qkv = qkv.clone()
             out = _RopeFn.apply(qkv, self, lens, doc_start)
-            if hasattr(out, "_psd_src"):  # mark_dirty returns the same Python object, tag included
-                del out._psd_src
+            drop_tag(out)  # mark_dirty returns the same Python object, the producing Linear's tag included
             return out
         return rope_ref(qkv, self.heads, self.cos, self.sin, lens, doc_start)

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from .. import native
 from ..utils.config import feature as _feat
-from .handover import Q8Pending, mx_grad_token
+from .handover import leave_dq8, leave_q8, mx_grad_gate, mx_grad_token, mx_pair
 
 
 def swiglu_ref(gu):
@@ -53,26 +53,22 @@ class _SwigluFn(torch.autograd.Function):
             # MX hand-over (psd_mx_output_to): also the MX e4m3 copy of a for the fp8 Linear that reads it
             cons = mod._psd_mx_to
             if cons is not None and cons.psd_mx_input_ok(f):
-                q8 = torch.empty(*gu.shape[:-1], f, dtype=torch.float8_e4m3fn, device=gu.device)
-                sc8 = torch.empty(q8.numel() // 32, dtype=torch.uint8, device=gu.device)
+                q8, sc8 = mx_pair((*gu.shape[:-1], f), gu.device)
             # backward hand-over (psd_mx_grad_to): the forward token of the fp8 Linear that produced exactly this gu
             ctx.gtok = mx_grad_token(mod._psd_mxg_to, gu)
         a = native().swiglu_fwd(gu, 0, q8, sc8)
         if q8 is not None:
-            cons._psd_q8_pending = Q8Pending(a, q8, sc8)
+            leave_q8(cons, a, q8, sc8)
         return a
 
     @staticmethod
     def backward(ctx, da):
         (gu,) = ctx.saved_tensors
-        dq8 = dsc8 = None
-        if ctx.gtok is not None and _feat("fp8_llama_handover") and _feat("fp8_dgrad") and not _feat("fp8_wgrad"):
-            # the e5m2 copy of dgu for the bwd-data GEMM of the gate/up Linear (it ran MX)
-            dq8 = torch.empty(gu.shape, dtype=torch.float8_e5m2, device=gu.device)
-            dsc8 = torch.empty(gu.numel() // 32, dtype=torch.uint8, device=gu.device)
+        # the e5m2 copy of dgu for the bwd-data GEMM of the gate/up Linear (it ran MX)
+        dq8, dsc8 = mx_pair(gu.shape, gu.device, e5m2=True) if mx_grad_gate(ctx.gtok) else (None, None)
         dgu = native().swiglu_bwd(da.contiguous(), gu, 0, dq8, dsc8)
         if dq8 is not None:
-            ctx.mod._psd_mxg_to._psd_dq8_pending = (ctx.gtok, Q8Pending(dgu.view(-1, dgu.shape[-1]), dq8, dsc8))
+            leave_dq8(ctx.mod._psd_mxg_to, ctx.gtok, dgu, dq8, dsc8)
         return dgu, None
 
 
@@ -101,8 +97,8 @@ class SwiGLU(nn.Module):
     def psd_mx_grad_to(self, lin) -> None:
         """Declare that ``lin`` (an ``MfmaLinear``) produces ``gu``, so that ``lin``'s output gradient is this
         activation's ``dgu``: when that forward of ``lin`` ran the MX fp8 recipe and ``fp8_dgrad`` is on, the backward
-        kernel also writes the MX e5m2 copy of ``dgu`` and leaves it on ``lin`` (``_psd_dq8_pending``, with ``lin``'s
-        forward token) for its bwd-data GEMM."""
+        kernel also writes the MX e5m2 copy of ``dgu`` and leaves it on ``lin`` (``ops.handover.leave_dq8``, with
+        ``lin``'s forward token) for its bwd-data GEMM."""
         object.__setattr__(self, "_psd_mxg_to", lin)
 
     def forward(self, gu):

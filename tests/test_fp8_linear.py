@@ -287,6 +287,36 @@ def test_mx_linear_against_fp32_linear(gpu):
 
 
 @pytest.mark.gpu
+def test_mx_linear_ignores_a_dy_copy_left_for_an_earlier_forward(gpu, monkeypatch):
+    """A ``Q8Pending`` made for exactly this dy but carrying the previous forward's token (a backward that never
+    ran left it) is cleared and not used: dx and dW keep the bits of the run with nothing planted. 128 x 128 on
+    128 tokens is the smallest shape of the MX path."""
+    from parameter_server_distributed_amd.ops.handover import Q8Pending
+    from parameter_server_distributed_amd.ops.linear import MfmaLinear
+
+    monkeypatch.setenv("PSD_FEATURES", "linear_tune=0")
+    torch.manual_seed(0)
+    lin = _bf16_params(MfmaLinear(128, 128, bias=False, fp8="mx").to(gpu))
+    x = torch.randn(128, 128, device=gpu).to(torch.bfloat16).requires_grad_(True)
+    dy = torch.randn(128, 128, device=gpu).to(torch.bfloat16)
+    runs = []
+    for plant in (False, True):
+        x.grad = lin.weight.grad = None
+        stale = lin._psd_tok if plant else None
+        y = lin(x)
+        assert lin._psd_ran_mx and lin._psd_tok != stale
+        if plant:
+            lin._psd_dq8_pending = Q8Pending(dy, torch.zeros(128, 128, device=gpu).to(torch.float8_e5m2),
+                                             torch.zeros(128 * 128 // 32, device=gpu, dtype=torch.uint8), stale)
+        before = lin.psd_mx_grad_handovers
+        y.backward(dy)
+        assert lin._psd_dq8_pending is None and lin.psd_mx_grad_handovers == before
+        runs.append((x.grad.clone(), lin.weight.grad.clone()))
+    assert bool(runs[0][0].abs().sum() > 0)  # (the zero payload would have given dx = 0)
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+@pytest.mark.gpu
 def test_mx_linear_outside_the_contract_runs_the_bf16_path(gpu, monkeypatch):
     from parameter_server_distributed_amd.ops import conv as conv_ops
 

@@ -1,5 +1,5 @@
-"""The conv / BN hand-over records and helpers (ops/handover.py) and the single copies of the routing
-pieces in ops/conv.py (_dgrad_route, _write_dw), on the CPU with fake candidates and pinned autotune
+"""The conv / BN and the transformer hand-over records and helpers (ops/handover.py) and the single copies of the
+routing pieces in ops/conv.py (_dgrad_route, _write_dw), on the CPU with fake candidates and pinned autotune
 decisions: nothing is timed and no kernel runs. One GPU test: a stale record is ignored, not used."""
 import copy
 import types
@@ -30,7 +30,7 @@ def test_records_index_and_unpack_like_the_tuples_they_replace():
     assert ho.FoldPending("g", "coef", "y", "P")[3] == "P"
     y, part, rows = ho.StatsPending("y", "part", 2)
     assert (y, part, rows) == ("y", "part", 2)
-    t, q, sc = ho.Q8Pending("t", "q", "scales")
+    t, q, sc = ho.Q8Pending("t", "q", "scales")[:3]  # (a fourth field follows: the Linear's forward token)
     assert (t, q, sc) == ("t", "q", "scales") and ho.Q8Pending("t", "q", "s")[1] == "q"
 
 
@@ -115,6 +115,154 @@ def test_bn_reexports_the_moved_names():
     from parameter_server_distributed_amd.ops import bn
 
     assert bn.StridedDr is ho.StridedDr and bn.take_dr is ho.take_dr
+
+
+# ---------------------------------------------------------------------------------------------
+# the transformer side: the Linear's tag, tokens and takes
+
+
+def test_transformer_records_index_and_unpack_like_the_tuples_they_replace():
+    lin, tok = ho.LinearSrc("lin", 3)
+    assert (lin, tok) == ("lin", 3) and ho.LinearSrc("lin", 3)[1] == 3
+    tok, ptr, db = ho.BiasHand(3, 4096, "db")
+    assert (tok, ptr, db) == (3, 4096, "db") and ho.BiasHand(3, 4096, "db")[2] == "db"
+    tok, g = ho.PendingDx(3, "g")
+    assert (tok, g) == (3, "g") and ho.PendingDx(3, "g")[0] == 3
+    assert ho.Q8Pending("t", "q", "s").tok is None and len(ho.Q8Pending("t", "q", "s")) == 4
+    assert ho.Q8Pending("t", "q", "s", 7).tok == 7 and ho.Q8Pending("t", "q", "s", 7)[3] == 7
+
+
+def _lin(tok=5, bias="b", act=None, ran_mx=True):
+    return types.SimpleNamespace(_psd_tok=tok, bias=bias, act=act, _psd_ran_mx=ran_mx)
+
+
+def test_linear_src_is_the_latest_forward_of_the_named_linear():
+    lin, other, out = _lin(), _lin(), torch.zeros(2)
+    assert ho.linear_src(out) is None and ho.linear_src(out, lin) is None  # no tag
+    ho.tag_output(lin, out, 5)
+    assert ho.linear_src(out) == (lin, 5) and ho.linear_src(out, lin).lin is lin
+    assert ho.linear_src(out, other) is None  # the tag names another module
+    lin._psd_tok = 6  # the Linear ran again: the tag's token is old
+    assert ho.linear_src(out) is None and ho.linear_src(out, lin) is None
+    ho.drop_tag(out)
+    assert not hasattr(out, "_psd_src")
+    ho.drop_tag(out)  # nothing to drop
+    assert ho.forward_token(lin) == 6 and ho.forward_token(None) is None
+    assert ho.forward_token(types.SimpleNamespace()) is None
+
+
+@pytest.mark.parametrize("name,lin,tag_tok,want", [
+    ("bias absent", _lin(bias=None), 5, False),
+    ("act gelu", _lin(act="gelu"), 5, False),
+    ("stale token", _lin(), 4, False),
+    ("fresh", _lin(), 5, True),
+    ("fresh, act 'none'", _lin(act="none"), 5, True),
+])
+def test_bias_src_truth_table(name, lin, tag_tok, want):
+    out = torch.zeros(2)
+    assert ho.bias_src(out) is None
+    ho.tag_output(lin, out, tag_tok)
+    src = ho.bias_src(out)
+    assert (src is not None) is want
+    if want:
+        assert src.lin is lin and src.tok == 5
+
+
+@pytest.mark.parametrize("name,declared_is_tagged,ran_mx,tag_tok,want", [
+    ("another Linear", False, True, 5, None),
+    ("did not run MX", True, False, 5, None),
+    ("stale token", True, True, 4, None),
+    ("fresh", True, True, 5, 5),
+])
+def test_mx_grad_token_truth_table(name, declared_is_tagged, ran_mx, tag_tok, want):
+    lin, out = _lin(ran_mx=ran_mx), torch.zeros(2)
+    ho.tag_output(lin if declared_is_tagged else _lin(), out, tag_tok)
+    assert ho.mx_grad_token(lin, out) == want
+    assert ho.mx_grad_token(None, out) is None and ho.mx_grad_token(lin, None) is None
+    assert ho.mx_grad_token(lin, torch.zeros(2)) is None  # no tag
+
+
+def test_take_dq8_four_cases():
+    dy = torch.zeros(4, 8)
+    cases = {"wrong token": (6, dy, False), "other data_ptr": (5, torch.zeros(4, 8), False),
+             "same data_ptr, other shape": (5, dy.view(8, 4), False), "match": (5, dy, True)}
+    for name, (tok, t, hit) in cases.items():
+        mod = types.SimpleNamespace()
+        ho.leave_dq8(mod, tok, t, "q", "s")
+        rec = mod._psd_dq8_pending
+        assert isinstance(rec, ho.Q8Pending) and rec.tok == tok and rec.q == "q"
+        got = ho.take_dq8(mod, 5, dy)
+        assert (got is rec) if hit else (got is None), name
+        assert mod._psd_dq8_pending is None, name
+    # the record is keyed by the [tokens, out] view the Linear's backward compares
+    mod, dy3 = types.SimpleNamespace(), torch.zeros(2, 2, 8)
+    ho.leave_dq8(mod, 5, dy3, "q", "s")
+    assert ho.take_dq8(mod, 5, dy3.view(4, 8)).scales == "s"
+    assert ho.take_dq8(mod, 5, dy) is None  # nothing left
+
+
+def test_take_bias_four_cases():
+    dy = torch.zeros(4, 8)
+    cases = {"wrong token": (6, dy, False), "other data_ptr": (5, torch.zeros(4, 8), False), "match": (5, dy, True),
+             "match by data_ptr alone": (5, dy.view(8, 4), True)}
+    for name, (tok, t, hit) in cases.items():
+        lin = _lin()
+        ho.hand_bias(ho.LinearSrc(lin, tok), t, "db")
+        rec = lin._psd_bias_hand
+        assert isinstance(rec, ho.BiasHand) and rec == (tok, t.data_ptr(), "db")
+        got = ho.take_bias(lin, 5, dy)
+        assert (got is rec and got.db == "db") if hit else (got is None), name
+        assert lin._psd_bias_hand is None, name
+    assert ho.take_bias(types.SimpleNamespace(), 5, dy) is None  # absent
+
+
+def test_take_dx_takes_its_own_token_and_empties_the_queue():
+    mod = types.SimpleNamespace(_psd_pending_dx=[])
+    for tok, g in ((4, "old"), (5, "mine"), (6, "newer-stale")):
+        ho.queue_dx(mod, tok, g)
+    assert all(isinstance(e, ho.PendingDx) for e in mod._psd_pending_dx)
+    assert ho.take_dx(mod, 5) == "mine" and mod._psd_pending_dx == []
+    mod._psd_pending_dx += [(5, "first"), (5, "newest")]  # raw tuples, as a test plants them
+    assert ho.take_dx(mod, 5) == "newest" and mod._psd_pending_dx == []
+    mod._psd_pending_dx += [ho.PendingDx(4, "old"), ho.PendingDx(6, "newer")]
+    assert ho.take_dx(mod, 5) is None and mod._psd_pending_dx == []
+    assert ho.take_dx(mod, 5) is None
+
+
+def test_grad_out():
+    param, view = torch.zeros(3, 2, dtype=torch.bfloat16), torch.zeros(3, 2)
+    mod = types.SimpleNamespace(_psd_grad_sink=lambda p: view if p is param else None)
+    assert ho.grad_out(mod, param) is view and ho.grad_out(mod, param, like=param) is view
+    other = torch.zeros(5, dtype=torch.float64)
+    assert ho.grad_out(mod, other) is None  # the sink has no view of it
+    fresh = ho.grad_out(mod, other, like=other)
+    assert fresh is not other and (fresh.shape, fresh.dtype, fresh.device) == (other.shape, other.dtype, other.device)
+    bare = types.SimpleNamespace()
+    assert ho.grad_out(bare, param) is None
+    fresh = ho.grad_out(bare, param, like=param)
+    assert fresh is not param and fresh.shape == param.shape and fresh.dtype == torch.bfloat16
+
+
+def test_leave_q8_and_mx_pair():
+    cons, t = types.SimpleNamespace(), torch.zeros(2, 3, 64)
+    q, sc = ho.mx_pair(t.shape, t.device)
+    assert q.shape == t.shape and q.dtype == torch.float8_e4m3fn and sc.shape == (12,) and sc.dtype == torch.uint8
+    q5, sc5 = ho.mx_pair((4, 96), t.device, e5m2=True)
+    assert q5.shape == (4, 96) and q5.dtype == torch.float8_e5m2 and sc5.shape == (12,) and sc5.dtype == torch.uint8
+    ho.leave_q8(cons, t, q, sc)
+    rec = cons._psd_q8_pending
+    assert isinstance(rec, ho.Q8Pending) and rec.t is t and rec.q is q and rec.scales is sc and rec.tok is None
+    assert ho.take(cons, "_psd_q8_pending", t, strides=True) is rec and cons._psd_q8_pending is None
+
+
+@pytest.mark.parametrize("tok", [None, 5])
+@pytest.mark.parametrize("handover", [0, 1])
+@pytest.mark.parametrize("dgrad", [0, 1])
+@pytest.mark.parametrize("wgrad", [0, 1])
+def test_mx_grad_gate(monkeypatch, tok, handover, dgrad, wgrad):
+    monkeypatch.setenv("PSD_FEATURES", f"fp8_llama_handover={handover},fp8_dgrad={dgrad},fp8_wgrad={wgrad}")
+    want = tok is not None and handover == 1 and dgrad == 1 and wgrad == 0
+    assert ho.mx_grad_gate(tok) is want
 
 
 # ---------------------------------------------------------------------------------------------
