@@ -31,9 +31,9 @@ ARCH = os.environ.get("PSD_OFFLOAD_ARCH", "gfx950")
 _SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # rmsnorm.hip, swiglu.hip: the same for the MX side outputs' scaling chains (v * 2^-e per element before the fp8
 # conversion), so that a kernel's variants with and without the side output run the same scalar arithmetic.
-# rmsnorm_wide.hip: as rmsnorm.hip.
+# rmsnorm_wide.hip, layernorm_wide.hip: as rmsnorm.hip.
 HIP_FILE_FLAGS = {"lmhead_xent.hip": _SCALAR_F32, "rmsnorm.hip": _SCALAR_F32, "rmsnorm_wide.hip": _SCALAR_F32,
-                  "swiglu.hip": _SCALAR_F32}
+                  "layernorm_wide.hip": _SCALAR_F32, "swiglu.hip": _SCALAR_F32}
 
 
 def _rocm() -> Path:

@@ -21,7 +21,8 @@ struct LnArgs {
   uint16_t* dgamma;       // bwd out [H] bf16 (may be the PS gradient sink)
   uint16_t* dbeta;        // bwd out [H] bf16
   uint16_t* dhsum;        // bwd out [H] bf16 or null: column sums of dh (the branch Linear's bias gradient)
-  float* part;            // bwd workspace [ln_bwd_blocks(rows)][3][H] fp32 ([2] without dhsum)
+  float* part;            // bwd workspace [ln_bwd_blocks(rows)][3][H] fp32 ([2] without dhsum; the wide kernels:
+                          // [ln_wide_bwd_blocks(rows, H)])
   const int64_t* step;    // device step counter mixed into the dropout hash (may be null)
   int64_t rows;
   int32_t H;
@@ -66,6 +67,15 @@ bool ln_supported(int H);
 int ln_bwd_blocks(int64_t rows);
 hipError_t launch_ln_fwd(const LnArgs& a, hipStream_t stream);
 hipError_t launch_ln_bwd(const LnArgs& a, hipStream_t stream);
+// kernels/layernorm_wide.hip: the same LnArgs at H = 256 n, n = 5 .. 32 (1280 .. 8192), one workgroup per row per
+// round; x, h, gamma, beta, s, dy and q8 16-byte aligned. The grids: forward min(rows, LN_WIDE_FWD_CAP), backward
+// min(ceil(rows / LN_WIDE_BWD_ROWS), LN_WIDE_BWD_CAP up to H = 4096, half of it above)
+constexpr int LN_WIDE_FWD_CAP = 2048, LN_WIDE_BWD_ROWS = 16, LN_WIDE_BWD_CAP = 1024;
+bool ln_wide_supported(int H);
+int ln_wide_fwd_blocks(int64_t rows);
+int ln_wide_bwd_blocks(int64_t rows, int H);
+hipError_t launch_ln_wide_fwd(const LnArgs& a, hipStream_t stream);
+hipError_t launch_ln_wide_bwd(const LnArgs& a, hipStream_t stream);
 int emb_ln_bwd_blocks(int64_t rows);
 // part [nblk][NP][H] fp32 block partials -> bf16: row 0 into dgamma, row 1 into dbeta, rows 2.. into extra
 // [(NP - 2), H]; summed in a fixed order (deterministic). Pointers of rows NP does not reach are not used.

@@ -1,4 +1,5 @@
-// Tensor glue for the fused residual + dropout + LayerNorm kernels (kernels/layernorm.hip).
+// Tensor glue for the fused residual + dropout + LayerNorm kernels (kernels/layernorm.hip at H = 768 / 1024,
+// kernels/layernorm_wide.hip at H = 256 n, n = 5 .. 32).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 
@@ -16,6 +17,18 @@ void check_bf16(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd ln: ", what,
               " must be a contiguous bf16 device tensor");
 }
+// a hidden size one of the two kernel families takes; true for the wide one (layernorm_wide.hip)
+bool check_hidden(const char* op, int64_t H) {
+  const bool wide = H <= 8192 && ln_wide_supported((int)H);
+  TORCH_CHECK(wide || (H <= 1024 && ln_supported((int)H)), op,
+              ": H must be 768, 1024 or a multiple of 256 from 1280 to 8192, got ", H);
+  return wide;
+}
+// the wide kernels move 16 bytes per access: activations, gamma / beta and the MX payload
+void check_align16(const char* op, bool wide, int64_t H, const at::Tensor& t, const char* what) {
+  TORCH_CHECK(!wide || (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, op, ": ", what,
+              " must be 16-byte aligned at H = ", H);
+}
 }  // namespace
 
 std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const at::Tensor& gamma, const at::Tensor& beta,
@@ -26,8 +39,13 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
   check_bf16(gamma, "gamma");
   check_bf16(beta, "beta");
   const int64_t H = x.size(-1);
-  TORCH_CHECK(ln_supported((int)H) && h.sizes() == x.sizes() && gamma.numel() == H && beta.numel() == H,
-              "psd ln fwd: shapes (H must be 768 or 1024)");
+  const bool wide = check_hidden("psd ln fwd", H);
+  TORCH_CHECK(h.sizes() == x.sizes() && gamma.numel() == H && beta.numel() == H,
+              "psd ln fwd: shapes (h like x, gamma and beta [H])");
+  check_align16("psd ln fwd", wide, H, x, "x");
+  check_align16("psd ln fwd", wide, H, h, "h");
+  check_align16("psd ln fwd", wide, H, gamma, "gamma");
+  check_align16("psd ln fwd", wide, H, beta, "beta");
   const c10::DeviceGuard g(x.device());
   const int64_t rows = x.numel() / H;
   // the MX e4m3 copy of y for the consumer Linear (both outputs or neither)
@@ -40,6 +58,7 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
     TORCH_CHECK(sc8_out->scalar_type() == at::kByte && sc8_out->is_contiguous() && sc8_out->numel() == x.numel() / 32 &&
                     sc8_out->device() == x.device(),
                 "psd ln fwd: sc8 must be uint8 [rows, H / 32]");
+    check_align16("psd ln fwd", wide, H, *q8_out, "q8");
   }
   at::Tensor y = at::empty_like(x), s = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
@@ -61,7 +80,7 @@ std::vector<at::Tensor> ln_fwd(const at::Tensor& x, const at::Tensor& h, const a
   a.eps = (float)eps;
   a.p = (float)p;
   a.seed = (uint32_t)seed;
-  hipError_t e = launch_ln_fwd(a, stream_of(x));
+  hipError_t e = wide ? launch_ln_wide_fwd(a, stream_of(x)) : launch_ln_fwd(a, stream_of(x));
   check_hip(e, "psd ln fwd");
   return {y, s, mean, rstd};
 }
@@ -75,7 +94,11 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
   check_bf16(s, "s");
   check_bf16(gamma, "gamma");
   const int64_t H = s.size(-1);
-  TORCH_CHECK(ln_supported((int)H) && dy.sizes() == s.sizes() && gamma.numel() == H, "psd ln bwd: shapes");
+  const bool wide = check_hidden("psd ln bwd", H);
+  TORCH_CHECK(dy.sizes() == s.sizes() && gamma.numel() == H, "psd ln bwd: shapes");
+  check_align16("psd ln bwd", wide, H, dy, "dy");
+  check_align16("psd ln bwd", wide, H, s, "s");
+  check_align16("psd ln bwd", wide, H, gamma, "gamma");
   const c10::DeviceGuard g(s.device());
   const int64_t rows = s.numel() / H;
   TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows, "psd ln bwd: statistics");
@@ -89,7 +112,8 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
     check_bf16(*dhsum_out, "dhsum");
     TORCH_CHECK(dhsum_out->numel() == H, "psd ln bwd: dhsum must be [H]");
   }
-  at::Tensor part = at::empty({(int64_t)ln_bwd_blocks(rows) * (hs ? 3 : 2) * H}, s.options().dtype(at::kFloat));
+  const int blocks = wide ? ln_wide_bwd_blocks(rows, (int)H) : ln_bwd_blocks(rows);
+  at::Tensor part = at::empty({(int64_t)blocks * (hs ? 3 : 2) * H}, s.options().dtype(at::kFloat));
   LnArgs a{};
   a.dy = cu16(dy);
   a.s = u16(s);
@@ -107,7 +131,7 @@ std::vector<at::Tensor> ln_bwd(const at::Tensor& dy_in, const at::Tensor& s, con
   a.H = (int32_t)H;
   a.p = (float)p;
   a.seed = (uint32_t)seed;
-  hipError_t e = launch_ln_bwd(a, stream_of(s));
+  hipError_t e = wide ? launch_ln_wide_bwd(a, stream_of(s)) : launch_ln_bwd(a, stream_of(s));
   check_hip(e, "psd ln bwd");
   return {dx, dh, dgamma, dbeta};
 }

@@ -1,5 +1,7 @@
 """``LayerNorm(x + dropout(h))`` -- the transformer residual tail -- on the fused gfx950 kernels of
-``csrc/kernels/layernorm.hip`` (one pass forward, one pass backward + a tiny gamma/beta finalize).
+``csrc/kernels/layernorm.hip`` (hidden 768 / 1024: one wave per row) and ``layernorm_wide.hip`` (hidden 256 n,
+n = 5 .. 32: one workgroup per row; feature ``layernorm_wide``): one pass forward, one pass backward + a tiny
+gamma/beta finalize.
 
 Dropout masks come from a counter-based hash of (per-site seed, device step counter, element), so
 they are regenerated in backward instead of stored, and a replayed hipGraph draws fresh masks each
@@ -84,8 +86,14 @@ class FusedAddLayerNorm(nn.LayerNorm):
         return [self.weight, self.bias]
 
     def _kernel_ok(self, x, h) -> bool:
-        return (x.is_cuda and x.dtype == torch.bfloat16 and h.dtype == torch.bfloat16 and x.shape == h.shape
-                and x.shape[-1] in (768, 1024) and self.weight is not None and self.weight.dtype == torch.bfloat16)
+        hid = x.shape[-1]
+        ok = (x.is_cuda and x.dtype == torch.bfloat16 and h.dtype == torch.bfloat16 and x.shape == h.shape
+              and self.weight is not None and self.weight.dtype == torch.bfloat16)
+        if not ok or hid in (768, 1024):
+            return ok
+        # layernorm_wide.hip: 16-byte accesses (contiguous tensors: the narrow sizes are copied where they are not)
+        return (hid % 256 == 0 and 1280 <= hid <= 8192 and _feat("layernorm_wide") and self.bias is not None
+                and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (x, h, self.weight, self.bias)))
 
     def forward(self, x, h, x_grad_to=None):
         """``x_grad_to``: the ``MfmaLinear`` that consumed ``x`` earlier in the forward (the block's

@@ -100,6 +100,9 @@ FEATURES: dict[str, tuple[bool, str]] = {
     "fp8_dgrad": (True, "fp8 e5m2-dY bwd-data of the fp8 convolutions and fp8 Linear layers"),
     "fp8_wgrad": (False, "fp8 e4m3 x e4m3 split-K weight gradient of the fp8 Linear layers (tokens % 128 == 0); off: bf16"),
     "fp8_ln_handover": (True, "the fused LayerNorm writes the MX e4m3 input of the fp8 Linear that consumes it"),
+    "layernorm_wide": (True, "the fused LayerNorm kernels also at hidden sizes 256 n, n = 5 .. 32 (1280 .. 8192: "
+                             "kernels/layernorm_wide.hip; 16-byte-aligned tensors); off: those sizes take the torch "
+                             "composite, as every other size does"),
     "fp8_llama_handover": (True, "the Llama block's fused RMSNorm / SwiGLU kernels write the MX operands of the fp8 "
                                  "Linears around them (e4m3 inputs forward, e5m2 output gradients backward); "
                                  "off: stand-alone quantize_mx passes, bitwise the same results"),
