@@ -24,15 +24,36 @@ void check_window(int64_t window, bool causal) {
   TORCH_CHECK(window >= 0, "psd attn: window must be >= 0 (0: off), got ", window);
   TORCH_CHECK(window == 0 || causal, "psd attn: window needs causal=True (the kernels serve no symmetric window)");
 }
+// grouped-query attention: kv_heads K/V heads (0: as many as heads), a divisor of heads; fewer than heads is causal
+// only, has its own packed width and is served by the streaming kernels (also checked first: argument errors,
+// whatever the tensors are). Returns the K/V head count.
+int64_t check_kv_heads(int64_t kv_heads, int64_t heads, bool causal, const at::Tensor& qkv) {
+  if (heads <= 0) return heads;  // make_args reports it
+  TORCH_CHECK(kv_heads >= 0 && kv_heads <= heads && (kv_heads == 0 || heads % kv_heads == 0),
+              "psd attn: kv_heads must be 0 (as many as heads) or a divisor of heads = ", heads, ", got ", kv_heads);
+  const int64_t hkv = kv_heads == 0 ? heads : kv_heads;
+  if (hkv == heads) return hkv;
+  TORCH_CHECK(causal,
+              "psd attn: kv_heads < heads needs causal=True (the kernels serve no bidirectional grouped-query attention)");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (heads + 2 * hkv) * 64,
+              "psd attn: with kv_heads = ", hkv, " qkv must be [B, S, (heads + 2*kv_heads)*64], got last dim ",
+              qkv.dim() == 3 ? qkv.size(2) : -1, " with heads = ", heads);
+  TORCH_CHECK(attn_long_supported((int)qkv.size(1), 64),
+              "psd attn: kv_heads < heads is served by the streaming kernels only (S a multiple of 64 in 192 .. 4096), "
+              "got S = ", qkv.size(1));
+  return hkv;
+}
 void check_attn(const at::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), "psd attn: ", what,
               " must be a contiguous bf16 device tensor");
 }
+// hkv: check_kv_heads' result. The head dim is qkv.size(2) / (heads + 2 * hkv).
 AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed, const c10::optional<at::Tensor>& step,
                    const c10::optional<at::Tensor>& lens, int64_t grid_cap, bool causal,
-                   const c10::optional<at::Tensor>& doc_start, int64_t window) {
-  TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
-  const int64_t dh = qkv.size(2) / (3 * heads);
+                   const c10::optional<at::Tensor>& doc_start, int64_t window, int64_t hkv) {
+  // (a grouped-query qkv, hkv < heads, has passed check_kv_heads: its width is (heads + 2 hkv) * 64)
+  TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (heads + 2 * hkv) == 0, "psd attn: qkv must be [B, S, 3*H*Dh]");
+  const int64_t dh = qkv.size(2) / (heads + 2 * hkv);
   TORCH_CHECK(attn_supported((int)qkv.size(1), (int)dh) || attn_long_supported((int)qkv.size(1), (int)dh),
               "psd attn: needs head dim 64 and S in {32, 64, 96, 128} (whole-head kernels) or a multiple of 64 in "
               "192 .. 4096 (streaming kernels)");
@@ -68,24 +89,29 @@ AttnArgs make_args(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
   }
   // window > 0 always takes the WINDOW copies; W >= S is the plain causal / document mask, so S stands for more
   a.window = (int32_t)std::min<int64_t>(window, qkv.size(1));
+  a.Hkv = (int32_t)hkv;  // == heads: the kernels launched without it; fewer: the GQA copies of the streaming kernels
   return a;
 }
 }  // namespace
 
+// kv_heads (0: heads): grouped-query attention, qkv [B, S, (heads + 2*kv_heads)*64] -- the query heads, the K heads,
+// the V heads of a row -- and query head h reads K/V head h / (heads / kv_heads); causal, streaming kernels only.
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal, c10::optional<at::Tensor> doc_start, int64_t window) {
+                                 bool causal, c10::optional<at::Tensor> doc_start, int64_t window, int64_t kv_heads) {
   check_docs(doc_start, causal);
   check_window(window, causal);
+  const int64_t hkv = check_kv_heads(kv_heads, heads, causal, qkv);
   check_attn(qkv, "qkv");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window);
-  at::Tensor o = at::empty({qkv.size(0), qkv.size(1), qkv.size(2) / 3}, qkv.options());
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window, hkv);
+  const int64_t dh = qkv.size(2) / (heads + 2 * hkv);
+  at::Tensor o = at::empty({qkv.size(0), qkv.size(1), heads * dh}, qkv.options());
   at::Tensor lse = at::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(at::kFloat));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.lse = lse.data_ptr<float>();
-  hipError_t e = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads))) ? launch_attn_long_fwd(a, stream_of(qkv))
-                                                                            : launch_attn_fwd(a, stream_of(qkv));
+  hipError_t e = attn_long_supported(a.S, (int)dh) ? launch_attn_long_fwd(a, stream_of(qkv))
+                                                   : launch_attn_fwd(a, stream_of(qkv));
   check_hip(e, "psd attn fwd");
   return {o, lse};
 }
@@ -100,17 +126,21 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p,
 at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal, c10::optional<at::Tensor> doc_start, int64_t window) {
+                    bool causal, c10::optional<at::Tensor> doc_start, int64_t window, int64_t kv_heads) {
   check_docs(doc_start, causal);
   check_window(window, causal);
+  const int64_t hkv = check_kv_heads(kv_heads, heads, causal, qkv);
+  // the GQA copies write no bias partials (the Llama block's QKV has no bias)
+  TORCH_CHECK(hkv == heads || !given(bias_out), "psd attn bwd: bias_out is not served with kv_heads < heads");
   at::Tensor dout = dout_in.contiguous();
   check_attn(dout, "dout");
   check_attn(qkv, "qkv");
   check_attn(o, "o");
   const c10::DeviceGuard g(qkv.device());
-  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window);
-  TORCH_CHECK(o.sizes() == dout.sizes() && o.size(0) == qkv.size(0) && o.size(1) == qkv.size(1) &&
-                  o.size(2) * 3 == qkv.size(2),
+  AttnArgs a = make_args(qkv, heads, p, seed, step, lens, grid_cap, causal, doc_start, window, hkv);
+  const int64_t dh = qkv.size(2) / (heads + 2 * hkv);
+  TORCH_CHECK(o.dim() == 3 && o.sizes() == dout.sizes() && o.size(0) == qkv.size(0) && o.size(1) == qkv.size(1) &&
+                  o.size(2) == heads * dh,
               "psd attn bwd: o / dout must be [B, S, H*Dh]");
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
                   lse.numel() == (int64_t)a.B * a.H * a.S,
@@ -121,7 +151,7 @@ at::Tensor attn_bwd(const at::Tensor& dout_in, const at::Tensor& qkv, const at::
   a.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
   a.dqkv = reinterpret_cast<uint16_t*>(dqkv.data_ptr());
   const bool bias = given(bias_out);
-  const bool is_long = attn_long_supported(a.S, (int)(qkv.size(2) / (3 * heads)));
+  const bool is_long = attn_long_supported(a.S, (int)dh);
   const int prows = is_long ? attn_long_bpart_rows(a.B, a.S) : a.B;  // partial rows: one per work item of a sequence
   at::Tensor bpart;
   if (bias) {

@@ -187,13 +187,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("stem_wgrad", &stem_wgrad);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
         py::arg("step") = py::none(), py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
-        py::arg("doc_start") = py::none(), py::arg("window") = 0);
+        py::arg("doc_start") = py::none(), py::arg("window") = 0, py::arg("kv_heads") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("heads"),
         py::arg("p"), py::arg("seed"), py::arg("step") = py::none(), py::arg("bias_out") = py::none(),
         py::arg("lens") = py::none(), py::arg("grid_cap") = 0, py::arg("causal") = false,
-        py::arg("doc_start") = py::none(), py::arg("window") = 0);
+        py::arg("doc_start") = py::none(), py::arg("window") = 0, py::arg("kv_heads") = 0);
   m.def("rope_", &rope_, py::arg("qkv"), py::arg("heads"), py::arg("cos"), py::arg("sin"), py::arg("lens") = py::none(),
-        py::arg("doc_start") = py::none(), py::arg("inverse") = false, py::arg("blocks") = 0);
+        py::arg("doc_start") = py::none(), py::arg("inverse") = false, py::arg("blocks") = 0,
+        py::arg("kv_heads") = 0);
   m.def("rms_fwd", &rms_fwd, py::arg("r"), py::arg("h") = py::none(), py::arg("gamma"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("step") = py::none(), py::arg("q8_out") = py::none(),
         py::arg("sc8_out") = py::none());

@@ -566,8 +566,10 @@ static hipError_t launch_bwd_t(const AttnArgs& a, hipStream_t st) {
    : a.lens   ? fn<nw, true, false>(a, st)                                     \
               : fn<nw, false, false>(a, st))
 
+static bool attn_gqa(const AttnArgs& a) { return a.Hkv != 0 && a.Hkv != a.H; }  // no GQA copies here either
+
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window) return hipErrorInvalidValue;  // no window copies here
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window || attn_gqa(a)) return hipErrorInvalidValue;  // no window copies here
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_fwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_fwd_t, 2);
@@ -576,7 +578,7 @@ hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   }
 }
 hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
-  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window) return hipErrorInvalidValue;  // no window copies here
+  if (!attn_supported(a.S, D) || (a.doc && !a.causal) || a.window || attn_gqa(a)) return hipErrorInvalidValue;  // no window copies here
   switch (a.S / 32) {
     case 1: return PSD_ATTN_PICK(launch_bwd_t, 1);
     case 2: return PSD_ATTN_PICK(launch_bwd_t, 2);

@@ -71,6 +71,14 @@
 // query chunk with lb > 128 kt + 127 (dK/dV) are not even staged. W >= S is passed as S.
 // With a.window == 0 the launchers pick the copies they picked before; the other instantiations
 // contain no window code (if constexpr), and AttnArgs::window sits in former padding.
+// Grouped-query attention (GQA instantiations, 1 <= a.Hkv < a.H, H % Hkv == 0, G = H / Hkv; one set, on top of
+// the window copies, which serve plain causal and documents too: the launchers pass W = S for "no window"):
+// a row of qkv / dqkv is the H query heads, the Hkv key heads, the Hkv value heads, and query head h reads
+// K/V head h / G. Forward and dQ are the window copies with that row stride and those chunk pointers -- the same
+// item, arithmetic, lse, O and dropout index per query head, so bitwise the multi-head result on the tensor
+// with every K/V head repeated G times. dK/dV takes the item (batch, K/V head, key tile) and walks the
+// query chunks once per query head of the group with the K / V fragments and the dK^T / dV^T accumulators
+// kept in registers (see the kernel). No bias partials. The other instantiations contain no GQA code.
 // Bias hand-over: bpart[(b * ceil(S/128) + tile)][3*H*64] gets the fp32 column sums of the item's dQ
 // (dQ pass) and dK, dV (dK/dV pass), summed in a fixed order; launch_colsum_final reduces the rows.
 #include <algorithm>
@@ -162,15 +170,16 @@ __device__ __forceinline__ float wave_colsum(float* red, const af32x16 (&t)[2]) 
 }  // namespace
 
 // Forward. Persistent over items (bh, query tile); LDS: K and V chunk tiles, two buffers.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false, bool GQA = false>
 __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
   static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
+  static_assert(WINDOW || !GQA, "the grouped-query copy is the window copy with the group's K/V head");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
   const int S = a.S, HD = a.H * D;
-  const int64_t qkv_rs = 3 * (int64_t)HD;
+  const int64_t qkv_rs = kv_row_stride<GQA>(a);
   const int nqt = (S + 127) >> 7;
   const int nitems = a.B * a.H * nqt;
   const float sl = a.scale * LOG2E;
@@ -191,6 +200,13 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
     int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;  // key chunks with a valid key; none for a padded tile
     if (CAUSAL) nck = min(nck, 2 * (qt + 1));        // and with a key <= the tile's last query
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
+    // the K / V head this query head reads; GQA: its group's h / G (the items of one tile index are numbered by
+    // head, so the G heads of a group are neighbours and stream the same chunks out of L2 together)
+    int koff = HD, voff = 2 * HD;  // from base to the K and the V head
+    if constexpr (GQA) {
+      koff += (h / (a.H / a.Hkv) - h) * D;
+      voff = koff + a.Hkv * D;
+    }
     // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
     // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
     // (a padded query: doc is not read, start 0). WINDOW: the same with the lower bound lb_of for the
@@ -210,8 +226,8 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
     lane_frags(qf, base + (int64_t)q * qkv_rs, vq, hh);
     u32x4 pk[2], pv[2];
     if (nck > 0) {  // the first chunk walked, into its own buffer
-      fetch_rows(pk, base + HD, qkv_rs, KC * c0, L);
-      fetch_rows(pv, base + 2 * HD, qkv_rs, KC * c0, L);
+      fetch_rows(pk, base + koff, qkv_rs, KC * c0, L);
+      fetch_rows(pv, base + voff, qkv_rs, KC * c0, L);
       put_rows(smem + (c0 & 1) * 2 * TILE_B, pk);
       put_rows(smem + (c0 & 1) * 2 * TILE_B + TILE_B, pv);
     }
@@ -225,8 +241,8 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
       const uint8_t* Vs = Ks + TILE_B;
       const bool more = c + 1 < nck;
       if (more) {  // in flight during this chunk's products
-        fetch_rows(pk, base + HD, qkv_rs, KC * (c + 1), L);
-        fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
+        fetch_rows(pk, base + koff, qkv_rs, KC * (c + 1), L);
+        fetch_rows(pv, base + voff, qkv_rs, KC * (c + 1), L);
       }
       // causal: a wave computes in chunks with 64 c <= q0 only and leaves m, l, ot alone in the others
       // (documents: nor in a chunk that ends before the start of its first query's document)
@@ -327,17 +343,18 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_kernel(AttnArgs a) {
 }
 
 // Backward, dQ pass: the forward's item and orientation; also writes D = rowsum(dO . O) to dsum.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false, bool GQA = false>
 __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __restrict__ dsum) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
   static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
+  static_assert(WINDOW || !GQA, "the grouped-query copy is the window copy with the group's K/V head");
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B];
   float* red = reinterpret_cast<float*>(smem);
   float* cs_s = reinterpret_cast<float*>(smem + RED_B);  // [4][64]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
   const int S = a.S, HD = a.H * D;
-  const int64_t qkv_rs = 3 * (int64_t)HD;
+  const int64_t qkv_rs = kv_row_stride<GQA>(a);
   const int nqt = (S + 127) >> 7;
   const int nitems = a.B * a.H * nqt;
   const float sl = a.scale * LOG2E;
@@ -358,6 +375,13 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
     int nck = 128 * qt < L ? (L + KC - 1) / KC : 0;
     if (CAUSAL) nck = min(nck, 2 * (qt + 1));
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
+    // the K / V head this query head reads; GQA: its group's h / G (the items of one tile index are numbered by
+    // head, so the G heads of a group are neighbours and stream the same chunks out of L2 together)
+    int koff = HD, voff = 2 * HD;  // from base to the K and the V head
+    if constexpr (GQA) {
+      koff += (h / (a.H / a.Hkv) - h) * D;
+      voff = koff + a.Hkv * D;
+    }
     // DOCS: the tile's first chunk (the start of its first query's document; that query is valid when
     // nck > 0), the starts of the wave's first and last valid query (wave-uniform) and the lane's own
     // (a padded query: doc is not read, start 0). WINDOW: the same with the lower bound lb_of for the
@@ -393,8 +417,8 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
     }
     u32x4 pk[2], pv[2];
     if (nck > 0) {  // the first chunk walked, into its own buffer
-      fetch_rows(pk, base + HD, qkv_rs, KC * c0, L);
-      fetch_rows(pv, base + 2 * HD, qkv_rs, KC * c0, L);
+      fetch_rows(pk, base + koff, qkv_rs, KC * c0, L);
+      fetch_rows(pv, base + voff, qkv_rs, KC * c0, L);
       put_rows(smem + (c0 & 1) * 2 * TILE_B, pk);
       put_rows(smem + (c0 & 1) * 2 * TILE_B + TILE_B, pv);
     }
@@ -407,8 +431,8 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
       const uint8_t* Vs = Ks + TILE_B;
       const bool more = c + 1 < nck;
       if (more) {
-        fetch_rows(pk, base + HD, qkv_rs, KC * (c + 1), L);
-        fetch_rows(pv, base + 2 * HD, qkv_rs, KC * (c + 1), L);
+        fetch_rows(pk, base + koff, qkv_rs, KC * (c + 1), L);
+        fetch_rows(pv, base + voff, qkv_rs, KC * (c + 1), L);
       }
       if (live && (!CAUSAL || KC * c <= q0) && (!DOCS || KC * c + KC - 1 >= dlo)) {
         const int kb0 = KC * c;
@@ -462,7 +486,7 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
       __syncthreads();
     }
     if (q0 < S) store_row(a.dqkv + ((int64_t)b * S + q) * qkv_rs + h * D, dqt, a.scale, vq, hh);
-    if (a.bpart) {  // column sums of this tile's dQ (waves without a valid query hold zeros), waves in order
+    if (!GQA && a.bpart) {  // column sums of this tile's dQ (waves without a valid query hold zeros), waves in order
       const float s = wave_colsum(red, dqt);
       cs_s[w * 64 + lane] = s;
       __syncthreads();
@@ -479,11 +503,19 @@ __global__ __launch_bounds__(NT) void attn_long_dq_kernel(AttnArgs a, float* __r
 
 // Backward, dK/dV pass: item (bh, 128-key tile), the key on the lane. LDS: Q and dO chunk tiles, two
 // buffers, plus the chunk's lse and D.
-template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false>
+// GQA copy: item (batch, K/V head, 128-key tile). The wave's K and V fragments are loaded once; the
+// query-chunk walk then runs G = H / Hkv times, once per query head of the group in ascending h, each pass
+// streaming that head's Q, dO, lse, D (and the starts, which do not depend on the head) through the same
+// two LDS buffers and hashing that head's dropout index. dK^T and dV^T stay in their fp32 accumulators
+// across the passes and are rounded once: the group's sum is formed in one workgroup in a fixed order.
+// G is uniform over the grid and every pass has the barriers of a walk of the other copies: the first
+// chunk's put + barrier follows the barrier that ends the pass before it, so no wave still reads the buffer.
+template <bool VARLEN, bool CAUSAL, bool DOCS = false, bool WINDOW = false, bool GQA = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void attn_long_dkv_kernel(AttnArgs a, const float* __restrict__ dsum) {
   static_assert(VARLEN || !CAUSAL, "the causal copy is length-aware");
   static_assert(CAUSAL || !DOCS, "the document copy is causal");
   static_assert(DOCS || !WINDOW, "the window copy is the document copy with lb_of for the start");
+  static_assert(WINDOW || !GQA, "the grouped-query copy is the window copy with a pass per query head of the group");
   constexpr int NR = DOCS ? 3 : 2;  // per-row values of a chunk: lse, D and (DOCS) the document start / lower bound
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * TILE_B + 2 * NR * KC * 4];
   float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B);  // [buf][lse, D(, doc)][64]
@@ -491,52 +523,40 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
   float* cs_s = reinterpret_cast<float*>(smem + RED_B);  // [4][2][64]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hh = lane >> 5;
   const int S = a.S, HD = a.H * D;
-  const int64_t qkv_rs = 3 * (int64_t)HD;
+  const int64_t qkv_rs = kv_row_stride<GQA>(a);
   const int nkt = (S + 127) >> 7;
-  const int nitems = a.B * a.H * nkt;
+  const int KH = GQA ? a.Hkv : a.H;     // K/V heads: the items' head axis
+  const int G = GQA ? a.H / a.Hkv : 1;  // query heads per K/V head: passes per item
+  const int nitems = a.B * KH * nkt;
   const float sl = a.scale * LOG2E;
   const uint32_t key = attn_key(a.seed, a.step);
   const bool drop = a.thresh != 0u;
 
   for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-    int bh = it / nkt, kt = it - bh * nkt;
+    int bh = it / nkt, kt = it - bh * nkt;  // (GQA: bh counts K/V heads until the passes start)
     if constexpr (CAUSAL) {  // key tile kt is seen by the query chunks from 2 kt on: the heavy tiles first
-      bh = it % (a.B * a.H);
-      kt = it / (a.B * a.H);
+      bh = it % (a.B * KH);
+      kt = it / (a.B * KH);
     }
-    const int b = bh / a.H, h = bh - b * a.H;
+    const int b = bh / KH, h = bh - b * KH;  // GQA: h is the K/V head
     const int L = item_len<VARLEN, CAUSAL>(a, b, S);
     const int k0 = 128 * kt + 32 * w, kg = k0 + (lane & 31);
     const bool live = k0 < L;  // this wave has a valid key (wave-uniform)
     const bool vk = kg < L;
     const int nqc = 128 * kt < L ? (L + KC - 1) / KC : 0;  // query chunks with a valid row
+    // query head h of the sequence; K head h is H heads on in every copy and V head h v_head_off (attn_frag.h)
     const uint16_t* base = a.qkv + (int64_t)b * S * qkv_rs + h * D;
     const uint16_t* dob = a.dout + (int64_t)b * S * HD + h * D;
 
     abf16x8 kf[4], vf[4];
     lane_frags(kf, base + HD + (int64_t)kg * qkv_rs, vk, hh);
-    lane_frags(vf, base + 2 * HD + (int64_t)kg * qkv_rs, vk, hh);
-    u32x4 pq[2], pd[2];
-    float pr = 0.f;
-    auto fetch = [&](int c) {
-      fetch_rows(pq, base, qkv_rs, KC * c, L);
-      fetch_rows(pd, dob, HD, KC * c, L);
-      if (threadIdx.x < 2 * KC) {
-        const int r = KC * c + (threadIdx.x & (KC - 1));
-        pr = r < L ? (threadIdx.x < KC ? a.lse : dsum)[(int64_t)bh * S + r] : 0.f;
-      }
-      if constexpr (DOCS) {  // the third wave: the chunk's document starts (as int bits; zeros past L)
-        if (threadIdx.x >= 2 * KC && threadIdx.x < 3 * KC) {
-          const int r = KC * c + (threadIdx.x & (KC - 1));
-          pr = __int_as_float(r < L ? lb_of<DOCS, WINDOW>(a, b, S, r) : 0);
-        }
-      }
-    };
-    auto put = [&](int bf) {
-      put_rows(smem + bf * 2 * TILE_B, pq);
-      put_rows(smem + bf * 2 * TILE_B + TILE_B, pd);
-      if (threadIdx.x < NR * KC) row_s[bf * NR * KC + threadIdx.x] = pr;
-    };
+    lane_frags(vf, base + v_head_off<GQA>(a) + (int64_t)kg * qkv_rs, vk, hh);
+    if constexpr (GQA) {  // from here on: the group's first query head, h G
+      bh = b * a.H + h * G;
+      base += (h * G - h) * D;
+      dob += (h * G - h) * D;
+    }
+    af32x16 dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};  // lane owns key kg, d = 32 dt + acc_row(i)
     const int c0 = CAUSAL ? 2 * kt : 0;  // causal: queries before the key tile see none of it (c0 < nqc when nqc > 0)
     // DOCS: the walk stops at the first chunk whose first query's document starts past the tile's last
     // key; monotone starts make every later chunk invisible too (WINDOW: its lower bound, monotone as
@@ -548,80 +568,109 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
       const uint64_t bal = __ballot(past);
       if (bal) cend = __ffsll((unsigned long long)bal) - 1;
     }
-    if (nqc > 0) {
-      fetch(c0);
-      put(c0 & 1);
-    }
-    __syncthreads();
+    // one walk per query head of the K/V head: G in the GQA copy (ascending: bh, base and dob step on after each),
+    // one elsewhere
+    for (int g = 0; g < G; ++g) {
+      u32x4 pq[2], pd[2];
+      float pr = 0.f;
+      auto fetch = [&](int c) {
+        fetch_rows(pq, base, qkv_rs, KC * c, L);
+        fetch_rows(pd, dob, HD, KC * c, L);
+        if (threadIdx.x < 2 * KC) {
+          const int r = KC * c + (threadIdx.x & (KC - 1));
+          pr = r < L ? (threadIdx.x < KC ? a.lse : dsum)[(int64_t)bh * S + r] : 0.f;
+        }
+        if constexpr (DOCS) {  // the third wave: the chunk's document starts (as int bits; zeros past L)
+          if (threadIdx.x >= 2 * KC && threadIdx.x < 3 * KC) {
+            const int r = KC * c + (threadIdx.x & (KC - 1));
+            pr = __int_as_float(r < L ? lb_of<DOCS, WINDOW>(a, b, S, r) : 0);
+          }
+        }
+      };
+      auto put = [&](int bf) {
+        put_rows(smem + bf * 2 * TILE_B, pq);
+        put_rows(smem + bf * 2 * TILE_B + TILE_B, pd);
+        if (threadIdx.x < NR * KC) row_s[bf * NR * KC + threadIdx.x] = pr;
+      };
+      if (nqc > 0) {
+        fetch(c0);
+        put(c0 & 1);
+      }
+      __syncthreads();
 
-    af32x16 dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};  // lane owns key kg, d = 32 dt + acc_row(i)
-    for (int c = c0; c < (DOCS ? cend : nqc); ++c) {
-      const uint8_t* Qs = smem + (c & 1) * 2 * TILE_B;
-      const uint8_t* dOs = Qs + TILE_B;
-      const float* lse_s = row_s + (c & 1) * NR * KC;
-      const float* D_s = lse_s + KC;
-      const int* doc_s = reinterpret_cast<const int*>(D_s + KC);  // DOCS only
-      const bool more = c + 1 < (DOCS ? cend : nqc);
-      if (more) fetch(c + 1);
-      if (live) {
-        const int qb0 = KC * c;
-        // (rolled, and two waves per SIMD asked for: unrolled the compiler interleaves both query blocks
-        // and takes 256 + ~200 registers, one wave per SIMD)
+      for (int c = c0; c < (DOCS ? cend : nqc); ++c) {
+        const uint8_t* Qs = smem + (c & 1) * 2 * TILE_B;
+        const uint8_t* dOs = Qs + TILE_B;
+        const float* lse_s = row_s + (c & 1) * NR * KC;
+        const float* D_s = lse_s + KC;
+        const int* doc_s = reinterpret_cast<const int*>(D_s + KC);  // DOCS only
+        const bool more = c + 1 < (DOCS ? cend : nqc);
+        if (more) fetch(c + 1);
+        if (live) {
+          const int qb0 = KC * c;
+          // (rolled, and two waves per SIMD asked for: unrolled the compiler interleaves both query blocks
+          // and takes 256 + ~200 registers, one wave per SIMD)
 #pragma unroll 1
-        for (int j = 0; j < 2; ++j) {
-          if (VARLEN && qb0 + 32 * j >= L) continue;
-          if (CAUSAL && qb0 + 32 * j < k0) continue;  // every query of the block is before the wave's keys
-          if constexpr (DOCS) {  // or its first query's (so every query's) document starts past them
-            if (__builtin_amdgcn_readfirstlane(doc_s[32 * j]) > k0 + 31) continue;
-          }
-          const int qfirst = CAUSAL && qb0 + 32 * j == k0 ? kg : 0;  // first query that sees this lane's key
-          af32x16 st = zero16(), dpt = zero16();  // S and dP: rows = queries qb0 + 32 j + acc_row(i), col = key kg
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            st = mfma(rowfrag(Qs, LDT * 2, 32 * j, 16 * ks), kf[ks], st);
-            dpt = mfma(rowfrag(dOs, LDT * 2, 32 * j, 16 * ks), vf[ks], dpt);
-          }
-#pragma unroll
-          for (int ks2 = 0; ks2 < 2; ++ks2) {
-            float pv[8], dv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const int i = 8 * ks2 + e;
-              const int ql = 32 * j + acc_row(i, hh), qg = qb0 + ql;
-              const float p = aexp2(fmaf(st[i], sl, -(lse_s[ql] * LOG2E)));
-              float pdv = p, dp = dpt[i];
-              if (drop) {  // the pair's other key is the neighbouring lane's: one hash per element, same bits
-                const bool kp = drop_keep(key, ((uint64_t)bh * S + qg) * S + kg, a.thresh);
-                pdv = kp ? p * a.rescale : 0.f;
-                dp = kp ? dp * a.rescale : 0.f;
-              }
-              pv[e] = pdv;
-              dv[e] = p * (dp - D_s[ql]);
-              if constexpr (VARLEN) {  // masked key or padded query: exact zeros
-                if (!vk || qg >= L || (CAUSAL && qg < qfirst)) pv[e] = dv[e] = 0.f;
-              }
-              if constexpr (DOCS) {  // the key is of an earlier document than the query
-                if (kg < doc_s[ql]) pv[e] = dv[e] = 0.f;
-              }
+          for (int j = 0; j < 2; ++j) {
+            if (VARLEN && qb0 + 32 * j >= L) continue;
+            if (CAUSAL && qb0 + 32 * j < k0) continue;  // every query of the block is before the wave's keys
+            if constexpr (DOCS) {  // or its first query's (so every query's) document starts past them
+              if (__builtin_amdgcn_readfirstlane(doc_s[32 * j]) > k0 + 31) continue;
             }
-            const abf16x8 pb = pack8(pv), dsb = pack8(dv);
+            const int qfirst = CAUSAL && qb0 + 32 * j == k0 ? kg : 0;  // first query that sees this lane's key
+            af32x16 st = zero16(), dpt = zero16();  // S and dP: rows = queries qb0 + 32 j + acc_row(i), col = key kg
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-              dvt[dt] = mfma(trfrag_accrows(dOs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), pb, dvt[dt]);
-              dkt[dt] = mfma(trfrag_accrows(Qs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), dsb, dkt[dt]);
+            for (int ks = 0; ks < 4; ++ks) {
+              st = mfma(rowfrag(Qs, LDT * 2, 32 * j, 16 * ks), kf[ks], st);
+              dpt = mfma(rowfrag(dOs, LDT * 2, 32 * j, 16 * ks), vf[ks], dpt);
+            }
+#pragma unroll
+            for (int ks2 = 0; ks2 < 2; ++ks2) {
+              float pv[8], dv[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                const int i = 8 * ks2 + e;
+                const int ql = 32 * j + acc_row(i, hh), qg = qb0 + ql;
+                const float p = aexp2(fmaf(st[i], sl, -(lse_s[ql] * LOG2E)));
+                float pdv = p, dp = dpt[i];
+                if (drop) {  // the pair's other key is the neighbouring lane's: one hash per element, same bits
+                  const bool kp = drop_keep(key, ((uint64_t)bh * S + qg) * S + kg, a.thresh);
+                  pdv = kp ? p * a.rescale : 0.f;
+                  dp = kp ? dp * a.rescale : 0.f;
+                }
+                pv[e] = pdv;
+                dv[e] = p * (dp - D_s[ql]);
+                if constexpr (VARLEN) {  // masked key or padded query: exact zeros
+                  if (!vk || qg >= L || (CAUSAL && qg < qfirst)) pv[e] = dv[e] = 0.f;
+                }
+                if constexpr (DOCS) {  // the key is of an earlier document than the query
+                  if (kg < doc_s[ql]) pv[e] = dv[e] = 0.f;
+                }
+              }
+              const abf16x8 pb = pack8(pv), dsb = pack8(dv);
+#pragma unroll
+              for (int dt = 0; dt < 2; ++dt) {
+                dvt[dt] = mfma(trfrag_accrows(dOs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), pb, dvt[dt]);
+                dkt[dt] = mfma(trfrag_accrows(Qs, LDT * 2, 32 * j + 16 * ks2, 32 * dt), dsb, dkt[dt]);
+              }
             }
           }
         }
+        if (more) put((c + 1) & 1);
+        __syncthreads();
       }
-      if (more) put((c + 1) & 1);
-      __syncthreads();
+      if constexpr (GQA) {  // the group's next query head
+        ++bh;
+        base += D;
+        dob += D;
+      }
     }
-    if (k0 < S) {
+    if (k0 < S) {  // (GQA: the group's sums, rounded here and nowhere before)
       uint16_t* out = a.dqkv + ((int64_t)b * S + kg) * qkv_rs + h * D;
       store_row(out + HD, dkt, a.scale, vk, hh);
-      store_row(out + 2 * HD, dvt, 1.f, vk, hh);
+      store_row(out + v_head_off<GQA>(a), dvt, 1.f, vk, hh);
     }
-    if (a.bpart) {
+    if (!GQA && a.bpart) {
       const float sk = wave_colsum(red, dkt);
       const float sv = wave_colsum(red, dvt);
       cs_s[(w * 2 + 0) * 64 + lane] = sk * a.scale;
@@ -644,15 +693,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void at
 bool attn_long_supported(int S, int head_dim) { return head_dim == D && S > 128 && S <= 4096 && S % 64 == 0; }
 int attn_long_bpart_rows(int B, int S) { return B * ((S + 127) / 128); }
 
+// grouped-query call: fewer K/V heads than query heads (0 stands for H)
+static bool is_gqa(const AttnArgs& a) { return a.Hkv != 0 && a.Hkv != a.H; }
+
+// item_heads: the head axis of the kernel's items (a.H; a.Hkv for the GQA dK/dV pass)
 template <typename K, typename... Extra>
-static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra... extra) {
+static hipError_t launch_long(K kernel, const AttnArgs& a, int item_heads, hipStream_t st, Extra... extra) {
   if ((a.doc || a.window) && !a.causal) return hipErrorInvalidValue;
   if (a.window < 0) return hipErrorInvalidValue;
   // persistent: the resident workgroups per CU (registers / LDS), each walks items it, it + grid, ...
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), NT, 0) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  const int64_t nitems = (int64_t)a.B * a.H * ((a.S + 127) / 128);
+  const int64_t nitems = (int64_t)a.B * item_heads * ((a.S + 127) / 128);
   int grid = (int)std::min<int64_t>(nitems, (int64_t)per_cu * cu_count());
   if (a.grid_cap > 0) grid = std::min(grid, a.grid_cap);
   if (grid < 1) return hipSuccess;
@@ -664,18 +717,40 @@ static hipError_t launch_long(K kernel, const AttnArgs& a, hipStream_t st, Extra
 // documents, causal with a window (with or without documents); with a.window == 0 the choice is the one
 // made before the window copies existed, without a.doc the one before the document copies
 #define PSD_ATTN_LONG_PICK(k, ...)                                               \
-  (a.window ? launch_long(&k<true, true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__) \
-   : a.doc ? launch_long(&k<true, true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
-   : a.causal ? launch_long(&k<true, true>, a, st __VA_OPT__(, ) __VA_ARGS__)    \
-            : a.lens ? launch_long(&k<true, false>, a, st __VA_OPT__(, ) __VA_ARGS__) \
-                     : launch_long(&k<false, false>, a, st __VA_OPT__(, ) __VA_ARGS__))
+  (a.window ? launch_long(&k<true, true, true, true>, a, a.H, st __VA_OPT__(, ) __VA_ARGS__) \
+   : a.doc ? launch_long(&k<true, true, true>, a, a.H, st __VA_OPT__(, ) __VA_ARGS__)    \
+   : a.causal ? launch_long(&k<true, true>, a, a.H, st __VA_OPT__(, ) __VA_ARGS__)    \
+            : a.lens ? launch_long(&k<true, false>, a, a.H, st __VA_OPT__(, ) __VA_ARGS__) \
+                     : launch_long(&k<false, false>, a, a.H, st __VA_OPT__(, ) __VA_ARGS__))
+
+// Grouped-query calls (is_gqa) all take the one set of GQA copies, <VARLEN, CAUSAL, DOCS, WINDOW, GQA> all
+// true: the window copies serve plain causal (a.doc null) and documents too, and a call without a window
+// passes W = S, which cuts nothing. They are causal only and write no bias partials.
+static bool gqa_args(const AttnArgs& a, AttnArgs& g) {
+  if (a.Hkv < 1 || a.Hkv > a.H || a.H % a.Hkv != 0 || !a.causal || a.bpart || a.window < 0) return false;
+  g = a;
+  if (!g.window) g.window = g.S;
+  return true;
+}
 
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t st) {
   if (!attn_long_supported(a.S, D)) return hipErrorInvalidValue;
+  if (is_gqa(a)) {
+    AttnArgs g;
+    if (!gqa_args(a, g)) return hipErrorInvalidValue;
+    return launch_long(&attn_long_fwd_kernel<true, true, true, true, true>, g, g.H, st);
+  }
   return PSD_ATTN_LONG_PICK(attn_long_fwd_kernel);
 }
 hipError_t launch_attn_long_bwd(const AttnArgs& a, float* dsum, hipStream_t st) {
   if (!attn_long_supported(a.S, D) || !dsum) return hipErrorInvalidValue;
+  if (is_gqa(a)) {
+    AttnArgs g;
+    if (!gqa_args(a, g)) return hipErrorInvalidValue;
+    hipError_t e = launch_long(&attn_long_dq_kernel<true, true, true, true, true>, g, g.H, st, dsum);
+    if (e != hipSuccess) return e;
+    return launch_long(&attn_long_dkv_kernel<true, true, true, true, true>, g, g.Hkv, st, (const float*)dsum);
+  }
   hipError_t e = PSD_ATTN_LONG_PICK(attn_long_dq_kernel, dsum);
   if (e != hipSuccess) return e;
   return PSD_ATTN_LONG_PICK(attn_long_dkv_kernel, (const float*)dsum);

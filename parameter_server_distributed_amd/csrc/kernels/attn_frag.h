@@ -120,6 +120,29 @@ __device__ __forceinline__ int lb_of(const AttnArgs& a, int b, int S, int t) {
   }
 }
 
+// Grouped-query attention (GQA copies of the streaming kernels; 1 <= a.Hkv < a.H and H % Hkv == 0, which the
+// launchers check): a row of qkv / dqkv holds the H query heads, then the Hkv key heads, then the Hkv value
+// heads, and query head h reads K/V head h / (H / Hkv). The other copies read a.H only: 3 H heads per row,
+// K head h and V head h.
+template <bool GQA>
+__device__ __forceinline__ int64_t kv_row_stride(const AttnArgs& a) {
+  if constexpr (GQA) {
+    return (int64_t)(a.H + 2 * a.Hkv) * D;
+  } else {
+    return 3 * (int64_t)(a.H * D);
+  }
+}
+// With p the address of query head kh of a row (kh < Hkv <= H: the slot exists), K head kh is at p + H * 64 in
+// every copy, and V head kh at p + v_head_off: the K block is Hkv heads long in the GQA copies, H elsewhere.
+template <bool GQA>
+__device__ __forceinline__ int v_head_off(const AttnArgs& a) {
+  if constexpr (GQA) {
+    return (a.H + a.Hkv) * D;
+  } else {
+    return 2 * (a.H * D);
+  }
+}
+
 }  // namespace
 
 }  // namespace psd

@@ -29,6 +29,12 @@ struct AttnArgs {
   const int32_t* doc;     // [B, S] device document starts or null (off); causal only: query q sees keys
                           // doc[b, q] <= key <= q. Clamped to [0, t] and only compared on the device, entries
                           // at positions >= the length are never read; the DOCS copies
+  int32_t Hkv;            // grouped-query attention: K/V heads. 0 or H: as many as query heads, the packed layout
+                          // above and the kernels launched before this field existed. 1 <= Hkv < H, H % Hkv == 0
+                          // (causal, streaming kernels only): qkv and dqkv are [B, S, (H + 2 Hkv) * 64] -- the H
+                          // query heads, the Hkv key heads, the Hkv value heads of a row -- query head h reads
+                          // K/V head h / (H / Hkv), dK / dV are summed over the group, and bpart must be null; the
+                          // GQA copies. (The struct had no padding left: appended, no other field moved.)
 };
 bool attn_supported(int S, int head_dim);
 hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t stream);
@@ -37,7 +43,7 @@ hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t stream);
 // Streaming kernels for 128 < S <= 4096, S % 64 == 0 (kernels/attention_long.hip): the same AttnArgs and
 // contracts, except that bpart has attn_long_bpart_rows(B, S) rows of [3*H*64] (one per 128-row tile
 // of a sequence) and backward takes an fp32 [B, H, S] scratch for D = rowsum(dO . O). Only they serve
-// a.window (the whole-head launchers refuse it).
+// a.window and a.Hkv < a.H (the whole-head launchers refuse both).
 bool attn_long_supported(int S, int head_dim);
 int attn_long_bpart_rows(int B, int S);
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);

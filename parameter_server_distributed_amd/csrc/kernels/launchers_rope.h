@@ -21,6 +21,9 @@ struct RopeArgs {
   int32_t B, S, H;
   int32_t inverse;      // != 0: the angle negated (the backward)
   int32_t blocks;       // 0: the launcher's own grid; > 0: at most this many workgroups
+  int32_t Hkv;          // 0 or H: as many K/V heads as Q heads. 1 <= Hkv < H, H % Hkv == 0 (grouped-query
+                        // layout): qkv is [B, S, (H + 2 Hkv) * 64], the H Q heads and the Hkv K heads of a row
+                        // (contiguous) are rotated, the Hkv V heads are never touched
 };
 hipError_t launch_rope(const RopeArgs& a, hipStream_t stream);
 

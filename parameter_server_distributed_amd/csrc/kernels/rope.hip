@@ -17,6 +17,9 @@
 // items are numbered row-major and walked by a grid-stride loop of 256-lane workgroups (<= 2048); a lane
 // keeps (b, t, item in row) and advances them by the stride's precomputed (rows, items) split, so the loop
 // has no division and nothing is sized by S; row and element offsets are 64-bit.
+// Grouped-query layout (a.Hkv < a.H): a row is the H Q heads, the Hkv K heads and the Hkv V heads; the first
+// H + Hkv heads are still contiguous, so a row has 4 (H + Hkv) items and (H + 2 Hkv) * 64 elements and nothing
+// else changes.
 //
 // Regime: pure streaming, 2/3 of qkv read and written once. Plain loads and stores: the attention reads
 // qkv next, and the tables (<= 1 MB at P = 4096) stay in L2. No LDS, no atomics, nothing summed: each
@@ -30,7 +33,7 @@ namespace psd {
 // srow / srem: the grid stride (gridDim * 256 items) as whole rows and left-over items; db / dt: srow as
 // whole sequences and left-over rows
 __global__ __launch_bounds__(256) void rope_kernel(RopeArgs a, uint32_t srem, int64_t db, int64_t dt) {
-  const uint32_t L = 8u * (uint32_t)a.H;  // items per row
+  const uint32_t L = 4u * (uint32_t)(a.H + a.Hkv);  // items per row: four per Q head and per K head
   const int64_t S = a.S, B = a.B;
   const uint32_t idx0 = blockIdx.x * 256u + threadIdx.x;  // < 2048 * 256
   const uint32_t row0 = idx0 / L;
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256) void rope_kernel(RopeArgs a, uint32_t srem, in
   int64_t b = row0 / (uint32_t)a.S;
   int64_t t = row0 - (uint32_t)b * (uint32_t)a.S;
   const float sgn = a.inverse ? -1.f : 1.f;
-  const int64_t row_elems = 192 * (int64_t)a.H;
+  const int64_t row_elems = 64 * ((int64_t)a.H + 2 * a.Hkv);
   while (b < B) {
     int64_t len = S;
     if (a.lens) {
@@ -86,11 +89,14 @@ __global__ __launch_bounds__(256) void rope_kernel(RopeArgs a, uint32_t srem, in
   }
 }
 
-hipError_t launch_rope(const RopeArgs& a, hipStream_t st) {
+hipError_t launch_rope(const RopeArgs& args, hipStream_t st) {
+  RopeArgs a = args;
+  if (a.Hkv == 0) a.Hkv = a.H;  // the kernel reads the K/V head count itself
   if (a.B < 0 || a.S < 0 || a.H <= 0 || a.blocks < 0 || a.H > (1 << 20)) return hipErrorInvalidValue;
+  if (a.Hkv < 1 || a.Hkv > a.H || a.H % a.Hkv != 0) return hipErrorInvalidValue;
   if (a.B == 0 || a.S == 0) return hipSuccess;
   if (!a.qkv || !a.cos || !a.sin) return hipErrorInvalidValue;
-  const int64_t L = 8 * (int64_t)a.H;
+  const int64_t L = 4 * ((int64_t)a.H + a.Hkv);
   const int64_t items = (int64_t)a.B * a.S * L;
   int64_t grid = stream_grid(items, 256);
   if (a.blocks > 0 && grid > a.blocks) grid = a.blocks;

@@ -200,14 +200,17 @@ std::vector<at::Tensor> stem_fwd(const at::Tensor& x, const at::Tensor& w, const
 at::Tensor stem_wgrad(const at::Tensor& x, const at::Tensor& dy);
 std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv, int64_t heads, double p, int64_t seed,
                                  c10::optional<at::Tensor> step, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                                 bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0);
+                                 bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0,
+                                 int64_t kv_heads = 0);
 at::Tensor attn_bwd(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& o, const at::Tensor& lse,
                     int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> step,
                     c10::optional<at::Tensor> bias_out, c10::optional<at::Tensor> lens, int64_t grid_cap,
-                    bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0);
+                    bool causal, c10::optional<at::Tensor> doc_start = c10::nullopt, int64_t window = 0,
+                    int64_t kv_heads = 0);
 // rotary position embedding of the Q and K heads of a packed qkv, in place (rope_ops.cpp)
 at::Tensor rope_(at::Tensor qkv, int64_t heads, const at::Tensor& cos, const at::Tensor& sin,
-                 c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks);
+                 c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks,
+                 int64_t kv_heads = 0);
 // pre-norm residual step r_new = r + dropout(h), y = RMSNorm(r_new) * gamma, and its backward (rmsnorm_ops.cpp)
 std::vector<at::Tensor> rms_fwd(const at::Tensor& r, c10::optional<at::Tensor> h, const at::Tensor& gamma, double eps,
                                 double p, int64_t seed, c10::optional<at::Tensor> step,

@@ -24,14 +24,21 @@ void check_table(const at::Tensor& t, const at::Tensor& qkv, const char* name) {
 // cos / sin: fp32 [P, 32], P >= S. lens (optional, int32 [B]): rows past a length are not touched.
 // doc_start (optional, int32 [B, S], with or without lens): positions restart at each document.
 // inverse: the angle negated (the backward). blocks > 0 bounds the grid (tests); the bits do not depend on it.
+// kv_heads (0: heads): grouped-query layout [B, S, (heads + 2*kv_heads)*64]; the Q heads and the kv_heads K heads
+// are rotated.
 at::Tensor rope_(at::Tensor qkv, int64_t heads, const at::Tensor& cos, const at::Tensor& sin,
-                 c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks) {
+                 c10::optional<at::Tensor> lens, c10::optional<at::Tensor> doc_start, bool inverse, int64_t blocks,
+                 int64_t kv_heads) {
+  // (kv_heads first: an argument error, whatever the tensor is; with heads <= 0 the check below speaks)
+  TORCH_CHECK(heads <= 0 || (kv_heads >= 0 && kv_heads <= heads && (kv_heads == 0 || heads % kv_heads == 0)),
+              "psd rope: kv_heads must be 0 (as many as heads) or a divisor of heads = ", heads, ", got ", kv_heads);
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous() && aligned16(qkv),
               "psd rope: qkv must be a contiguous bf16 device tensor");
   TORCH_CHECK(heads > 0 && heads <= (1 << 20), "psd rope: heads must be positive, got ", heads);
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64,
-              "psd rope: qkv must be [B, S, 3*heads*64] (head dim 64), got last dim ", qkv.dim() == 3 ? qkv.size(2) : -1,
-              " with heads = ", heads);
+  const int64_t hkv = kv_heads == 0 ? heads : kv_heads;
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (heads + 2 * hkv) * 64,
+              "psd rope: qkv must be [B, S, (heads + 2*kv_heads)*64] (3*heads*64 without kv_heads; head dim 64), got "
+              "last dim ", qkv.dim() == 3 ? qkv.size(2) : -1, " with heads = ", heads, ", kv_heads = ", kv_heads);
   TORCH_CHECK(qkv.size(0) <= INT32_MAX && qkv.size(1) <= INT32_MAX, "psd rope: qkv has too many rows");
   check_table(cos, qkv, "cos");
   check_table(sin, qkv, "sin");
@@ -57,6 +64,7 @@ at::Tensor rope_(at::Tensor qkv, int64_t heads, const at::Tensor& cos, const at:
   a.B = (int32_t)qkv.size(0);
   a.S = (int32_t)qkv.size(1);
   a.H = (int32_t)heads;
+  a.Hkv = (int32_t)hkv;
   a.inverse = inverse ? 1 : 0;
   a.blocks = (int32_t)blocks;
   check_hip(launch_rope(a, stream_of(qkv)), "psd rope");

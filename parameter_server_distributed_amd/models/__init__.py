@@ -104,7 +104,7 @@ def build(name: str, device, dtype=torch.bfloat16, num_classes: int | None = Non
                              window=kw.get("window"),
                              pos=kw.get("pos", "learned"), rope_base=kw.get("rope_base", 10000.0),
                              arch=kw.get("arch", "gpt"), ffn=kw.get("ffn"),
-                             fused_head=bool(kw.get("fused_head", False))),
+                             fused_head=bool(kw.get("fused_head", False)), kv_heads=kw.get("kv_heads")),
                     device, dtype)
         min_len = kw.get("min_seq_len")  # padded batches with lengths in [min_seq_len, seq_len]
         pack = kw.get("pack_docs")  # (lo, hi): rows packed with documents of lengths in [lo, hi]

@@ -56,8 +56,10 @@ VOCAB = 40512
 
 class GPTForLM(nn.Module):
     def __init__(self, layers=12, hidden=768, heads=12, vocab=VOCAB, max_pos=512, dropout=0.1, fp8=False,
-                 window=None, pos="learned", rope_base=10000.0, arch="gpt", ffn=None, fused_head=False):
+                 window=None, pos="learned", rope_base=10000.0, arch="gpt", ffn=None, fused_head=False, kv_heads=None):
         super().__init__()
+        if kv_heads is not None and arch != "llama":
+            raise ValueError("GPTForLM: kv_heads (grouped-query attention) is built for arch='llama' only")
         if pos not in ("learned", "rope"):
             raise ValueError(f"GPTForLM: pos must be 'learned' or 'rope', got {pos!r}")
         if arch not in ("gpt", "llama"):
@@ -85,8 +87,9 @@ class GPTForLM(nn.Module):
             from .llama_block import LlamaLayer, default_ffn
 
             ffn = default_ffn(hidden) if ffn is None else int(ffn)
-            self.layers = nn.ModuleList([LlamaLayer(hidden, heads, ffn, dropout, i, window=window, rope=rope, fp8=fp8)
-                                         for i in range(layers)])
+            # kv_heads: grouped-query attention in every block (models/llama_block.py); None: multi-head
+            self.layers = nn.ModuleList([LlamaLayer(hidden, heads, ffn, dropout, i, window=window, rope=rope, fp8=fp8,
+                                                    kv_heads=kv_heads) for i in range(layers)])
             # the last block's branch joins the stream here; seeds 2 * i + 1, 2 * i + 2 belong to block i
             self.norm_f = FusedAddRMSNorm(hidden, eps=1e-6, p=dropout, seed=2 * layers + 1)
             if fp8:

@@ -43,22 +43,33 @@ def default_ffn(hidden: int) -> int:
 
 class LlamaLayer(nn.Module):
     def __init__(self, hidden=768, heads=12, ffn=2048, dropout=0.1, index=0, window=None, rope=None, eps=1e-6,
-                 fp8=False):
+                 fp8=False, kv_heads=None):
         super().__init__()
         if not (fp8 is False or (isinstance(fp8, str) and fp8 == "mx")):
             raise ValueError(f"LlamaLayer: fp8 must be False or 'mx', got {fp8!r}")
+        # kv_heads: grouped-query attention (ops/attention.py) -- the QKV Linear writes heads query heads and
+        # kv_heads key and value heads of 64 per row; None: as many as heads, the block without the argument
+        if kv_heads is not None and (int(kv_heads) < 1 or heads % int(kv_heads) != 0):
+            raise ValueError(f"LlamaLayer: kv_heads must divide heads = {heads}, got {kv_heads}")
         # rope: (max_pos, base) -- rotary position embedding of Q and K between the QKV Linear and the
         # attention (ops/rope.py); None: no such module
         self.rot = None
         if rope is not None:
             from ..ops.rope import RotaryQK
 
-            self.rot = RotaryQK(heads, int(rope[0]), float(rope[1]))
+            self.rot = RotaryQK(heads, int(rope[0]), float(rope[1]), kv_heads=kv_heads)
         self.heads = heads
+        qkv_out = 3 * hidden
+        if kv_heads is not None:
+            if hidden != heads * 64:
+                raise ValueError(f"LlamaLayer: kv_heads needs head dim 64 (hidden = heads * 64), got hidden = {hidden}, "
+                                 f"heads = {heads}")
+            qkv_out = (heads + 2 * int(kv_heads)) * 64
         # seeds as BertLayer's: attention 1000 + index, the two norm sites 2 * index + 1 and 2 * index + 2
         self.norm1 = FusedAddRMSNorm(hidden, eps=eps, p=dropout, seed=2 * index + 1)
-        self.qkv = MfmaLinear(hidden, 3 * hidden, bias=False, fp8=fp8)
-        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=True, window=window)
+        self.qkv = MfmaLinear(hidden, qkv_out, bias=False, fp8=fp8)
+        self.attn = FusedSelfAttention(heads, p=dropout, seed=1000 + index, causal=True, window=window,
+                                       kv_heads=kv_heads)
         self.proj = MfmaLinear(hidden, hidden, bias=False, fp8=fp8)
         self.norm2 = FusedAddRMSNorm(hidden, eps=eps, p=dropout, seed=2 * index + 2)
         # gate_proj and up_proj as one Linear: its output is the packed [.., 2 ffn] the activation reads in place

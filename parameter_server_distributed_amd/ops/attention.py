@@ -42,6 +42,16 @@ a window's reach; ``W >= S`` cuts nothing and takes exactly the path of a module
 whole-head kernels have none: S <= 128 with ``W < S`` takes SDPA with the band AND-ed into the mask. The
 native ops take ``window`` last (0: off) and raise on a window without ``causal`` or at an S <= 128.
 
+Grouped-query attention: ``FusedSelfAttention(heads, ..., causal=True, kv_heads=Hkv)`` with ``Hkv`` a divisor of
+``heads`` takes the packed ``[B, S, (heads + 2*Hkv)*64]`` -- per row the ``heads`` query heads, then the ``Hkv`` key
+heads, then the ``Hkv`` value heads -- and query head ``h`` attends with K/V head ``h // (heads // Hkv)`` (Llama's
+``repeat_interleave``). Output, ``lse``, masks, ``lens``, ``doc_start``, ``window`` and the dropout mask (indexed by
+the query head) are those of the multi-head call on the expanded tensor, bit for bit; ``dK`` / ``dV`` are summed
+over a group's query heads in fp32 inside one workgroup and rounded once. The streaming kernels have one set of
+GQA copies (feature ``attn_gqa``, S = 192 .. 4096, causal only, no QKV-bias hand-over); S <= 128,
+``causal=False`` and everything else SDPA takes run SDPA on K and V repeated per group. ``kv_heads=None`` or
+``heads`` is the module without the argument.
+
 CPU tensors, other dtypes, head dims != 64 or S not in {32, 64, 96, 128} or {192, 256, .., 4096} use SDPA
 -- the reference the tests compare against -- with the same length, causal, document and window
 semantics.
@@ -96,11 +106,15 @@ class _AttnFn(torch.autograd.Function):
     def forward(ctx, qkv, mod, p, lens=None, doc_start=None, window=None):
         # qkv straight from the latest forward of an MfmaLinear with a bias and no activation: backward also
         # sums dqkv's columns -- that Linear's bias gradient -- and hands it over
-        ctx.src = bias_src(qkv) if _feat("attn_bias") else None
+        # (grouped-query attention: the GQA copies write no bias partials, and the native op refuses a bias_out)
+        ctx.src = bias_src(qkv) if _feat("attn_bias") and mod.kv_heads == mod.heads else None
         qkv = qkv.contiguous()
         # window: None on every path that existed before it (no argument passed), else the W of the window copies
         ctx.win = () if window is None else (int(window),)
-        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens, 0, mod.causal, doc_start, *ctx.win)
+        # kv_heads: passed only by a grouped-query module
+        ctx.kv = {} if mod.kv_heads == mod.heads else {"kv_heads": mod.kv_heads}
+        o, lse = native().attn_fwd(qkv, mod.heads, p, mod.seed, mod.step, lens, 0, mod.causal, doc_start, *ctx.win,
+                                   **ctx.kv)
         ctx.mod, ctx.p, ctx.lens, ctx.doc = mod, p, lens, doc_start
         ctx.save_for_backward(qkv, o, lse)
         return o
@@ -111,7 +125,7 @@ class _AttnFn(torch.autograd.Function):
         mod, src = ctx.mod, ctx.src
         db = grad_out(src.lin, src.lin.bias, like=src.lin.bias) if src is not None else None
         dqkv = native().attn_bwd(do, qkv, o, lse, mod.heads, ctx.p, mod.seed, mod.step, db, ctx.lens, 0, mod.causal,
-                                 ctx.doc, *ctx.win)
+                                 ctx.doc, *ctx.win, **ctx.kv)
         if src is not None:
             hand_bias(src, dqkv, db)
         return dqkv, None, None, None, None, None
@@ -125,14 +139,19 @@ class FusedSelfAttention(nn.Module):
     kernels at the kernel shapes; a bidirectional one has no kernel for it and takes SDPA with the
     symmetric same-document mask."""
 
-    def __init__(self, heads: int, p: float = 0.1, seed: int = 0, causal: bool = False, window: int | None = None):
+    def __init__(self, heads: int, p: float = 0.1, seed: int = 0, causal: bool = False, window: int | None = None,
+                 kv_heads: int | None = None):
         super().__init__()
         if window is not None:
             if int(window) < 1:
                 raise ValueError(f"window must be >= 1 (the query's own key included) or None, got {window}")
             if not causal:
                 raise ValueError("window needs causal=True: there is no symmetric window")
+        if kv_heads is not None and (int(kv_heads) < 1 or heads % int(kv_heads) != 0):
+            raise ValueError(f"kv_heads must divide heads = {heads} (or be None: as many as heads), got {kv_heads}")
         self.heads = heads
+        # K/V heads (module docstring, "Grouped-query attention"); == heads: every path as without the argument
+        self.kv_heads = heads if kv_heads is None else int(kv_heads)
         self.p = p
         self.causal = bool(causal)
         self.window = None if window is None else int(window)
@@ -142,7 +161,8 @@ class FusedSelfAttention(nn.Module):
     def _kernel_ok(self, qkv) -> bool:
         B, S, E = qkv.shape
         return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0
-                and E // (3 * self.heads) == 64 and S % 32 == 0 and 32 <= S <= 128)
+                and E // (3 * self.heads) == 64 and S % 32 == 0 and 32 <= S <= 128
+                and self.kv_heads == self.heads)  # the whole-head kernels have no grouped-query copies
 
     @staticmethod
     def long_kernel_shape_ok(S: int, head_dim: int) -> bool:
@@ -156,9 +176,12 @@ class FusedSelfAttention(nn.Module):
 
     def _long_kernel_ok(self, qkv) -> bool:
         B, S, E = qkv.shape
-        if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % (3 * self.heads) == 0 and _feat("attn_long")):
+        nh = self.heads + 2 * self.kv_heads  # heads of a row: 3 * heads without grouped-query attention
+        if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and E % nh == 0 and _feat("attn_long")):
             return False
-        dh = E // (3 * self.heads)
+        if self.kv_heads != self.heads and not (self.causal and _feat("attn_gqa")):
+            return False  # the GQA copies are causal
+        dh = E // nh
         return self.long_kernel_shape_ok(S, dh) or (self.xlong_kernel_shape_ok(S, dh) and _feat("attn_xlong"))
 
     def forward(self, qkv, lens=None, doc_start=None):
@@ -175,8 +198,14 @@ class FusedSelfAttention(nn.Module):
     def _sdpa(self, qkv, lens, p, doc_start=None, window=None):
         """``F.scaled_dot_product_attention`` on transposed views (what no kernel takes; tools/attn_bench.py --sdpa)."""
         B, S, E = qkv.shape
-        H = self.heads
-        q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)
+        H, Hkv = self.heads, self.kv_heads
+        if Hkv == H:
+            q, k, v = qkv.view(B, S, 3, H, E // (3 * H)).permute(2, 0, 3, 1, 4).unbind(0)
+        else:  # grouped-query: [Q heads | K heads | V heads] per row, each K/V head repeated for its group's queries
+            dh = E // (H + 2 * Hkv)
+            q, k, v = (t.reshape(B, S, -1, dh).transpose(1, 2) for t in qkv.split((H * dh, Hkv * dh, Hkv * dh), -1))
+            k, v = (t.repeat_interleave(H // Hkv, dim=1) for t in (k, v))
+            E = 3 * H * dh  # of the expanded tensor: the rest is the multi-head path
         if lens is None and doc_start is None and window is None:
             a = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=self.causal)
             return a.transpose(1, 2).reshape(B, S, E // 3)

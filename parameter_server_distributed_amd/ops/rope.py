@@ -49,14 +49,27 @@ def _positions(B: int, S: int, device, doc_start):
     return t - torch.minimum(doc_start.long().clamp(min=0), t)
 
 
-def rope_ref(qkv, heads: int, cos, sin, lens=None, doc_start=None, inverse: bool = False):
+def _kv(heads: int, kv_heads) -> int:
+    """K/V heads of the packed layout: ``heads`` without ``kv_heads`` (None or 0), else a divisor of ``heads``."""
+    if not kv_heads:
+        return int(heads)
+    if int(kv_heads) < 1 or heads % int(kv_heads) != 0:
+        raise ValueError(f"kv_heads must divide heads = {heads} (or be None: as many as heads), got {kv_heads}")
+    return int(kv_heads)
+
+
+def rope_ref(qkv, heads: int, cos, sin, lens=None, doc_start=None, inverse: bool = False, kv_heads=None):
     """The torch composite with the semantics of the native ``rope_``, on any device and dtype, out of
     place: fp32 maths on the given tables (fp64 for an fp64 ``qkv``), one rounding to ``qkv``'s dtype,
     and a copy in which rows past a length, rows at position 0 and the V third are passed through. The
-    CPU path of ``RotaryQK`` and the yardstick of the tests."""
-    if qkv.dim() != 3 or qkv.shape[2] != 3 * heads * HEAD_DIM:
-        raise ValueError(f"rope_ref: qkv must be [B, S, 3*heads*64], got {tuple(qkv.shape)} with heads = {heads}")
+    CPU path of ``RotaryQK`` and the yardstick of the tests. ``kv_heads``: the grouped-query layout
+    ``[B, S, (heads + 2*kv_heads)*64]``, the ``heads`` Q heads and the ``kv_heads`` K heads rotated."""
+    hkv = _kv(heads, kv_heads)
+    if qkv.dim() != 3 or qkv.shape[2] != (heads + 2 * hkv) * HEAD_DIM:
+        raise ValueError(f"rope_ref: qkv must be [B, S, (heads + 2*kv_heads)*64] (3*heads*64 without kv_heads), got "
+                         f"{tuple(qkv.shape)} with heads = {heads}, kv_heads = {kv_heads}")
     B, S, E = qkv.shape
+    nrot = (heads + hkv) * HEAD_DIM  # the Q and K heads of a row: 2 E / 3 without kv_heads
     if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != HEAD_DIM // 2 or cos.shape[0] < S:
         raise ValueError(f"rope_ref: cos / sin must be [P, 32] with P >= S = {S}, got {tuple(cos.shape)}, "
                          f"{tuple(sin.shape)}")
@@ -69,16 +82,17 @@ def rope_ref(qkv, heads: int, cos, sin, lens=None, doc_start=None, inverse: bool
     s = sin.to(mt)[pos][:, :, None, :]
     if inverse:
         s = -s
-    qk = qkv[:, :, :2 * E // 3].reshape(B, S, 2 * heads, HEAD_DIM)
+    qk = qkv[:, :, :nrot].reshape(B, S, heads + hkv, HEAD_DIM)
     x1, x2 = qk[..., :HEAD_DIM // 2].to(mt), qk[..., HEAD_DIM // 2:].to(mt)
     rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(qkv.dtype)
     # a select, not a blend: what a passed-through row holds (NaN included) never enters the result
-    rot = torch.where(keep[:, :, None, None], rot, qk).reshape(B, S, 2 * E // 3)
-    return torch.cat([rot, qkv[:, :, 2 * E // 3:]], dim=-1)
+    rot = torch.where(keep[:, :, None, None], rot, qk).reshape(B, S, nrot)
+    return torch.cat([rot, qkv[:, :, nrot:]], dim=-1)
 
 
-def _kernel_ok(t, heads: int) -> bool:
-    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 3 and t.shape[2] == 3 * heads * HEAD_DIM
+def _kernel_ok(t, heads: int, kv_heads: int | None = None) -> bool:
+    nh = heads + 2 * (kv_heads or heads)
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 3 and t.shape[2] == nh * HEAD_DIM
             and t.is_contiguous() and t.data_ptr() % 16 == 0)
 
 
@@ -89,19 +103,21 @@ class _RopeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, mod, lens, doc_start):
         ctx.mark_dirty(qkv)
-        native().rope_(qkv, mod.heads, mod.cos, mod.sin, lens, doc_start, False, 0)
+        native().rope_(qkv, mod.heads, mod.cos, mod.sin, lens, doc_start, False, 0, **mod._kv_kw)
         ctx.mod, ctx.lens, ctx.doc = mod, lens, doc_start
         return qkv
 
     @staticmethod
     def backward(ctx, g):
         mod = ctx.mod
-        if g.requires_grad or not _kernel_ok(g, mod.heads):
+        if g.requires_grad or not _kernel_ok(g, mod.heads, mod.kv_heads):
             # a gradient that is part of a graph (create_graph), expanded or otherwise not the kernel's layout
-            return rope_ref(g, mod.heads, mod.cos, mod.sin, ctx.lens, ctx.doc, True), None, None, None
+            return (rope_ref(g, mod.heads, mod.cos, mod.sin, ctx.lens, ctx.doc, True, mod.kv_heads), None, None,
+                    None)
         if not mod.grad_in_place:
             g = g.clone()
-        return native().rope_(g, mod.heads, mod.cos, mod.sin, ctx.lens, ctx.doc, True, 0), None, None, None
+        return (native().rope_(g, mod.heads, mod.cos, mod.sin, ctx.lens, ctx.doc, True, 0, **mod._kv_kw), None, None,
+                None)
 
 
 class RotaryQK(nn.Module):
@@ -135,11 +151,15 @@ class RotaryQK(nn.Module):
 
     _psd_fp32_buffers = True  # models.prepare() keeps the tables fp32
 
-    def __init__(self, heads: int, max_pos: int, base: float = 10000.0):
+    def __init__(self, heads: int, max_pos: int, base: float = 10000.0, kv_heads: int | None = None):
         super().__init__()
         if int(heads) < 1:
             raise ValueError(f"RotaryQK: heads must be >= 1, got {heads}")
         self.heads = int(heads)
+        # grouped-query layout [B, S, (heads + 2*kv_heads)*64]: the Q heads and the kv_heads K heads are rotated;
+        # None or heads: the module (and the native call) without the argument
+        self.kv_heads = _kv(self.heads, kv_heads)
+        self._kv_kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}
         self.max_pos = int(max_pos)
         self.base = float(base)
         self.grad_in_place = True
@@ -157,14 +177,15 @@ class RotaryQK(nn.Module):
         return f"heads={self.heads}, max_pos={self.max_pos}, base={self.base}"
 
     def forward(self, qkv, lens=None, doc_start=None):
-        if qkv.dim() != 3 or qkv.shape[2] != 3 * self.heads * HEAD_DIM:
-            raise ValueError(f"RotaryQK: qkv must be [B, S, 3*{self.heads}*64], got {tuple(qkv.shape)}")
+        if qkv.dim() != 3 or qkv.shape[2] != (self.heads + 2 * self.kv_heads) * HEAD_DIM:
+            raise ValueError(f"RotaryQK: qkv must be [B, S, 3*{self.heads}*64] "
+                             f"([B, S, ({self.heads} + 2*{self.kv_heads})*64] with kv_heads), got {tuple(qkv.shape)}")
         if qkv.shape[1] > self.max_pos:
             raise ValueError(f"RotaryQK: S = {qkv.shape[1]} exceeds max_pos = {self.max_pos}")
-        if _kernel_ok(qkv, self.heads) and _feat("rope"):
+        if _kernel_ok(qkv, self.heads, self.kv_heads) and _feat("rope"):
             if qkv.is_leaf and qkv.requires_grad:  # autograd allows no in-place update of such a leaf
                 qkv = qkv.clone()
             out = _RopeFn.apply(qkv, self, lens, doc_start)
             drop_tag(out)  # mark_dirty returns the same Python object, the producing Linear's tag included
             return out
-        return rope_ref(qkv, self.heads, self.cos, self.sin, lens, doc_start)
+        return rope_ref(qkv, self.heads, self.cos, self.sin, lens, doc_start, kv_heads=self.kv_heads)

@@ -125,6 +125,9 @@ FEATURES: dict[str, tuple[bool, str]] = {
                         "transposed views there, as for every other S > 128"),
     "attn_xlong": (True, "the streaming fused attention kernels also at S = 576 .. 4096 (multiples of 64; needs "
                          "attn_long); off: S > 512 goes back to SDPA on transposed views"),
+    "attn_gqa": (True, "grouped-query attention (FusedSelfAttention(kv_heads < heads), causal) on the GQA copies of the "
+                       "streaming kernels at S = 192 .. 4096 (needs attn_long / attn_xlong); off: SDPA on K and V "
+                       "repeated per group"),
     "rope": (True, "in-place rotary position embedding kernel on the packed QKV (ops/rope.py RotaryQK); off: the "
                    "out-of-place torch composite rope_ref"),
     "head_xent": (True, "fused LM head + cross-entropy kernels where ops/loss.linear_cross_entropy is called "

@@ -9,6 +9,7 @@ default shape is BERT-base pre-training (B 256, S 128, 12 heads of 64).
   python tools/attn_bench.py --seq 512 --batch 64 --causal # the causal instantiations (keys <= q)
   python tools/attn_bench.py --seq 512 --batch 64 --docs 128 --sdpa  # packed documents of mean length 128
   python tools/attn_bench.py --seq 2048 --batch 8 --causal --window 256 --sdpa  # sliding window of 256 keys
+  python tools/attn_bench.py --seq 1024 --batch 16 --causal --kv-heads 4 --sdpa  # grouped-query: 12 Q, 4 K/V heads
 
 With --min-len the bytes count the valid rows only (what the variable-length kernels have to move)
 and the FLOP rate counts the valid (query, key) pairs. With --causal the FLOP rate counts the visible
@@ -66,12 +67,19 @@ def main():
     ap.add_argument("--window", type=int, default=None,
                     help="sliding window: query q sees the W keys up to and including q (needs --causal)")
     ap.add_argument("--windows", type=int, default=None, help="timing windows per figure (default 1, with --sdpa 5)")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="grouped-query attention: K/V heads, a divisor of 12 (needs --causal and S >= 192); "
+                         "with --sdpa the SDPA path runs on the tensor expanded to 12 K/V heads")
     args = ap.parse_args()
     C = native()
     dev = torch.device("cuda")
     B, S, H, D = args.batch, args.seq, 12, 64
+    K = H if args.kv_heads is None else args.kv_heads
+    if K < 1 or H % K != 0 or (K != H and not args.causal):
+        ap.error(f"--kv-heads must divide {H} and needs --causal")
+    kw = {} if K == H else {"kv_heads": K}  # the last keyword of attn_fwd / attn_bwd, passed only when it says something
     nwin = args.windows if args.windows is not None else (5 if args.sdpa else 1)
-    qkv = (torch.randn(B, S, 3 * H * D, device=dev) * 0.5).to(torch.bfloat16)
+    qkv = (torch.randn(B, S, (H + 2 * K) * D, device=dev) * 0.5).to(torch.bfloat16)
     do = torch.randn(B, S, H * D, device=dev).to(torch.bfloat16)
     step = torch.tensor([3], device=dev, dtype=torch.int64)
     el = B * S * H * D * 2  # bytes of one [B, S, H, 64] bf16 tensor
@@ -120,32 +128,38 @@ def main():
         extra = (extra[0] if extra else None, args.window)
         print(f"window {args.window}: {flop_f / (4 * H * D) / (B * S):.1f} visible keys per query")
     it = args.iters
-    print(f"B {B}, S {S}, H {H}, D {D}{', causal' if causal else ''}; {nwin} window(s) of {it} calls")
+    print(f"B {B}, S {S}, H {H}{f', KV heads {K}' if K != H else ''}, D {D}{', causal' if causal else ''}; "
+          f"{nwin} window(s) of {it} calls")
     head = "| p | fwd us | fwd TB/s | fwd TF/s | bwd us | bwd TB/s | bwd TF/s |"
     if args.sdpa:
         from parameter_server_distributed_amd.ops.attention import FusedSelfAttention
 
         mod = FusedSelfAttention(H, causal=causal).to(dev)
-        xg = qkv.clone().requires_grad_(True)
+        xg = qkv
+        if K != H:  # the multi-head tensor a user without the GQA copies would build: each K/V head G times
+            q, k, v = qkv.split((H * D, K * D, K * D), -1)
+            k, v = (t.view(B, S, K, D).repeat_interleave(H // K, dim=2).view(B, S, H * D) for t in (k, v))
+            xg = torch.cat([q, k, v], -1)
+        xg = xg.clone().requires_grad_(True)
         head += " sdpa fwd us | sdpa bwd us | fwd+bwd us | sdpa fwd+bwd us |"
     print(head)
     print("|" + "---:|" * (head.count("|") - 1))
     for p in (0.0, 0.1):
-        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra)
+        o, lse = C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra, **kw)
         tf, tb, sf, sb = [], [], [], []
         for _ in range(nwin):  # the paths alternate inside a window
-            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra), it))
+            tf.append(t_us(lambda: C.attn_fwd(qkv, H, p, 7, step, lens, 0, causal, *extra, **kw), it))
             if args.sdpa:
                 sf.append(t_us(lambda: mod._sdpa(xg, lens, p, *extra), it))
-            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens, 0, causal, *extra), it))
+            tb.append(t_us(lambda: C.attn_bwd(do, qkv, o, lse, H, p, 7, step, None, lens, 0, causal, *extra, **kw), it))
             if args.sdpa:
                 so = mod._sdpa(xg, lens, p, *extra)
                 sb.append(t_us(lambda: torch.autograd.grad(so, xg, do, retain_graph=True), it))
                 del so
         mf, mb = statistics.median(tf), statistics.median(tb)
-        # fwd: read q, k, v; write o (+ lse). bwd: read q, k, v, o, dO; write dq, dk, dv
-        row = (f"| {p} | {_fmt(tf)} | {4 * el / mf / 1e6:.2f} | {flop_f / mf / 1e6:.0f} | {_fmt(tb)} | "
-               f"{8 * el / mb / 1e6:.2f} | {2.5 * flop_f / mb / 1e6:.0f} |")
+        # fwd: read q, k, v; write o (+ lse). bwd: read q, k, v, o, dO; write dq, dk, dv (k, v, dk, dv: K / H of el each)
+        row = (f"| {p} | {_fmt(tf)} | {(2 + 2 * K / H) * el / mf / 1e6:.2f} | {flop_f / mf / 1e6:.0f} | {_fmt(tb)} | "
+               f"{(4 + 4 * K / H) * el / mb / 1e6:.2f} | {2.5 * flop_f / mb / 1e6:.0f} |")
         if args.sdpa:
             row += (f" {_fmt(sf)} | {_fmt(sb)} | {_fmt([a + b for a, b in zip(tf, tb)])} | "
                     f"{_fmt([a + b for a, b in zip(sf, sb)])} |")
